@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark of the propagation path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (SURVEY.md 8d / BASELINE.json configs[1]): personalized PageRank, alpha = 0.85, to tol = 1e-6 with the
 L1 residual (the "headline" stopping rule), on a synthetic RMAT graph (a, b, c, d) =
@@ -164,6 +164,24 @@ def allcore_cpu_gteps(MT, nnz, repeats=3):
                 sample=f"{repeats} SpMV of the same graph, OpenMP pull kernel over CSR(M^T), fp64")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy in float32 (the engine's storage precision), so that two builds can be
+    compared output for output.  An array over the 64 MB budget is written as a fixed sample: the entries at
+    DIR/<name>_index.npy (float64 positions, seeded, sorted), the same for every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, vec in arrays.items():
+        values = vec.numpy(np.float32) if hasattr(vec, "numpy") else np.asarray(vec, dtype=np.float32)
+        values = values.reshape(-1)
+        if values.nbytes > DUMP_LIMIT_BYTES:
+            index = np.sort(np.random.default_rng(0).choice(values.size, size=DUMP_LIMIT_BYTES // 12, replace=False))
+            values = values[index]
+            np.save(os.path.join(out_dir, name + "_index.npy"), index.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), values)
+
+
 def single_gpu(args):
     import pygrank_amd as pg
     from pygrank_amd import _lib as L
@@ -213,6 +231,8 @@ def single_gpu(args):
     L.check(lib.pgh_sync())
     elapsed = time.perf_counter() - t0
     gteps = nnz * spmv_total / elapsed / 1e9
+    if getattr(args, "dump_outputs", None):         # what the last timed step handed its caller, read back after the clock stopped
+        dump_outputs(args.dump_outputs, dict(ranks=ranks.np))
 
     # ---- roofline leg: HIP events around every launch of the dominant kernel (one extra, untimed run)
     L.check(lib.pgh_profile_reset())
@@ -980,7 +1000,13 @@ def main():
     ap.add_argument("--no-symmetric", action="store_true", help="skip the symmetrised-graph side measurement")
     ap.add_argument("--no-same-graph", action="store_true", help="N > 1: skip the single-GPU run of the same graph on rank 0")
     ap.add_argument("--force-partitioned", action="store_true", help="run the row-partitioned path even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ranks of the last timed step as DIR/ranks.npy (float32; --gpus 1 only; dumps/<label> is ignored by git)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_partitioned or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is supported on the single-GPU path (--gpus 1) only")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:       # no launcher around us: become the launcher's parent
         sys.exit(spawn_ranks(args))

@@ -889,6 +889,11 @@ class DeviceGraph:
         L.check(L.lib().pgh_resident_in(self._h, vec._h, float(hole), y._h, xg._h if xg is not None else None))
         res = _Resident(self, y, xg)
         if _kind(vec) in _MEMORY_KINDS and vec._keepalive is None:
+            # copies of vectors that have died go before any live one: whether a new vector happens to reuse a dead one's id must
+            # not decide which live copy is evicted
+            for key in [key for key, entry in self._resident.items() if entry[0]() is None]:
+                del self._resident[key]
+            self._resident.pop(id(vec), None)
             while len(self._resident) >= 6:
                 self._resident.pop(next(iter(self._resident)))
             self._resident[id(vec)] = (weakref.ref(vec), res, hole)

@@ -36,3 +36,37 @@ def test_single_gpu_leg_fields(host_engine):
     assert line["roofline"]["frac_of_measured_copy"] is not None and "residual" in line["roofline"]["kernel"]
     assert line["cpu_baseline"]["all_cores"]["cores"] >= 1
     assert line["secondary"]["heat_kernel_t5_31_iterations"]["spmv_per_run"] in (29, 30)
+
+
+def test_dump_outputs_are_the_last_timed_step(host_engine, tmp_path):
+    """--dump-outputs DIR: the ranks of the last timed step as float32 DIR/ranks.npy, bit for bit the same from run to run; --steps is
+    the number of timed steps, and a run with one step fewer ends on another personalization."""
+    import numpy as np
+
+    def dump(steps, tag):
+        out_dir = tmp_path / tag
+        args = argparse.Namespace(gpus=1, steps=steps, warmup=1, scale=10, ef=8, no_cpu=True, no_secondary=True, no_symmetric=True,
+                                  dump_outputs=str(out_dir))
+        line = bench.single_gpu(args)
+        assert line["steps"] == steps and len(line["config"]["iterations_per_step"]) == steps and line["ms_per_step"] > 0
+        assert sorted(p.name for p in out_dir.iterdir()) == ["ranks.npy"]
+        ranks = np.load(out_dir / "ranks.npy")
+        assert ranks.dtype == np.float32 and ranks.shape == (line["config"]["n"],)
+        return ranks
+
+    first, again, shorter = dump(3, "a"), dump(3, "b"), dump(2, "c")
+    assert np.array_equal(first, again)
+    assert np.all(np.isfinite(first)) and first.sum() > 0
+    assert not np.array_equal(first, shorter)
+
+
+def test_dump_outputs_keeps_to_the_budget(tmp_path):
+    import numpy as np
+    big = np.arange(bench.DUMP_LIMIT_BYTES // 4 + 10, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path), dict(vec=big))
+    values, index = np.load(tmp_path / "vec.npy"), np.load(tmp_path / "vec_index.npy")
+    assert values.dtype == np.float32 and index.dtype == np.float64
+    assert values.nbytes + index.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.all(np.diff(index) > 0) and np.array_equal(values, big[index.astype(np.int64)].astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "again"), dict(vec=big))
+    assert np.array_equal(np.load(tmp_path / "again" / "vec_index.npy"), index)

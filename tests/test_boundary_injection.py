@@ -1,14 +1,9 @@
-"""The drop-in boundary, proven on the reference's own code: tests/golden/make_boundary_injection.py (dev
-container only -- it imports /root/reference) registers pygrank_amd/backend/hip.py in the unmodified reference loader
-and runs the reference's PageRank / HeatKernel / AbsorbingWalks / SymmetricAbsorbingRandomWalks on it; this test holds
-the committed outcome to equal iteration counts and <= 1e-6 relative L-inf against the reference's numpy backend, and --
-where the reference is present -- regenerates it and checks that the committed file is current."""
+"""The drop-in boundary, proven on the reference's own code: tests/golden/make_boundary_injection.py (run where
+the reference is installed) registers pygrank_amd/backend/hip.py in the unmodified reference loader and runs the reference's
+PageRank / HeatKernel / AbsorbingWalks / SymmetricAbsorbingRandomWalks on it; this test holds the committed outcome to equal
+iteration counts and <= 1e-6 relative L-inf against the reference's numpy backend."""
 import json
 import os
-import subprocess
-import sys
-
-import pytest
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -28,16 +23,3 @@ def test_committed_injection_results():
     kinds = {name.split("/")[1].split("_")[0] for name in cases}
     assert {"pagerank", "heat", "absorbing", "sarw"} <= kinds
 
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/pygrank"), reason="the reference exists in the dev container only")
-def test_injection_reproduces(tmp_path, oracle_build_dir):
-    before = _load()
-    backup = tmp_path / "boundary_injection.json"
-    target = os.path.join(HERE, "boundary_injection.json")
-    backup.write_text(open(target).read())
-    try:
-        res = subprocess.run([sys.executable, os.path.join(HERE, "make_boundary_injection.py")], capture_output=True, text=True, timeout=900)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
-        assert _load() == before
-    finally:
-        open(target, "w").write(backup.read_text())

@@ -61,3 +61,31 @@ def test_converge_to_eigenvectors(host_engine, graphs):
     assert rel_linf(r1, want) <= 1e-6
     r2 = np.asarray(pg.PageRank(0.99, tol=1e-9, max_iters=5000).rank(graph, p.copy()).np, dtype=np.float64)
     assert scipy.stats.spearmanr(r1, r2)[0] > 0.99
+
+
+def test_resident_copies_outlive_dead_ones(host_engine):
+    """A graph keeps at most six resident copies of its operands.  A copy whose vector has died goes before any live one, whatever
+    id the next vector happens to get: otherwise a new vector that reuses a dead one's id would evict a live copy that a vector
+    created at another address keeps (the number of transfers of a run would depend on the allocator's history)."""
+    import gc
+    import scipy.sparse as sp
+    from pygrank_amd.device import DeviceGraph, DeviceVector
+    from oracle import ref_loops as orc
+    A, directed, _ = cases.GRAPHS["rmat10_dir"]()
+    g = DeviceGraph.from_scipy(sp.csr_array(orc.normalize(A, "col", directed)))
+    n = g.shape[0]
+    assert g._resident_lengths()
+    live = [DeviceVector.from_host(np.full(n, float(i))) for i in range(5)]
+    for vec in live:
+        g._resident_copy(vec)
+    dead = DeviceVector.from_host(np.zeros(n))
+    g._resident_copy(dead)
+    assert len(g._resident) == 6
+    del dead
+    gc.collect()
+    for _ in range(2):                            # a new vector, at the dead one's address or elsewhere
+        newcomer = DeviceVector.from_host(np.ones(n))
+        g._resident_copy(newcomer)
+        assert all(id(vec) in g._resident and g._resident[id(vec)][0]() is vec for vec in live)
+        assert g._resident[id(newcomer)][0]() is newcomer and len(g._resident) == 6
+        del newcomer
