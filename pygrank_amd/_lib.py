@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI declared in include/pgh.h.
+"""ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -198,6 +198,16 @@ SUM, ABSSUM, MAX, MIN = range(4)
 ERR_MABS, ERR_L1, ERR_LINF, ERR_ITERS = range(4)
 K_SPMV, K_FIXUP, K_RESIDUAL, K_FINAL, K_SPMM, K_COMBINE, K_PB_GATHER, K_PB_ACCUM, K_PACK = range(9)
 
+# name -> (restype, argtypes); every symbol include/pgh_batch.h declares.  Bound apart from SIGNATURES (batch_entry): a library
+# without them -- the host test double under oracle/ -- still loads, and the filters run such batches column by column.
+BATCH_SIGNATURES = {
+    "pgh_poly_run_batch": (C.c_int, [c_graph, c_mat, C.c_void_p, C.c_int32, c_mat, C.POINTER(LoopCfg), C.c_void_p,
+                                     C.POINTER(LoopResult)]),
+    "pgh_absorb_run_batch": (C.c_int, [c_graph, c_mat, c_vec, c_mat, C.POINTER(LoopCfg), C.c_void_p, C.POINTER(LoopResult)]),
+    "pgh_sarw_run_batch": (C.c_int, [c_graph, c_mat, c_mat, C.POINTER(LoopCfg), C.c_void_p, C.POINTER(LoopResult)]),
+}
+BATCH_DECLINED = 2        # include/pgh_batch.h PGH_BATCH_DECLINED: the loop does not serve this input, nothing was written
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -213,6 +223,31 @@ def _bind(cdll):
         fn.restype = restype
         fn.argtypes = argtypes
     return cdll
+
+
+def bind_batch(cdll):
+    """Binds the include/pgh_batch.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    bound = {}
+    for name, (restype, argtypes) in BATCH_SIGNATURES.items():
+        try:
+            fn = getattr(cdll, name)
+        except AttributeError:
+            bound[name] = None
+            continue
+        fn.restype = restype
+        fn.argtypes = argtypes
+        bound[name] = fn
+    return bound
+
+
+def batch_entry(name):
+    """The bound include/pgh_batch.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_batch_entries", None)
+    if cache is None:
+        cache = bind_batch(cdll)
+        cdll._pgh_batch_entries = cache
+    return cache[name]
 
 
 def load_library(path=None):

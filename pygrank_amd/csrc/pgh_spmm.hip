@@ -13,6 +13,7 @@
 // segments leave [tile][64] carries combined in a fixed order by k_mm_fixup.  k_mm_combine applies the PageRank
 // epilogue per column and writes the next gather slab; k_mm_residual / k_mm_close keep the per-column loop state.
 #include "pgh_kernels.h"
+#include "pgh_batch.h"
 
 #include <vector>
 
@@ -568,7 +569,9 @@ struct StepParams {
 // TRACK: the form that also writes the non-zero map.  It needs 134+ registers (three wavefronts per SIMD instead of four: 900 us instead of
 // 690 for the pass at scale 23), so it is a kernel of its own that runs only while the iterate is sparse; both forms are launched for
 // every step and the one the device-side test does not select returns at once (as the two forms of k_mm_partial do).
-template <bool TRACK>
+// WALK: the row-affine step of the absorbing walks (pgh_absorb_run_batch / pgh_sarw_run_batch): the row word is the walk's
+// {u * dst scale, s'', 1 / s'', v} (k_mm_walk_rowops) and the personalization term is v_r * p instead of (1 - alpha) * p.
+template <bool TRACK, bool WALK = false>
 __global__ __launch_bounds__(WG) void k_mm_step(StepParams c, int64_t n, int ld, int b, const BatchState* __restrict__ state,
                                                  double* __restrict__ partials /* [4][grid][64]: S, T, R', D */) {
     __shared__ double s_red[4][WG / 64][kLanes];
@@ -639,7 +642,7 @@ __global__ __launch_bounds__(WG) void k_mm_step(StepParams c, int64_t n, int ld,
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float yo = xo[u][k] * op[u][2];                       // the previous iterate's y (one rounding)
-                const float y = a[k] * (sum[u][k] * op[u][0]) + bc * pv[u][k];
+                const float y = a[k] * (sum[u][k] * op[u][0]) + (WALK ? op[u][3] : bc) * pv[u][k];
                 if (frozen[k] != 0.f) {
                     out[k] = xo[u][k];                                       // a stopped column keeps its row bit for bit
                     continue;
@@ -1333,7 +1336,7 @@ int make_drop(pgh_graph_s* g, double rate, uint64_t seed, MMDrop* out, const MMD
 }
 int spmm_impl(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y, double rate, uint64_t seed);
 int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, double rate, uint64_t seed0,
-               pgh_loop_result* results);
+               pgh_loop_result* results, const f32x4* walk_rowop = nullptr);
 }  // namespace
 
 extern "C" int pgh_spmm(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y) { return spmm_impl(g, x, y, 0.0, 0); }
@@ -1418,8 +1421,10 @@ int poll_ring(PollRing** out) {
     return 0;
 }
 
+// walk_rowop (null for PageRank): the row words of an absorbing walk (k_mm_walk_rowops); the step is then k_mm_step<., true> with
+// a = the quotient alone, and the residual comes from the separate kernel (the in-kernel prediction is PageRank's column sums)
 int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, double rate, uint64_t seed0,
-               pgh_loop_result* results) {
+               pgh_loop_result* results, const f32x4* walk_rowop) {
     PGH_CHECK(g && p && ranks && cfg && results, "pgh_ppr_run_batch: null argument");
     PGH_CHECK(g->n_rows == g->n_cols && p->n == g->n_cols && ranks->n == g->n_cols && p->b == ranks->b, "pgh_ppr_run_batch: shape mismatch");
     PGH_CHECK(p->b >= 1 && p->b <= kLanes, "pgh_ppr_run_batch: the batch width must be in [1, 64]");
@@ -1430,7 +1435,9 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     const int b = p->b, ld = (b + 3) & ~3;
     const int64_t n = g->n_cols, n_int = f.n_out;
     const size_t slab = sizeof(float) * (size_t)n_int * ld;
-    const f32x4* rowop = reinterpret_cast<const f32x4*>(f.mm_rowop);
+    const bool walk = walk_rowop != nullptr;
+    const f32x4* rowop = walk ? walk_rowop : reinterpret_cast<const f32x4*>(f.mm_rowop);
+    const double alpha = walk ? 1.0 : cfg->alpha;                   // a walk's step: a = its quotient
     DevBytes pint, xg0, xg1, sums, partial, folded, state_mem, factors, row_flags, nz_maps, nz_counts, zero_row;
     PGH_TRY(zero_row.alloc(sizeof(float) * (size_t)(ld + 4)));
     PGH_HIP(hipMemsetAsync(zero_row.p, 0, sizeof(float) * (size_t)(ld + 4), r.stream));
@@ -1464,7 +1471,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     PGH_HIP(hipEventRecord(ev_a, r.stream));
     if (!skip_dead) PGH_HIP(hipMemsetAsync(sums.p, 0, slab, r.stream));      // structural zeros of the rows without entries (every row is processed)
     // the in-kernel residual: sum rules, the plain matrix (a dropped matrix has other column sums every step), PGH_MM_FUSED=0 turns it off
-    const bool fused_first = (cfg->err_kind == PGH_ERR_L1 || cfg->err_kind == PGH_ERR_MABS) && rate == 0.0 &&
+    const bool fused_first = (cfg->err_kind == PGH_ERR_L1 || cfg->err_kind == PGH_ERR_MABS) && rate == 0.0 && !walk &&
                              !(getenv("PGH_MM_FUSED") != nullptr && atoi(getenv("PGH_MM_FUSED")) == 0);
     bool step1_predicted = false;                // the way in's sums give step 1 its predicted quotient (PGH_MM_FIRST_PRED=0: the separate kernel)
     k_mm_state_init<<<1, kLanes, 0, r.stream>>>(state, b);
@@ -1507,7 +1514,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     int flags = fused ? 2 : 0;
     CloseParams cp{};
     cp.tol = cfg->tol;
-    cp.alpha = cfg->alpha;
+    cp.alpha = alpha;
     cp.n_orig = n;
     cp.use_quotient = cfg->use_quotient;
     cp.err_kind = cfg->err_kind;
@@ -1551,7 +1558,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         c.row_flags = row_flags.as<uint8_t>();
         c.xg_old = buf[(k - 1) & 1];
         c.xg_new = buf[k & 1];
-        c.alpha = cfg->alpha;
+        c.alpha = alpha;
         c.mode = mode;
         c.nz_map = sparse_gate ? nz_map[k & 1] : nullptr;
         c.nz_part = sparse_gate ? nz_part : nullptr;
@@ -1561,8 +1568,13 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         c.zero = zero_row.as<float>();
         {
             ProfScope prof(PGH_K_COMBINE);
-            k_mm_step<false><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
-            if (sparse_gate) k_mm_step<true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+            if (walk) {
+                k_mm_step<false, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+                if (sparse_gate) k_mm_step<true, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+            } else {
+                k_mm_step<false><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+                if (sparse_gate) k_mm_step<true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+            }
         }
         k_mm_fold4<<<dim3(kLanes, 4), WG, 0, r.stream>>>(partial.as<double>(), cgrid, state, fold);
         if (mode == 1) {
@@ -1637,3 +1649,388 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     return 0;
 }
 }  // namespace
+
+// =================================================================================================
+// Multi-seed loops of the other filters (include/pgh_batch.h): the closed-form filters' Taylor form and the two absorbing walks.
+// They reuse the multi-seed layout, the gather pass (mm_partial), the permutes, BatchState and the poll ring of the PageRank batch.
+// =================================================================================================
+namespace {
+
+// an input these loops do not serve: nothing was written, the caller runs the columns one by one
+int declined(const char* msg) {
+    set_error(msg);
+    return PGH_BATCH_DECLINED;
+}
+
+// the row words of an absorbing walk in the multi-seed id space: {u * dst scale, s'', 1 / s'', v} with y = a * u * (M^T x) + v * p,
+// u = deg / (lam + deg), v = lam / (lam + deg).  lam == null: the symmetric walk, lam = (1 + sqrt(1 + 4 deg)) / 2 and the source factor
+// 1 / lam folded into the gather scale s'' (the single-vector loop's k_sarw_vectors + pre_scale).  Padding rows take lam = 1, deg = 0
+// (u = 0, v = 1: a zero row).  A real row with lam + deg == 0 or a non-finite word sets *bad.
+__global__ __launch_bounds__(WG) void k_mm_walk_rowops(const float* __restrict__ dst_scale, const float* __restrict__ src_scale,
+                                                        const float* __restrict__ degrees, const float* __restrict__ lam,
+                                                        const int32_t* __restrict__ perm, int64_t n_int, int64_t n_valid, f32x4* __restrict__ out,
+                                                        int* __restrict__ bad) {
+    for (int64_t r = blockIdx.x * (int64_t)WG + threadIdx.x; r < n_int; r += (int64_t)gridDim.x * WG) {
+        const int64_t o = perm ? perm[r] : (r < n_valid ? r : -1);
+        const double deg = o >= 0 ? (double)degrees[o] : 0.0;
+        float l, pre = 1.f;
+        if (lam != nullptr) {
+            l = o >= 0 ? lam[o] : 1.f;
+        } else {
+            const double a = (1.0 + sqrt(1.0 + 4.0 * deg)) / 2.0;
+            l = (float)a;
+            pre = (float)(1.0 / a);
+        }
+        const float s = src_scale != nullptr ? src_scale[r] : 1.f;
+        const float sp = s != 0.f ? s * pre : 1.f;          // a row nobody gathers keeps y itself in the slab
+        const double den = (double)l + deg;
+        const float ds = dst_scale != nullptr ? dst_scale[r] : 1.f;
+        const float u = (float)((double)ds * deg / den), v = (float)((double)l / den);
+        if (o >= 0 && !(isfinite(u) && isfinite(v))) atomicOr(bad, 1);
+        out[r] = f32x4{u, sp, 1.f / sp, v};
+    }
+}
+
+// the closed-form filters' first term: result_1 = c_1 * p in place over the internal personalization (rows whose p is zero become
+// zeros: every row of the result slab is written), and per workgroup the column's |result_1| (sum or max) -- the single-vector loop's
+// delta_1 = |result_1 - 0|
+__global__ __launch_bounds__(WG) void k_mm_poly_init(float* __restrict__ res, const uint8_t* __restrict__ row_flags, int64_t n, int ld, float c1,
+                                                      int linf, double* __restrict__ partial) {
+    __shared__ double s_red[WG / 64][kLanes];
+    const int lane = threadIdx.x & 63, wave_in_wg = threadIdx.x >> 6;
+    const int lpr = lanes_per_row(ld), rows_per_wave = 64 / lpr;
+    const int l = lane & (lpr - 1), c4 = 4 * l;
+    const bool live = c4 < ld;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + wave_in_wg) * rows_per_wave + lane / lpr;
+    const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
+    for (int64_t r = first; live && r < n; r += stride) {
+        f32x4* at = reinterpret_cast<f32x4*>(res + r * ld + c4);
+        const f32x4 v = (row_flags[r] & 1) ? *at * c1 : f32x4{0.f, 0.f, 0.f, 0.f};
+        *at = v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double d = fabs((double)v[k]);
+            acc[k] = linf ? fmax(acc[k], d) : acc[k] + d;
+        }
+    }
+    for (int j = threadIdx.x; j < (WG / 64) * kLanes; j += WG) (&s_red[0][0])[j] = 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double t = acc[k];
+        for (int off = lpr; off < 64; off += lpr) {
+            const double o = __shfl_down(acc[k], off, 64);
+            t = linf ? fmax(t, o) : t + o;
+        }
+        if (lane < lpr && live) s_red[wave_in_wg][c4 + k] = t;
+    }
+    __syncthreads();
+    if (wave_in_wg == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < WG / 64; ++w) t = linf ? fmax(t, s_red[w][lane]) : t + s_red[w][lane];
+        partial[(int64_t)blockIdx.x * kLanes + lane] = t;
+    }
+}
+
+// the single-vector loop's host-side check at iteration 2 (convergence.py:96-101 on delta_1), per column
+__global__ void k_mm_poly_first(BatchState* __restrict__ state, const double* __restrict__ err1, int check, int err_kind, double tol, long long n) {
+    const int lane = threadIdx.x;
+    int done = 1;
+    if (lane < state->b) {
+        double e = err1[lane];
+        if (err_kind == PGH_ERR_MABS && n > 0) e /= (double)n;
+        state->err[lane] = e;
+        if (check && e <= tol) {
+            state->done[lane] = 1;
+            state->converged[lane] = 1;
+        }
+        done = state->done[lane];
+    }
+    const unsigned long long all = __ballot(done != 0);
+    if (lane == 0) state->all_done = (all == ~0ULL) ? 1 : 0;
+}
+
+// One Taylor step of every column (ClosedFormGraphFilter._step, abstract_filters.py:248-256, as pgh_poly_run's EPI_POLY epilogue):
+// term_k = M^T term_{k-1} (y = row sum * dst scale), result += c_k * term_k for the columns still running, and the exact change
+// sum_r |result_new - result_old| (or its max) per column into [grid][64] partials.  The next gather slab is term_k * s'.  A stopped
+// column keeps its result rows; its term goes on being formed (nobody reads it).  Rows whose flag is 0 are zero for ever: not touched.
+struct PolyStepParams {
+    const float*   sums;       // [n, ld] plain row sums (structural zeros never written)
+    const f32x4*   rowop;      // [n] {dst scale, s', 1 / s', row sum of M}
+    const uint8_t* row_flags;  // [n] bit 0: p holds a non-zero; bit 1: the row has entries; 0: zero for ever
+    float*         result;     // [n, ld] in / out
+    float*         xg_new;     // [n, ld]
+    const float*   zero;       // [ld] zeros
+    float          c;          // (float) c_k
+    int            linf;
+};
+__global__ __launch_bounds__(WG) void k_mm_poly_step(PolyStepParams c, int64_t n, int ld, int b, const BatchState* __restrict__ state,
+                                                      double* __restrict__ partials) {
+    __shared__ double s_red[WG / 64][kLanes];
+    if (state->all_done) return;
+    const int lane = threadIdx.x & 63, wave_in_wg = threadIdx.x >> 6;
+    const int lpr = lanes_per_row(ld), rows_per_wave = 64 / lpr;
+    const int l = lane & (lpr - 1), c4 = 4 * l;
+    const bool live = c4 < b;
+    bool frozen[4], want[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool col = c4 + k < b;
+        frozen[k] = !col || state->done[c4 + k] != 0;
+        want[k] = !frozen[k];
+    }
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + wave_in_wg) * rows_per_wave + lane / lpr;
+    const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
+    constexpr int U = PGH_MM_COMB_U;
+    const float* const zero4 = c.zero + c4;
+    for (int64_t r0 = first; r0 < n; r0 += stride * U) {
+        f32x4 sum[U], ro[U];
+        float ds[U], sp[U];
+        int fl[U];
+        // every load of a trip unconditional (a row without the operand reads the zero row), as in k_mm_step
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t r = r0 + u * stride;
+            fl[u] = (live && r < n) ? (int)c.row_flags[r] : 0;
+            const bool ok = fl[u] != 0;
+            const int64_t at = (ok ? r : 0) * ld + c4;
+            sum[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>((ok && (fl[u] & 2)) ? c.sums + at : zero4));
+            ro[u] = *reinterpret_cast<const f32x4*>(ok ? c.result + at : zero4);
+            const f32x4 op = c.rowop[ok ? r : 0];
+            ds[u] = op[0];
+            sp[u] = op[1];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (fl[u] == 0) continue;
+            const int64_t at = (r0 + u * stride) * ld + c4;
+            f32x4 xg, rn;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float y = sum[u][k] * ds[u];
+                xg[k] = y * sp[u];
+                rn[k] = frozen[k] ? ro[u][k] : ro[u][k] + c.c * y;
+                const double d = frozen[k] ? 0.0 : fabs((double)rn[k] - (double)ro[u][k]);
+                acc[k] = c.linf ? fmax(acc[k], d) : acc[k] + d;
+            }
+            *reinterpret_cast<f32x4*>(c.xg_new + at) = xg;
+            *reinterpret_cast<f32x4*>(c.result + at) = rn;
+        }
+    }
+    for (int j = threadIdx.x; j < (WG / 64) * kLanes; j += WG) (&s_red[0][0])[j] = 0.0;      // columns beyond 4 * lanes
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double t = acc[k];
+        for (int off = lpr; off < 64; off += lpr) {
+            const double o = __shfl_down(acc[k], off, 64);
+            t = c.linf ? fmax(t, o) : t + o;
+        }
+        if (lane < lpr && c4 < ld) s_red[wave_in_wg][c4 + k] = want[k] ? t : 0.0;
+    }
+    __syncthreads();
+    if (wave_in_wg == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < WG / 64; ++w) t = c.linf ? fmax(t, s_red[w][lane]) : t + s_red[w][lane];
+        partials[(int64_t)blockIdx.x * kLanes + lane] = t;
+    }
+}
+
+int check_batch_shapes(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop_cfg* cfg, const char* who) {
+    PGH_CHECK(g && p && out && cfg, std::string(who) + ": null argument");
+    if (g->n_rows != g->n_cols) return declined("the multi-seed loops need a square matrix");
+    if (!g->bsf.enabled) return declined("the multi-seed loops need a graph with the blocked layout");
+    PGH_CHECK(p->n == g->n_cols && out->n == g->n_cols && p->b == out->b, std::string(who) + ": shape mismatch");
+    PGH_CHECK(p->b >= 1 && p->b <= kLanes, std::string(who) + ": the batch width must be in [1, 64]");
+    PGH_CHECK(cfg->end_modulo >= 1, "end_modulo must be >= 1");
+    return 0;
+}
+
+int walk_batch(pgh_graph_t g, pgh_mat_t p, const float* lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+               pgh_loop_result* results) {
+    PGH_CHECK(g->degrees != nullptr, "the absorbing walks need the graph's degrees");
+    PGH_TRY(ensure_mm_layout(g));
+    const BsfFormat& f = g->bsf_mm;
+    const int64_t n_int = f.n_out;
+    DevBytes rowop, bad;
+    PGH_TRY(rowop.alloc(sizeof(f32x4) * (size_t)(n_int > 0 ? n_int : 1)));
+    PGH_TRY(bad.alloc(sizeof(int)));
+    Runtime& r = rt();
+    PGH_HIP(hipMemsetAsync(bad.p, 0, sizeof(int), r.stream));
+    k_mm_walk_rowops<<<blocks_for(n_int), WG, 0, r.stream>>>(f.dst_scale, f.src_scale, g->degrees, lam, f.perm, n_int, g->n_rows,
+                                                             rowop.as<f32x4>(), bad.as<int>());
+    PGH_HIP(hipGetLastError());
+    int h_bad = 0;
+    PGH_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, r.stream));
+    PGH_HIP(hipStreamSynchronize(r.stream));
+    if (h_bad) return declined("a row with absorption + degree == 0 (or a non-finite absorption): the single-vector loop's NaN");
+    pgh_loop_cfg from_p = *cfg;
+    from_p.start_from_p = 1;                               // ranks are output only
+    return batch_impl(g, p, ranks, &from_p, out_scales, 0.0, 0, results, rowop.as<f32x4>());
+}
+
+}  // namespace
+
+extern "C" int pgh_absorb_run_batch(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
+                                    const double* out_scales, pgh_loop_result* results) {
+    PGH_CHECK(results && lam, "pgh_absorb_run_batch: null argument");
+    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, "pgh_absorb_run_batch"));
+    PGH_CHECK(lam->n == g->n_cols, "pgh_absorb_run_batch: absorption length mismatch");
+    return walk_batch(g, p, lam->data, ranks, cfg, out_scales, results);
+}
+
+extern "C" int pgh_sarw_run_batch(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                                  pgh_loop_result* results) {
+    PGH_CHECK(results, "pgh_sarw_run_batch: null argument");
+    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, "pgh_sarw_run_batch"));
+    return walk_batch(g, p, nullptr, ranks, cfg, out_scales, results);
+}
+
+// The Taylor form of pgh_poly_run for b columns: iteration `it` uses coeffs[it - 1] (0 beyond num_coeffs), iteration 1 is result_1 =
+// c_1 p with the check of iteration 2 on |result_1|, step k (iteration k + 1) adds c_{k+1} (M^T)^k p, the check of iteration k + 2
+// compares result_{k+1} with result_k.  Column j: iterations = 2 + its steps, as pgh_poly_run reports them.
+extern "C" int pgh_poly_run_batch(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
+                                  const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results) {
+    PGH_CHECK(results && (coeffs || num_coeffs == 0), "pgh_poly_run_batch: null argument");
+    PGH_TRY(check_batch_shapes(g, p, result, cfg, "pgh_poly_run_batch"));
+    Runtime& r = rt();
+    const int b = p->b, ld = (b + 3) & ~3;
+    const int64_t n = g->n_cols;
+    auto coeff = [&](int it) -> double { return (it >= 1 && it <= num_coeffs) ? coeffs[it - 1] : 0.0; };
+    for (int j = 0; j < b; ++j) memset(&results[j], 0, sizeof(pgh_loop_result));
+    if (cfg->max_iters <= 1) {            // convergence.py:86-89: stops before the first step, the sum is empty
+        PGH_HIP(hipMemsetAsync(result->data, 0, sizeof(float) * (size_t)n * b, r.stream));
+        PGH_HIP(hipStreamSynchronize(r.stream));
+        for (int j = 0; j < b; ++j) results[j].iterations = 1;
+        return 0;
+    }
+    PGH_TRY(ensure_mm_layout(g));
+    const BsfFormat& f = g->bsf_mm;
+    const int64_t n_int = f.n_out;
+    const size_t slab = sizeof(float) * (size_t)n_int * ld;
+    const f32x4* rowop = reinterpret_cast<const f32x4*>(f.mm_rowop);
+    DevBytes res_slab, xg0, xg1, sums, partial, folded, state_mem, factors, row_flags, nz_map, nz_counts, zero_row;
+    PGH_TRY(zero_row.alloc(sizeof(float) * (size_t)(ld + 4)));
+    PGH_HIP(hipMemsetAsync(zero_row.p, 0, sizeof(float) * (size_t)(ld + 4), r.stream));
+    PGH_TRY(row_flags.alloc((size_t)((n_int + 63) / 64 * 64 + 64)));
+    PGH_TRY(nz_map.alloc((size_t)((n_int + 63) / 64 * 64 + 64)));          // (written by the way in; the loop keeps the dense pass)
+    const int in_grid = blocks_for(n_int * lanes_per_row(ld));
+    PGH_TRY(nz_counts.alloc(sizeof(int) * (size_t)(2 * in_grid * (WG / 64))));
+    const bool skip_dead = f.mm_row_has != nullptr;       // every run starts from p: rows without entries and without p stay zero
+    PGH_TRY(res_slab.alloc(slab));
+    PGH_TRY(xg0.alloc(slab));
+    PGH_TRY(xg1.alloc(slab));
+    PGH_TRY(sums.alloc(slab));
+    const int cgrid = combine_grid();
+    PGH_TRY(partial.alloc(sizeof(double) * (size_t)cgrid * kLanes));
+    PGH_TRY(folded.alloc(sizeof(double) * 5 * kLanes));                  // S, T, R', D (zeros: no quotient) + the folded change
+    PGH_TRY(state_mem.alloc(sizeof(BatchState)));
+    PGH_TRY(factors.alloc(sizeof(double) * kLanes));
+    BatchState* state = state_mem.as<BatchState>();
+    double* fold = folded.as<double>();
+    PollRing* ring = nullptr;
+    PGH_TRY(poll_ring(&ring));
+    hipEvent_t ev_a, ev_b;
+    PGH_HIP(hipEventCreate(&ev_a));
+    PGH_HIP(hipEventCreate(&ev_b));
+    PGH_HIP(hipEventRecord(ev_a, r.stream));
+    if (!skip_dead) PGH_HIP(hipMemsetAsync(sums.p, 0, slab, r.stream));
+    PGH_HIP(hipMemsetAsync(folded.p, 0, sizeof(double) * 5 * kLanes, r.stream));
+    k_mm_state_init<<<1, kLanes, 0, r.stream>>>(state, b);
+    {
+        PermuteIn2 q{};
+        q.nz_map = nz_map.as<uint8_t>();
+        q.nz_rows = nz_counts.as<int>();
+        q.live_rows = nz_counts.as<int>() + in_grid * (WG / 64);
+        q.src_p = p->data;
+        q.src_x = p->data;                                 // term_1 = p: the first gather slab
+        q.out_p = res_slab.as<float>();                    // p, turned into result_1 = c_1 p in place below
+        q.out_xg0 = xg0.as<float>();
+        q.out_xg1 = xg1.as<float>();
+        q.rowop = rowop;
+        q.row_flags = row_flags.as<uint8_t>();
+        q.row_has = skip_dead ? f.mm_row_has : nullptr;
+        k_mm_permute_in2<<<in_grid, WG, 0, r.stream>>>(q, f.perm, n_int, n, b, ld);
+    }
+    const int linf = cfg->err_kind == PGH_ERR_LINF;
+    k_mm_poly_init<<<cgrid, WG, 0, r.stream>>>(res_slab.as<float>(), row_flags.as<uint8_t>(), n_int, ld, (float)coeff(1), linf,
+                                               partial.as<double>());
+    k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, 0);
+    const int check2 = (cfg->err_kind != PGH_ERR_ITERS) && (2 < cfg->max_iters) && (2 % cfg->end_modulo == 0);
+    k_mm_poly_first<<<1, kLanes, 0, r.stream>>>(state, fold + 4 * kLanes, check2, cfg->err_kind, cfg->tol, (long long)n);
+    PGH_HIP(hipGetLastError());
+    float* buf[2] = {xg0.as<float>(), xg1.as<float>()};
+    const int max_steps = cfg->max_iters - 2 > 0 ? cfg->max_iters - 2 : 0;
+    CloseParams cp{};
+    cp.tol = cfg->tol;
+    cp.n_orig = n;
+    cp.use_quotient = 0;
+    cp.err_kind = cfg->err_kind;
+    cp.mode = 0;
+    // step k runs iteration k + 1; its check is the one of iteration k + 2
+    auto enqueue_step = [&](int k) -> int {
+        PGH_TRY(mm_partial(g, buf[(k - 1) & 1], ld, b, sums.as<float>(), state));
+        PolyStepParams c{};
+        c.sums = sums.as<float>();
+        c.rowop = rowop;
+        c.row_flags = row_flags.as<uint8_t>();
+        c.result = res_slab.as<float>();
+        c.xg_new = buf[k & 1];
+        c.zero = zero_row.as<float>();
+        c.c = (float)coeff(k + 1);
+        c.linf = linf;
+        {
+            ProfScope prof(PGH_K_COMBINE);
+            k_mm_poly_step<<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+        }
+        const int it = k + 2;
+        CloseParams c2 = cp;
+        c2.check = (cfg->err_kind != PGH_ERR_ITERS) && (it < cfg->max_iters) && (it % cfg->end_modulo == 0);
+        if (c2.check) k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, 0);
+        k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
+        PGH_HIP(hipGetLastError());
+        PGH_HIP(hipMemcpyAsync(&ring->host[k % kPollRing], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
+        PGH_HIP(hipEventRecord(ring->ev[k % kPollRing], r.stream));
+        return 0;
+    };
+    // up to three steps enqueued beyond the last one whose outcome the host has seen (launches behind the stop are no-ops)
+    int enq = 0, seen = 0;
+    for (;;) {
+        while (enq < max_steps && enq - seen < 3) {
+            PGH_TRY(enqueue_step(enq + 1));
+            ++enq;
+        }
+        if (seen == enq) break;
+        const int k = seen + 1;
+        PGH_HIP(hipEventSynchronize(ring->ev[k % kPollRing]));
+        ++seen;
+        if (ring->host[k % kPollRing].all_done) break;
+    }
+    BatchState host_state;
+    PGH_HIP(hipMemcpyAsync(&host_state, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
+    PGH_HIP(hipStreamSynchronize(r.stream));
+    double h_factors[kLanes];
+    for (int j = 0; j < kLanes; ++j) h_factors[j] = j < b ? (out_scales ? out_scales[j] : cfg->out_scale) : 1.0;
+    PGH_HIP(hipMemcpyAsync(factors.p, h_factors, sizeof(h_factors), hipMemcpyHostToDevice, r.stream));
+    k_mm_permute_out<<<blocks_for(n_int * lanes_per_row(ld)), WG, 0, r.stream>>>(res_slab.as<float>(), f.perm, n_int, n, b, ld,
+                                                                                 factors.as<double>(), result->data);
+    PGH_HIP(hipGetLastError());
+    PGH_HIP(hipEventRecord(ev_b, r.stream));
+    PGH_HIP(hipEventSynchronize(ev_b));
+    float ms = 0.f;
+    PGH_HIP(hipEventElapsedTime(&ms, ev_a, ev_b));
+    (void)hipEventDestroy(ev_a);
+    (void)hipEventDestroy(ev_b);
+    for (int j = 0; j < b; ++j) {
+        results[j].iterations = 2 + host_state.steps[j];
+        results[j].converged = host_state.converged[j];
+        results[j].spmv_count = host_state.steps[j];
+        results[j].last_error = host_state.err[j];
+        results[j].loop_ms = (double)ms;
+    }
+    return 0;
+}

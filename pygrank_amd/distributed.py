@@ -1074,9 +1074,11 @@ class ReplicatedPropagation:
     """NodeRanking.propagate (pygrank/core/signals.py:225-226) across the GPUs of a node as a REPLICA SPLIT (last
     sentence: "cfg3-style batches can alternatively be split across GPUs with zero communication").  Every rank holds the whole
     graph (the scale-23 bench graph is 1 GB of images in 288 GB of HBM) and the same feature matrix; rank r runs the columns
-    [r * B / P, (r + 1) * B / P) through `ranker.propagate` -- the single-GPU multi-seed loop (pgh_ppr_run_batch: every column keeps
+    [r * B / P, (r + 1) * B / P) through `ranker.propagate` -- the single-GPU multi-seed loops (pgh_ppr_run_batch, and pgh_poly_run_batch /
+    pgh_absorb_run_batch / pgh_sarw_run_batch of include/pgh_batch.h: every column keeps
     its own quotient, residual and stopping iteration) -- and nothing is exchanged until the result slabs are, optionally,
-    all-gathered at the end.  `ranker` is any filter of pygrank_amd with a `propagate` (PageRank takes the batched route)."""
+    all-gathered at the end.  `ranker` is any filter of pygrank_amd with a `propagate` (PageRank, the closed-form filters' taylor form and the absorbing
+    walks take the batched route where their single-vector run is the f32 fused loop)."""
 
     def __init__(self, ranker):
         self.ranker = ranker

@@ -39,6 +39,42 @@ def _f64_image_usable(g):
     return g is not None and g.shape[0] == g.shape[1] and g.shape[0] > 0 and g.nnz > 0 and "row-major" not in g.format()
 
 
+def _propagate_in_batches(ranker, features, cfg, run):
+    """signals.py:225-226 (one rank() per feature column) as multi-seed device loops of up to 64 columns with the prologue of
+    PageRank.propagate: per-column L1 norms (abstract_filters.py:52-55; zero columns stay zero), preserve_norm factors, the loop
+    started from p (:56), ConvergenceManager's verdict per non-zero column.  run(P, R, cfg_ref, scales, results) -> status of one
+    include/pgh_batch.h call.  Returns the [n, B] ranks, or None when the engine declined the first chunk (nothing was run)."""
+    from pygrank_amd.device import DeviceMatrix
+    F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
+    if not isinstance(F, DeviceMatrix):
+        F = DeviceMatrix.from_columns([F])
+    cfg.start_from_p = 1
+    batches = []
+    out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
+    for start in range(0, F.b, 64):
+        chunk = F if F.b <= 64 else F.get_cols(start, min(64, F.b - start))
+        norms = chunk.col_abssum()
+        P = chunk.div_cols(norms)
+        R = DeviceMatrix.empty(chunk.n, chunk.b)
+        results = (L.LoopResult * chunk.b)()
+        scales = (C.c_double * chunk.b)(*[(float(nrm) if ranker.preserve_norm else 1.0) for nrm in norms])
+        ranker.convergence.start()
+        status = run(P, R, C.byref(cfg), scales, results)
+        if status == L.BATCH_DECLINED and not batches:
+            return None
+        L.check(status)
+        batches.append([dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms)
+                        for r in results])
+        ranker.last_batches = batches
+        for r, nrm in zip(results, norms):
+            if nrm != 0:
+                ranker.convergence.finish_device_loop(r.iterations, r.converged)   # raises like the per-column run would
+        if out is None:
+            return R
+        out.set_cols(start, R)
+    return out
+
+
 class GraphFilter(NodeRanking):
     """abstract_filters.py:11-106."""
 
@@ -166,6 +202,22 @@ class GraphFilter(NodeRanking):
     def _prepare_graph(self, graph, *args, **kwargs):
         return graph
 
+    def _batch_graph(self, graph, args, kwargs, allowed=()):
+        """The device graph of a multi-seed loop (include/pgh_batch.h) for propagate(graph, ..., *args, **kwargs), or None where a single
+        rank() would not run the f32 fused loop: extra arguments, graph_dropout, f64 iterates (dtype or a tolerance below fp32 eps), a
+        personalization transform, a stopping rule the engine cannot evaluate, a non-square / row-major / empty or non-device graph."""
+        if args or any(k not in allowed and not (k == "graph_dropout" and not kwargs[k]) for k in kwargs):
+            return None
+        if self._loop_cfg() is None or self._f64_wanted():
+            return None
+        transform = self.personalization_transform
+        if not (isinstance(transform, Tautology) and transform.ranker is None) or type(self)._prepare_graph is not GraphFilter._prepare_graph:
+            return None
+        g = _device_graph(self.preprocessor(graph))
+        if g is None or g.shape[0] != g.shape[1] or g.shape[0] == 0 or g.nnz == 0 or "row-major" in g.format():
+            return None
+        return g
+
     def _start(self, M, personalization, ranks, *args, **kwargs):
         pass
 
@@ -247,6 +299,13 @@ class RecursiveGraphFilter(GraphFilter):
     def _plain_quotient(self):
         return (self.use_quotient is None or isinstance(self.use_quotient, (bool, int))) \
             and not self.converge_to_eigenvectors
+
+    def _walk_batch_graph(self, cls, graph, args, kwargs, allowed=()):
+        """_batch_graph for the walks of class `cls`: also the plain quotient and the class's own formula, step and start."""
+        if not self._plain_quotient() or type(self)._formula is not cls._formula or type(self)._step is not RecursiveGraphFilter._step \
+                or type(self)._start is not cls._start:
+            return None
+        return self._batch_graph(graph, args, kwargs, allowed)
 
     def _run_recursive(self, entry, g, cfg, ranks, *vectors):
         if cfg is None or g is None or g.shape[0] != g.shape[1]:
@@ -435,6 +494,22 @@ class AbsorbingWalks(RecursiveGraphFilter):
             return self._run_recursive(L.lib().pgh_absorb_run_f64, g, cfg, ranks, p, lam)
         return self._run_recursive(L.lib().pgh_absorb_run, g, cfg, ranks, p, lam)
 
+    def propagate(self, graph, features, *args, **kwargs):
+        """signals.py:225-226 (one rank() per feature column, each with the same `absorption=`) as multi-seed batches of up to 64
+        columns through pgh_absorb_run_batch (include/pgh_batch.h) wherever a single rank() would run the f32 loop of pgh_absorb_run;
+        every column keeps its own quotient, residual and stopping iteration.  The column loop otherwise."""
+        g = self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",))
+        entry = L.batch_entry("pgh_absorb_run_batch") if g is not None else None
+        if entry is not None:
+            lam = (to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np
+            if isinstance(lam, DeviceVector) and len(lam) == g.shape[0]:
+                cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
+                out = _propagate_in_batches(self, features, cfg,
+                                            lambda P, R, cfg_ref, scales, res: entry(g._h, P._h, lam._h, R._h, cfg_ref, scales, res))
+                if out is not None:
+                    return out
+        return super().propagate(graph, features, *args, **kwargs)
+
 
 class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
     """adhoc.py:317-369: symmetric partially absorbing random walks.  With d = degrees(M) and the per-node absorption
@@ -474,6 +549,19 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
             cfg, p = self._f64_operands(cfg, p)
             return self._run_recursive(L.lib().pgh_sarw_run_f64, g, cfg, ranks, p)
         return self._run_recursive(L.lib().pgh_sarw_run, g, cfg, ranks, p)
+
+    def propagate(self, graph, features, *args, **kwargs):
+        """signals.py:225-226 as multi-seed batches of up to 64 columns through pgh_sarw_run_batch (include/pgh_batch.h) wherever a
+        single rank() would run the f32 loop of pgh_sarw_run; the column loop otherwise."""
+        g = self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs)
+        entry = L.batch_entry("pgh_sarw_run_batch") if g is not None else None
+        if entry is not None:
+            cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
+            out = _propagate_in_batches(self, features, cfg,
+                                        lambda P, R, cfg_ref, scales, res: entry(g._h, P._h, R._h, cfg_ref, scales, res))
+            if out is not None:
+                return out
+        return super().propagate(graph, features, *args, **kwargs)
 
 
 class LowPassRecursiveGraphFilter(GraphFilter):
@@ -832,6 +920,27 @@ class ClosedFormGraphFilter(GraphFilter):
                               last_error=res.last_error, loop_ms=res.loop_ms)
         self.convergence.finish_device_loop(res.iterations, res.converged)
         return True
+
+    def propagate(self, graph, features, *args, **kwargs):
+        """signals.py:225-226 (one rank() per feature column) as multi-seed batches of up to 64 columns through pgh_poly_run_batch
+        (include/pgh_batch.h) wherever a single rank() would run the f32 taylor loop of pgh_poly_run: the adjacency is streamed once
+        per term for the whole batch and every column stops at its own iteration.  The column loop otherwise (the "chebyshev" form,
+        an optimisation dict, overridden hooks, f64 iterates ...)."""
+        own = ClosedFormGraphFilter
+        g = None
+        if self.coefficient_type == "taylor" and self.optimization_dict is None and type(self)._step is own._step \
+                and type(self)._recursion is own._recursion and type(self)._start is own._start \
+                and type(self)._retrieve_power is own._retrieve_power and type(self)._prepare is own._prepare:
+            g = self._batch_graph(graph, args, kwargs)
+        entry = L.batch_entry("pgh_poly_run_batch") if g is not None else None
+        if entry is not None:
+            cfg = self._loop_cfg(0.0, False, 1.0)
+            coeffs = np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64)
+            out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: entry(
+                g._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res))
+            if out is not None:
+                return out
+        return super().propagate(graph, features, *args, **kwargs)
 
 
 class GenericGraphFilter(ClosedFormGraphFilter):

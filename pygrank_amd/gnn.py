@@ -4,7 +4,8 @@ model's forward pass; the reference gets its gradients from running the filter o
 This backend's loops are not an autograd tape, but the filters a GNN propagates with are LINEAR maps of the feature matrix -- a fixed number
 of steps (``error_type="iters"``), no L1 quotient: Y = F X with F = sum_k c_k (M^T)^k -- so the gradient of a loss with respect to the
 features is the SAME filter run on the transposed operator: dL/dX = F^T dL/dY, F^T = sum_k c_k M^k.  ``differentiable_propagate`` is a
-``torch.autograd.Function`` around ``ranker.propagate`` (the engine's multi-seed loop: pgh_ppr_run_batch for PageRank) whose backward pass
+``torch.autograd.Function`` around ``ranker.propagate`` (the engine's multi-seed loops: pgh_ppr_run_batch for PageRank, pgh_poly_run_batch for
+the taylor form of the closed-form filters, include/pgh_batch.h) whose backward pass
 is one more ``propagate`` on the transposed graph (the same graph when the normalised matrix is symmetric; otherwise built once per graph
 from the stored M^T).  ``graph_dropout`` is not supported here (a different mask per step would have to be replayed in reverse order)."""
 import numpy as np
