@@ -133,7 +133,8 @@ inline int pb_blocks_for(int64_t n) {
 
 // ------------------------------------------------------------------------------------------------- build kernels
 // The planner's input and output without two n-word transfers (round 6): the per-row cold counts go to the host as BYTES (255 = "look
-// me up": the few rows with more are listed beside them), and the row -> bin map is made on the device from the bins' first rows.
+// me up": the few rows with more are listed beside them -- on dense graphs most rows: pb_plan then grows the list to their count), and the
+// row -> bin map is made on the device from the bins' first rows.
 __global__ void k_pb_counts_small(const uint32_t* __restrict__ counts, int n_out, unsigned char* __restrict__ small, uint32_t* __restrict__ big_rows,
                                   uint32_t* __restrict__ big_counts, uint32_t* __restrict__ big_n, uint32_t cap) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += gridDim.x * blockDim.x) {
@@ -968,8 +969,10 @@ PbView pb_view(const BsfFormat& f, const PbFormat& p) {
 
 // Decides whether the cold tail gets its own image and, if so, lays out the bins.  keys: the sorted stream
 // (block << 58 | row << 29 | col), is_hot: 1 = stays in the stream; on success entries of rows too heavy for a bin are
-// re-flagged as staying.  plan->row_bin is a device array and plan->host_bins a host array, both freed by pb_plan_release.
-int pb_plan(BsfFormat& f, const uint64_t* keys, int64_t E, const int* live, int hot, unsigned char* is_hot, PbPlan* plan, bool* use) {
+// re-flagged as staying.  plan->row_bin is a device array and plan->host_bins a host array, both freed by pb_plan_release
+// (pb_plan below: on every error return as well).
+static int pb_plan_layout(BsfFormat& f, const uint64_t* keys, int64_t E, const int* live, int hot, unsigned char* is_hot, PbPlan* plan,
+                          bool* use) {
     *use = false;
     // PGH_PB=0 switches the image off; PGH_PB_FORCE=1 lifts the size heuristics below (tests).
     const char* env = getenv("PGH_PB");
@@ -1020,7 +1023,7 @@ int pb_plan(BsfFormat& f, const uint64_t* keys, int64_t E, const int* live, int 
     std::vector<unsigned char> small((size_t)f.n_out);
     std::vector<std::pair<uint32_t, uint32_t>> big;          // (row, count), ascending rows
     {
-        const uint32_t cap = (uint32_t)std::max<int64_t>(1 << 16, f.n_out / 16);
+        uint32_t cap = (uint32_t)std::max<int64_t>(1 << 16, f.n_out / 16);
         PbBuf<unsigned char> d_small;
         PbBuf<uint32_t> d_rows, d_cnts, d_n;
         PGH_TRY(d_small.alloc(f.n_out));
@@ -1033,7 +1036,23 @@ int pb_plan(BsfFormat& f, const uint64_t* keys, int64_t E, const int* live, int 
         PGH_HIP(hipMemcpyAsync(small.data(), d_small.p, (size_t)f.n_out, hipMemcpyDeviceToHost, r.stream));
         PGH_HIP(hipMemcpyAsync(&big_n, d_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, r.stream));
         PGH_HIP(hipStreamSynchronize(r.stream));
-        PGH_CHECK(big_n <= cap, "propagation blocking: more rows with 255 or more cold entries than the planner lists");
+        if (big_n > cap) {
+            // dense graphs (most rows with hundreds of cold entries): the list did not hold them all -- grown to the count and filled
+            // again (the order the atomics gave does not matter: the list is sorted below)
+            cap = big_n;
+            PbBuf<uint32_t> rows_all, cnts_all;
+            PGH_TRY(rows_all.alloc(cap));
+            PGH_TRY(cnts_all.alloc(cap));
+            std::swap(d_rows.p, rows_all.p);               // (the short lists leave with rows_all / cnts_all)
+            std::swap(d_cnts.p, cnts_all.p);
+            PGH_HIP(hipMemsetAsync(d_n.p, 0, sizeof(uint32_t), r.stream));
+            k_pb_counts_small<<<pb_blocks_for(f.n_out), kBlock, 0, r.stream>>>(d_counts.p, f.n_out, d_small.p, d_rows.p, d_cnts.p, d_n.p, cap);
+            PGH_HIP(hipGetLastError());
+            uint32_t again = 0;
+            PGH_HIP(hipMemcpyAsync(&again, d_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, r.stream));
+            PGH_HIP(hipStreamSynchronize(r.stream));
+            PGH_CHECK(again == big_n, "propagation blocking: the rows with 255 or more cold entries changed between two counts");
+        }
         std::vector<uint32_t> rows(big_n), cnts(big_n);
         if (big_n > 0) {
             PGH_HIP(hipMemcpyAsync(rows.data(), d_rows.p, sizeof(uint32_t) * big_n, hipMemcpyDeviceToHost, r.stream));
@@ -1228,6 +1247,15 @@ int pb_plan(BsfFormat& f, const uint64_t* keys, int64_t E, const int* live, int 
     }
     *use = true;
     return 0;
+}
+
+int pb_plan(BsfFormat& f, const uint64_t* keys, int64_t E, const int* live, int hot, unsigned char* is_hot, PbPlan* plan, bool* use) {
+    const int rc = pb_plan_layout(f, keys, E, live, hot, is_hot, plan, use);
+    if (rc != 0) {                                     // a failed plan keeps nothing (need-list ranks, row -> bin map, host arrays)
+        pb_plan_release(plan);
+        *use = false;
+    }
+    return rc;
 }
 
 // cold_keys: the entries of the image as stream keys (block << 58 | row << 29 | col), any order; cold_vals: values or null.
