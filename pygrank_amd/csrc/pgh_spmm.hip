@@ -952,13 +952,17 @@ struct PermuteIn2 {
 __global__ __launch_bounds__(WG) void k_mm_permute_in2(PermuteIn2 q, const int32_t* __restrict__ perm, int64_t n_int, int64_t n_valid, int b, int ld) {
     const int lpr = lanes_per_row(ld), rows_per_wave = 64 / lpr;
     const int lane = threadIdx.x & 63, l = lane & (lpr - 1), c4 = 4 * l;
-    if (c4 >= ld) return;
+    // lanes whose float4 lies beyond the row take no part in the pass but stay for the workgroup's fold of the first step's sums: the
+    // fold zeroes the shared array and writes every column's partial with all threads (an early return left those of the columns
+    // c with 4 * (c % lanes) >= ld unwritten, and the predicted quotient of those columns was garbage -- every run of such a width
+    // paused at its first check)
+    const bool active = c4 < ld;
     const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + (threadIdx.x >> 6)) * rows_per_wave + lane / lpr;
     const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
     const bool vec = (b & 3) == 0;
     int nz_count = 0, live_count = 0;
     double t0[4] = {0.0, 0.0, 0.0, 0.0}, sp[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t r = first; r < n_int; r += stride) {
+    for (int64_t r = first; active && r < n_int; r += stride) {
         const int64_t o = perm ? perm[r] : (r < n_valid ? r : -1);
         auto fetch = [&](const float* src) __attribute__((always_inline)) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -994,7 +998,7 @@ __global__ __launch_bounds__(WG) void k_mm_permute_in2(PermuteIn2 q, const int32
         const unsigned long long anyx = __ballot(xnz) >> (lane & ~(lpr - 1));
         const bool row_nz = (anyx & ((1ULL << lpr) - 1ULL)) != 0ULL;
         (void)row_nz;
-        // (wave-uniform counts by ballot: lanes beyond the row length have left the kernel, a shuffle would read their registers)
+        // (wave-uniform counts by ballot: lanes beyond the row length are not in the loop, a shuffle would read their registers)
         nz_count += mm_store_row_bytes(q.nz_map, r - lane / lpr, n_int, __ballot(xnz), lpr, lane);
         live_count += __popcll(__ballot(l == 0 && flags != 0));
     }

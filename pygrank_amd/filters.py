@@ -63,7 +63,8 @@ def _propagate_in_batches(ranker, features, cfg, run):
         if status == L.BATCH_DECLINED and not batches:
             return None
         L.check(status)
-        batches.append([dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms)
+        batches.append([dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms,
+                             flags=r.flags)
                         for r in results])
         ranker.last_batches = batches
         for r, nrm in zip(results, norms):
@@ -444,7 +445,8 @@ class PageRank(RecursiveGraphFilter):
                 L.check(L.lib().pgh_ppr_run_batch_dropout(g._h, P._h, R._h, C.byref(cfg), scales, dropout, seed0, results))
             else:
                 L.check(L.lib().pgh_ppr_run_batch(g._h, P._h, R._h, C.byref(cfg), scales, results))
-            info = [dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms)
+            info = [dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms,
+                         flags=r.flags)
                     for r in results]
             self.last_batches.append(info)
             for r, nrm in zip(results, norms):
