@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h).
+"""ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
+include/pgh_tune.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -208,6 +209,19 @@ BATCH_SIGNATURES = {
 }
 BATCH_DECLINED = 2        # include/pgh_batch.h PGH_BATCH_DECLINED: the loop does not serve this input, nothing was written
 
+# name -> (restype, argtypes); every symbol include/pgh_tune.h declares.  Bound apart like the batch loops (tune_entry): on a library
+# without them the tuner scores its probes column by column.
+c_plan = C.c_void_p
+TUNE_SIGNATURES = {
+    "pgh_probe_plan_create": (C.c_int, [c_vec, c_vec, C.POINTER(c_plan)]),
+    "pgh_probe_plan_info": (C.c_int, [c_plan, c_i64p, c_i64p]),
+    "pgh_probe_plan_destroy": (C.c_int, [c_plan]),
+    "pgh_probe_auc": (C.c_int, [c_mat, C.c_void_p, C.c_int32, C.c_int32, c_plan, c_f64p]),
+}
+TUNE_DECLINED = 2         # include/pgh_tune.h PGH_TUNE_DECLINED: nothing was written, the caller takes the unfused route
+TUNE_LDS_BYTES = 61440    # include/pgh_tune.h PGH_TUNE_LDS_BYTES
+TUNE_MAX_POSITIVES = 8192 # include/pgh_tune.h PGH_TUNE_MAX_POSITIVES
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -225,10 +239,9 @@ def _bind(cdll):
     return cdll
 
 
-def bind_batch(cdll):
-    """Binds the include/pgh_batch.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+def _bind_optional(cdll, table):
     bound = {}
-    for name, (restype, argtypes) in BATCH_SIGNATURES.items():
+    for name, (restype, argtypes) in table.items():
         try:
             fn = getattr(cdll, name)
         except AttributeError:
@@ -238,6 +251,26 @@ def bind_batch(cdll):
         fn.argtypes = argtypes
         bound[name] = fn
     return bound
+
+
+def bind_batch(cdll):
+    """Binds the include/pgh_batch.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, BATCH_SIGNATURES)
+
+
+def bind_tune(cdll):
+    """Binds the include/pgh_tune.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, TUNE_SIGNATURES)
+
+
+def tune_entry(name):
+    """The bound include/pgh_tune.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_tune_entries", None)
+    if cache is None:
+        cache = bind_tune(cdll)
+        cdll._pgh_tune_entries = cache
+    return cache[name]
 
 
 def batch_entry(name):

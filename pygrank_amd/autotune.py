@@ -1,0 +1,368 @@
+"""Parameter tuning: the coordinate descent of [krasanakis2022autogf] and the tuner built on it.
+
+Restates pygrank/algorithms/autotune/optimization.py:9-25,64-212 (``optimize``), autotune/tuning.py:5-23 (``Tuner``) and
+autotune/parameterized.py:9-177 (``default_tuning_optimization``, ``SelfClearDict``, ``ParameterTuner``).
+
+One addition to the reference.  A coordinate step of ``optimize`` scores ``partitions`` candidates that differ in ONE weight.  When
+the loss object has a callable attribute ``many`` the step hands it the whole candidate list in one call.  ``ParameterTuner`` builds
+such a loss for its default setting (GenericGraphFilter over stored powers, measure AUC): the candidates of a step share the power
+slab of the training personalization (filters._PowerSlab), and ``pgh_probe_auc`` (include/pgh_tune.h) scores all of them in one
+streaming pass over it -- no [n, P] ranks, no normalisation, no compaction and no sort of n pairs per candidate.
+"""
+import ctypes as C
+import sys
+from collections.abc import Iterable
+from math import log
+from random import random
+
+import numpy as np
+
+from pygrank_amd import _lib as L
+from pygrank_amd.measures import AUC, split
+from pygrank_amd.preprocessing import preprocessor
+from pygrank_amd.signals import NodeRanking, to_signal
+from pygrank_amd.utils import remove_used_args
+
+
+def _log(text=""):
+    """pygrank/core/utils/__init__.py log(): progress on one console line."""
+    sys.stdout.write("\r" + text)
+    sys.stdout.flush()
+
+
+def _add(weights, index, increment, max_val, min_val, coarse=0):
+    """optimization.py:9-25: a copy of `weights` with `increment` added at `index`, clipped to [min_val, max_val] and (coarse != 0)
+    snapped to multiples of `coarse`."""
+    weights = [weight for weight in weights]
+    weights[index] = min(max_val, max(min_val, weights[index] + increment))
+    if coarse != 0:
+        weights[index] = round(weights[index] / coarse) * coarse
+    return weights
+
+
+def optimize(loss, max_vals=[1 for _ in range(1)], min_vals=None, deviation_tol=1.E-9, divide_range=1.01, partitions=5,
+             parameter_tol=float('inf'), depth=1, coarse=0, shrink_strategy="divide", partition_strategy="split", randomize=False,
+             weights=None, verbose=True, validation_loss=None):
+    """optimization.py:64-212: coordinate descent over the box [min_vals, max_vals].  Every step shrinks the search range of the
+    current variable ("divide": by divide_range; "shrinking": (max - min) / ((iter + 1)^divide_range log(iter + 2))), scores the
+    candidates of that variable ("split": `partitions` points across the range; "step": multiples of `partitions` inside it), moves to
+    the FIRST candidate of least loss and goes to the next variable (a random one with `randomize`), until the loss moved by at
+    most deviation_tol over a whole round and every range is at most parameter_tol.  `validation_loss` picks the returned weights among
+    the visited ones; `depth` > 1 restarts from the result with fresh ranges; `weights` is the starting point (default: the centre).
+
+    `loss.many(candidate_weights) -> [losses]`, when the loss object has it, is called once per step instead of `loss` once per
+    candidate; it must return what ``[loss(w) for w in candidate_weights]`` would."""
+    if min_vals is None:
+        min_vals = [0 for _ in max_vals]
+    for min_val, max_val in zip(min_vals, max_vals):
+        if min_val > max_val:
+            raise Exception("Empty parameter range [" + str(min_val) + "," + str(max_val) + "]")
+    if str(divide_range) != "shrinking" and divide_range <= 1:
+        raise Exception("divide_range should be greater than 1, otherwise the search space never shrinks.")
+    if weights is None:
+        weights = [(min_val + max_val) / 2 for min_val, max_val in zip(min_vals, max_vals)]
+    range_search = [(max_val - min_val) / 2 for min_val, max_val in zip(min_vals, max_vals)]
+    many = getattr(loss, "many", None)
+    if not callable(many):
+        many = None
+    curr_variable = 0
+    iteration = 0
+    range_deviations = [float('inf')] * len(max_vals)
+    best_weights = weights
+    best_loss = float('inf')
+    evals = 0
+    while True:
+        if randomize:
+            curr_variable = int(random() * len(weights))
+        if max(range_search) == 0:
+            break
+        if shrink_strategy == "shrinking":
+            range_search[curr_variable] = (max_vals[curr_variable] - min_vals[curr_variable]) \
+                / ((iteration + 1) ** divide_range * log(iteration + 2))
+        elif shrink_strategy == "divide":
+            range_search[curr_variable] /= divide_range
+        else:
+            raise Exception("Invalid shrink strategy: either shrinking or divide expected")
+        if range_search[curr_variable] == 0:
+            range_deviations[curr_variable] = 0
+            curr_variable += 1
+            if curr_variable >= len(max_vals):
+                curr_variable -= len(max_vals)
+            continue
+        if partition_strategy == "split":
+            increments = [range_search[curr_variable] * (part * 2. / (partitions - 1) - 1) for part in range(partitions)]
+        elif partition_strategy == "step":
+            reach = int(range_search[curr_variable] / partitions)
+            increments = [part * partitions for part in range(-reach, 1 + reach)]
+        else:
+            raise Exception("Invalid partition strategy: either split or step expected")
+        candidate_weights = [_add(weights, curr_variable, increment, max_vals[curr_variable], min_vals[curr_variable], coarse=coarse)
+                             for increment in increments]
+        losses = list(many(candidate_weights)) if many is not None else [loss(w) for w in candidate_weights]
+        if len(losses) != len(candidate_weights):
+            raise Exception("loss.many must return one loss per candidate")
+        loss_pairs = list(zip(candidate_weights, losses))
+        evals += len(loss_pairs)
+        weights, weights_loss = min(loss_pairs, key=lambda pair: pair[1])
+        prev_best_loss = best_loss
+        if validation_loss is not None:
+            weights_loss = validation_loss(weights)
+            if weights_loss < best_loss:
+                best_loss = weights_loss
+                best_weights = weights
+        else:
+            best_loss = weights_loss
+            best_weights = weights
+        range_deviations[curr_variable] = abs(prev_best_loss - best_loss)
+        if verbose:
+            _log(f"Tuning evaluations {evals} loss {best_loss:.8f} +- {max(range_deviations):.8f}")
+        if max(range_deviations) <= deviation_tol and max(range_search) <= parameter_tol:
+            break
+        iteration += 1
+        curr_variable += 1
+        if curr_variable >= len(max_vals):
+            curr_variable -= len(max_vals)
+    weights = best_weights
+    if verbose:
+        _log()
+    if depth > 1:
+        return optimize(loss, max_vals, min_vals, deviation_tol, divide_range, partitions, parameter_tol, depth - 1, coarse,
+                        shrink_strategy, partition_strategy, randomize, weights, verbose, validation_loss)
+    return weights
+
+
+default_tuning_optimization = {                             # parameterized.py:9-21
+    "max_vals": [1] + [1] * 40,
+    "min_vals": [1] + [0] * 40,
+    "deviation_tol": 1.E-6,
+    "parameter_tol": 1,
+    "verbose": True,
+    "divide_range": 1.01,
+    "partitions": 5,
+    "depth": 1,
+    "coarse": 0,
+    "shrink_strategy": "divide",
+    "partition_strategy": "split"
+}
+
+
+class SelfClearDict(dict):
+    """parameterized.py:24-35: a dictionary that holds one entry at a time (it clears itself before every assignment).  As the
+    `optimization_dict` of a closed-form filter it keeps the stored powers of the LAST personalization only: back-to-back calls on
+    one personalization (a tuner's probes) reuse them, and a new personalization releases the old slab."""
+
+    def __setitem__(self, key, value):
+        self.clear()
+        super().__setitem__(key, value)
+
+
+class Tuner(NodeRanking):
+    """tuning.py:5-23: a ranker that first finds the ranker to run."""
+
+    def tune(self, graph=None, personalization=None, *args, **kwargs):
+        return self._tune(graph, personalization, *args, **kwargs)[0]
+
+    def rank(self, graph=None, personalization=None, *args, **kwargs):
+        ranker, personalization = self._tune(graph, personalization, *args, **kwargs)
+        return ranker.rank(graph, personalization, *args, **kwargs)
+
+    def _tune(self, graph=None, personalization=None, *args, **kwargs):
+        raise Exception("Tuners should implement a _tune method")
+
+
+class _ProbePlan:
+    """The node classes of one validation split on the device (pgh_probe_plan_create, include/pgh_tune.h)."""
+
+    def __init__(self, known, exclude):
+        self._h = L.c_plan()
+        L.check(L.tune_entry("pgh_probe_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
+        pos, neg = C.c_int64(), C.c_int64()
+        L.check(L.tune_entry("pgh_probe_plan_info")(self._h, C.byref(pos), C.byref(neg)))
+        self.num_positive, self.num_negative = pos.value, neg.value
+
+    def __del__(self):
+        try:
+            if self._h is not None and L._lib is not None:
+                L.tune_entry("pgh_probe_plan_destroy")(self._h)
+        except Exception:
+            pass
+        self._h = None
+
+
+class _ProbeLoss:
+    """The tuner's loss for its default setting: ``loss(params)`` is the reference's one-probe evaluation
+    (parameterized.py:135-145), ``loss.many(candidates)`` scores a coordinate step's candidates together.
+
+    ``many``, per validation split: the candidates become GenericGraphFilter variants that share the tuner's optimisation dict, so
+    the split's power slab is found (or built) there and a later rank() on the same personalization finds it too; every variant's
+    coefficients are cut where its own stopping rule ends it (ClosedFormGraphFilter.probe_coefficients).  Then
+      * fused: ``pgh_probe_auc`` -- one pass over the slab for all candidates -- when the library exports it and does not decline;
+      * unfused: ``rank_many``'s [n, P] product and one ``measures.AUC`` per column with the split's `exclude`.
+    Neither route applies the generator's ``Normalize("max")``: the AUC does not change under division by a positive maximum (a
+    zero maximum means all-zero scores, AUC 0.5 either way), while an f32 division can round two neighbouring scores onto one
+    value and so turn a strict order into a tie -- which is why the unfused route leaves it out as well when it stands in for the
+    fused one (the two then agree to the last bit).  ``loss(params)`` keeps the reference's pipeline, Normalize included.
+    Losses are -best_direction * AUC averaged over the splits."""
+
+    def __init__(self, tuner, splits, filter_kwargs, args, kwargs):
+        self.tuner, self.splits, self.filter_kwargs, self.args, self.kwargs = tuner, splits, filter_kwargs, args, kwargs
+        self._plans = {}
+
+    def __call__(self, params):
+        return self.tuner._evaluate(self.splits, params, self.args, self.kwargs)
+
+    def _plan(self, index, validation, exclude):
+        plan = self._plans.get(index)
+        if plan is None:
+            plan = self._plans[index] = _ProbePlan(validation.np, None if exclude is None else to_signal(validation, exclude).np)
+        return plan
+
+    def _fused(self, index, validation, exclude, slab, coefficients):
+        """[AUC of every column of `coefficients`] through pgh_probe_auc, or None when the entry is missing or declines."""
+        entry = L.tune_entry("pgh_probe_auc")
+        if entry is None or slab.chebyshev or len(slab.slabs) < 1:     # (more than one slab of terms: the entry declines)
+            return None
+        plan = self._plan(index, validation, exclude)
+        terms, probes = coefficients.shape
+        flat = np.ascontiguousarray(coefficients, dtype=np.float64)
+        out = (C.c_double * probes)()
+        status = entry(slab.slabs[0]._h, flat.ctypes.data_as(C.c_void_p), terms, probes, plan._h, out)
+        if status == L.TUNE_DECLINED:
+            if plan.num_positive == 0 or plan.num_negative == 0:
+                raise Exception("Cannot evaluate AUC when all labels are the same")
+            return None
+        L.check(status)
+        return list(out)
+
+    def many(self, candidates):
+        from pygrank_amd.filters import GenericGraphFilter
+        candidates = list(candidates)
+        totals = [0.0] * len(candidates)
+        stats = self.tuner.last_tune
+        for start in range(0, len(candidates), 64):
+            chunk = candidates[start:start + 64]
+            variants = [GenericGraphFilter(params, **self.filter_kwargs) for params in chunk]
+            for index, (training, validation, exclude) in enumerate(self.splits):
+                direction = AUC(validation, exclude).best_direction()
+                plan = variants[0].probe_coefficients(training, None, variants)
+                aucs = None if plan is None or self.tuner.fuse is False else \
+                    self._fused(index, validation, exclude, plan[0], plan[1])
+                if aucs is not None:
+                    stats["fused_steps"] += 1
+                else:
+                    stats["unfused_steps"] += 1
+                    ranks = plan[0].combine_many(plan[1]) if plan is not None else variants[0].rank_many(training, None, variants)[0]
+                    measure = AUC(validation, exclude)
+                    aucs = [measure.evaluate(to_signal(training, ranks.column(q))) for q in range(len(chunk))]
+                for q, auc in enumerate(aucs):
+                    totals[start + q] -= direction * auc
+        return [total / len(self.splits) for total in totals]
+
+
+class ParameterTuner(Tuner):
+    """parameterized.py:38-177: tunes the parameters of a ranker family under a supervised measure on a training / validation
+    split of the personalization [krasanakis2022autogf].
+
+    ranker_generator: parameters -> ranker.  None (default): ``Normalize(GenericGraphFilter(params, ...))`` with an immutable-graph
+        preprocessor and a ``SelfClearDict`` optimisation dict unless the keywords say otherwise; the filter's keywords are taken
+        from kwargs (those ``optimize`` has no parameter for).
+    measure: known scores, exclude -> supervised measure (default AUC).
+    fraction_of_training: one ``split`` argument, or an iterable of them (one split each, seeds 0, 1, ...; losses are averaged).
+    cross_validate: number of tuning runs (split seeds shifted by the run's number) whose parameters are averaged.
+    combined_prediction: rank() applies the tuned ranker to the whole personalization (default) or to the training part.
+    tuning_backend: None or "hip" (this package has one engine).
+    optimizer: ``optimize`` or any callable(loss, **optimize arguments) -> parameters.
+    kwargs: the arguments of ``optimize`` (defaults: ``default_tuning_optimization``) and of the generated filter.
+
+    After a run ``last_params`` holds the tuned parameters and ``last_tune`` how many candidate batches took the fused
+    (``fused_steps``) and the unfused (``unfused_steps``) route of the default setting; ``fuse=False`` keeps ``many`` off the
+    fused entry (the unfused route then serves every step)."""
+
+    def __init__(self, ranker_generator=None, measure=AUC, fraction_of_training=0.9, cross_validate=1, combined_prediction=True,
+                 tuning_backend=None, optimizer=optimize, **kwargs):
+        if tuning_backend not in (None, "hip"):
+            raise Exception("tuning_backend is None or 'hip': this package drives one engine")
+        self.fuse = kwargs.pop("fuse", True)
+        self._filter_kwargs = None
+        if ranker_generator is None:
+            from pygrank_amd.filters import GenericGraphFilter
+            from pygrank_amd.postprocess import Normalize
+            if 'preprocessor' not in kwargs and 'assume_immutability' not in kwargs and 'normalization' not in kwargs:
+                kwargs['preprocessor'] = preprocessor(assume_immutability=True)
+            if "optimization_dict" not in kwargs:
+                kwargs["optimization_dict"] = SelfClearDict()
+            filter_kwargs = self._filter_kwargs = remove_used_args(optimize, kwargs)
+
+            def ranker_generator(params):
+                return Normalize(GenericGraphFilter(params, **filter_kwargs))
+        self.ranker_generator = ranker_generator
+        self.measure = measure
+        self.fraction_of_training = fraction_of_training
+        self.optimize_args = {kwarg: kwargs.get(kwarg, val) for kwarg, val in default_tuning_optimization.items()}
+        self.combined_prediction = combined_prediction
+        self.tuning_backend = tuning_backend
+        self.cross_validate = cross_validate
+        self.optimizer = optimizer
+        self.last_tune = dict(fused_steps=0, unfused_steps=0)
+
+    def _run(self, personalization, params, *args, **kwargs):
+        return self.ranker_generator(params).rank(personalization, *args, **kwargs)
+
+    def _evaluate(self, splits, params, args, kwargs):
+        """parameterized.py:135-145: the loss of one parameter vector, one rank() and one measure per split."""
+        val = 0
+        for training, validation, exclude in splits:
+            measure = self.measure(validation, exclude)
+            val = val - measure.best_direction() * measure.evaluate(self._run(training, params, *args, **kwargs))
+        return val / len(splits)
+
+    def _splits(self, personalization, seed0):
+        """[(training, validation, exclude)] of one tuning run (parameterized.py:125-133,143: the training part is excluded from the
+        measure unless it IS the validation part)."""
+        fractions = self.fraction_of_training if isinstance(self.fraction_of_training, Iterable) else [self.fraction_of_training]
+        splits = []
+        for seed, fraction in enumerate(fractions):
+            training, validation = split(personalization, fraction, seed0 + seed)
+            same = training is validation or np.array_equal(training._mirror(), validation._mirror())
+            splits.append((training, validation, None if same else training))
+        return splits
+
+    def _loss(self, splits, args, kwargs):
+        """The loss handed to the optimiser: with a ``many`` only for the default generator under AUC and no extra rank()
+        arguments; anything else is the reference's one-probe-at-a-time loss."""
+        if self._filter_kwargs is not None and self.measure is AUC and not args and not kwargs \
+                and self._filter_kwargs.get("optimization_dict") is not None \
+                and self._filter_kwargs.get("coefficient_type", "taylor").lower() in ("taylor", "chebyshev") \
+                and self._filter_kwargs.get("krylov_dims") is None:
+            return _ProbeLoss(self, splits, self._filter_kwargs, args, kwargs)
+        return lambda params: self._evaluate(splits, params, args, kwargs)
+
+    def _tune(self, graph=None, personalization=None, *args, **kwargs):
+        personalization = to_signal(graph, personalization)
+        self.last_tune = dict(fused_steps=0, unfused_steps=0)
+        total_params = []
+        training = personalization
+        for seed0 in range(self.cross_validate):
+            splits = self._splits(personalization, seed0)
+            training = splits[-1][0]
+            total_params.append(self.optimizer(self._loss(splits, args, kwargs), **self.optimize_args))
+        best_params = [0 for _ in total_params[0]]
+        for params in total_params:                          # parameterized.py:153-161: the mean over the runs
+            for i in range(len(best_params)):
+                best_params[i] += params[i] / self.cross_validate
+        self.last_params = best_params
+        return self.ranker_generator(best_params), personalization if self.combined_prediction else training
+
+    def references(self):
+        withheld = self.fraction_of_training
+        withheld = f"{1 - withheld:.3f}" if not isinstance(withheld, Iterable) else \
+            "/".join(f"{1 - fraction:.3f}" for fraction in withheld)
+        name = getattr(self.measure, "__name__", type(self.measure).__name__)
+        desc = "parameters tuned \\cite{krasanakis2022autogf} to optimize " + name \
+               + f" while withholding {withheld} of nodes for validation"
+        ret = list(self.ranker_generator([-42]).references())      # an invalid parameter value marks where the parameters are named
+        for i in range(len(ret)):
+            if "-42" in ret[i]:
+                ret[i] = desc
+                return ret
+        return ret + [desc]

@@ -855,6 +855,19 @@ class ClosedFormGraphFilter(GraphFilter):
         `variants`: filters like this one (same graph pipeline, same convergence settings are NOT required: every variant
         stops by its own rule).  Needs an optimisation dict on self (its powers -- or, for the "chebyshev" form, the terms of
         the f64 recurrence -- are shared); returns (DeviceMatrix, [iterations of every variant])."""
+        plan = self.probe_coefficients(graph, personalization, variants)
+        if plan is None:
+            from pygrank_amd.device import DeviceMatrix
+            zeros = backend.repeat(0.0, len(to_signal(graph, personalization).np))
+            return DeviceMatrix.from_columns([zeros] * len(variants)), [0] * len(variants)
+        slab, C_, iterations = plan
+        return slab.combine_many(C_), iterations
+
+    def probe_coefficients(self, graph, personalization, variants):
+        """What rank_many multiplies: (the power slab of this personalization, the [terms, P] coefficient matrix of the variants --
+        every variant cut where its own stopping rule ends it, preserve_norm folded in --, [iterations of every variant]), or None
+        for an all-zero personalization (every rank is zero).  A caller that only needs a statistic of the P columns (the tuner's
+        AUC, include/pgh_tune.h) takes it from here without the [n, P] product."""
         if self.optimization_dict is None:
             raise Exception("rank_many evaluates stored powers: construct the filter with optimization_dict={}")
         if len(variants) < 1 or len(variants) > 64:
@@ -864,9 +877,8 @@ class ClosedFormGraphFilter(GraphFilter):
         personalization = self.personalization_transform(personalization)
         raw = personalization.np
         norm = raw.abssum() if isinstance(raw, DeviceVector) else backend.sum(backend.abs(raw))
-        from pygrank_amd.device import DeviceMatrix
         if norm == 0:
-            return DeviceMatrix.from_columns([backend.repeat(0.0, len(raw))] * len(variants)), [0] * len(variants)
+            return None
         personalization = to_signal(personalization, personalization.np / norm)
         M = self.preprocessor(self._prepare_graph(personalization.graph, personalization))
         slab = self._slab_for(M, personalization)
@@ -890,7 +902,7 @@ class ClosedFormGraphFilter(GraphFilter):
         C_ = np.zeros((max(terms, 1), len(columns)))
         for q, c in enumerate(columns):
             C_[:len(c), q] = c
-        return slab.combine_many(C_), iterations
+        return slab, C_, iterations
 
     def _fused_loop(self, M, personalization, ranks, out_scale, *args, **kwargs):
         if args or kwargs or type(self)._step is not ClosedFormGraphFilter._step \

@@ -7,8 +7,10 @@ Restates pygrank/measures/supervised.py:18-47 (Supervised.to_numpy), :93-98 (Max
 (subtract, abs, sum).  AUC (supervised.py:255-263) is one device sort (pgh_auc); the other evaluation measures of the
 reference (NDCG, ...) are out of scope.
 """
+import collections.abc
 import ctypes as C
 import numbers
+import random
 
 from pygrank_amd import _lib as L
 from pygrank_amd import backend
@@ -22,6 +24,9 @@ class Measure:
 
     def evaluate(self, scores):
         raise Exception("Non-abstract subclasses of Measure should implement an evaluate method")
+
+    def best_direction(self):                                # measures/utils.py:15-24
+        return 1
 
 
 class Supervised(Measure):
@@ -47,6 +52,16 @@ class Supervised(Measure):
             raise Exception("Needs to parse graph signal scores or known_scores to be able to exclude specific nodes")
         plain = backend.to_array(scores, copy_array=bool(normalization))
         return backend.to_array(known), (backend.self_normalize(plain) if normalization else plain)
+
+    def best_direction(self):
+        """supervised.py:49-54: 1 when larger values of the measure are better, -1 otherwise -- found once per class by scoring a
+        perfect and an inverted answer."""
+        cls = type(self)
+        found = cls.__dict__.get("_best_direction")
+        if found is None:
+            found = 1 if cls([1, 0])([1, 0]) > cls([1, 0])([0, 1]) else -1
+            cls._best_direction = found
+        return found
 
     def evaluate(self, scores):
         known, scores = self.to_numpy(scores)
@@ -141,3 +156,36 @@ class Dot(_Pairwise):                                        # supervised.py:217
     def evaluate(self, scores):
         known, scores = self._pair(scores)
         return known.dot(scores)
+
+
+def split(groups, training_samples=0.8, seed=0):
+    """measures/utils.py:48-92: (training, test) of a graph signal (its non-zero nodes are dealt to the two sides, the others are
+    zero on both), of an iterable (two lists) or of a mapping of such (two mappings).  training_samples: below 1 a fraction, above 1
+    a count, negative = all but that many, exactly 1 = no split (both sides are the input).  The order is the reference's:
+    ``sorted`` (unless seed is None), then ``random.Random(seed).shuffle``.  The non-zero nodes of a signal are read from its host
+    mirror (one download) instead of one dictionary read per node of the graph."""
+    if training_samples == 1:
+        return groups, groups
+    if isinstance(groups, collections.abc.Mapping) and not isinstance(groups, GraphSignal):
+        training, testing = {}, {}
+        for group_id, group in groups.items():
+            training[group_id], testing[group_id] = split(group, training_samples, seed)
+        return training, testing
+    values = None
+    if isinstance(groups, GraphSignal):
+        values, node2id = groups._mirror(), groups.node2id
+        if hasattr(node2id, "n"):                            # nodes are positions (signals._IdentityMap): ascending = iteration order
+            group = [int(i) for i in values.nonzero()[0]]
+        else:
+            group = [node for node in groups if values[node2id[node]] != 0]
+    else:
+        group = list(groups)
+    if seed is not None:
+        group = sorted(group)
+    random.Random(seed).shuffle(group)
+    count = len(group)
+    cut = int(training_samples) if training_samples > 1 else \
+        (int(count * training_samples) if training_samples >= 0 else count + int(training_samples))
+    if values is None:
+        return group[:cut], group[cut:]
+    return tuple(to_signal(groups, {node: float(values[groups.node2id[node]]) for node in side}) for side in (group[:cut], group[cut:]))
