@@ -90,7 +90,8 @@ int pgh_filter_out(pgh_vec_t x, pgh_vec_t exclude, pgh_vec_t out, int64_t* out_l
 
 /* Ordinals / Top (algorithms/postprocess/postprocess.py:163-195,246-290): out[i] = 1 + the number of entries
  * that sort before x[i] in descending order of value (ties: lower index first, as python's stable sorted(reverse=True));
- * value of the k-th largest entry (k >= 1).  One device radix sort each. */
+ * value of the k-th largest entry (k >= 1).  One device radix sort each.  -0.0 and +0.0 tie.  The positions are stored as
+ * f32, like every vector: exact for vectors of up to 2^24 entries, rounded to the nearest f32 beyond. */
 int pgh_vec_ordinals(pgh_vec_t x, pgh_vec_t out);
 /* AUC of scores against binary labels (non-zero = positive), ties at their mid-rank: what sklearn.metrics.roc_curve + auc
  * compute in the reference (measures/supervised.py:255-263), with one device sort.  *num_positive receives the number of

@@ -213,7 +213,8 @@ class DeviceVector:
         return self.sum() / self._n
 
     def ordinals(self):
-        """1 for the largest entry, 2 for the next ... (ties: lower index first); one device radix sort."""
+        """1 for the largest entry, 2 for the next ... (ties: lower index first); one device radix sort.  The positions are stored as
+        f32, like every vector: exact for vectors of up to 2^24 entries."""
         out = DeviceVector.empty(self._n)
         L.check(L.lib().pgh_vec_ordinals(self._h, out._h))
         return out

@@ -460,6 +460,65 @@ def check_device_postprocessors_and_measures(pg):
         assert abs(got - want) <= 1e-6 * abs(want), (key, got, want)
 
 
+def check_postprocessors_on_tie_laden_signals(pg):
+    """Ordinals / Top / Threshold (postprocess.py:163-350) on signals full of ties -- a seed-set rank (one large zero group) and
+    draws from a handful of values with signed zeros and subnormals -- against dict-level restatements of what the reference does
+    with python's stable sorted(): ties keep node order, Top keeps every node that ties with the k-th, a count outside [1, n]
+    leaves the threshold at 0, a threshold equal to a score that occurs separates > from >=, "gap" takes the first largest drop.
+    All outputs are integers or 0 / 1: equality."""
+    import kernel_checks
+    n = 300
+    rng = np.random.default_rng(41)
+    A = sp.csr_array(sp.random(n, n, density=0.02, random_state=np.random.RandomState(5), format="csr"))
+    graph = pg.AdjacencyWrapper(A, directed=True)
+
+    def descending(scores):
+        return sorted(scores, key=scores.get, reverse=True)          # stable: equal scores stay in node order
+
+    def ordinals(scores):
+        want = np.zeros(n)
+        for position, node in enumerate(descending(scores)):
+            want[node] = position + 1
+        return want
+
+    def top(scores, keep):
+        count = int(keep * n) if keep < 1 else int(keep)
+        cut = scores[descending(scores)[count - 1]] if 1 <= count <= n else 0
+        return np.array([1.0 if scores[node] >= cut else 0.0 for node in range(n)])
+
+    def gap(scores):
+        best, cut, before = 0, 0, 0
+        for node in descending(scores):
+            if before > 0 and (before - scores[node]) / before > best:
+                best, cut = (before - scores[node]) / before, scores[node]
+            before = scores[node]
+        return cut
+
+    def threshold(scores, cut, inclusive):
+        cut = gap(scores) if cut == "gap" else cut
+        return np.array([1.0 if (scores[node] >= cut if inclusive else scores[node] > cut) else 0.0 for node in range(n)])
+
+    for kind in ("dup", "ppr"):
+        x = kernel_checks.order_statistics_input(rng, n, kind)
+        scores = {node: float(x[node]) for node in range(n)}
+        signal = pg.to_signal(graph, x)
+
+        def out(algo):
+            return np.asarray(algo.transform(signal).np, dtype=np.float64)
+        assert np.array_equal(out(pg.Ordinals()), ordinals(scores)), kind
+        for keep in (1, 5, n, n + 3, 0.5, 0.5 / n):
+            assert np.array_equal(out(pg.Top(keep)), top(scores, keep)), (kind, keep)
+        assert out(pg.Top(0.5 / n)).sum() == np.sum(x >= 0)              # no node asked for: the threshold stays 0
+        occurring = sorted(set(x[x > 0]))
+        for cut in (0.0, float(occurring[0]), float(occurring[len(occurring) // 2]), float(occurring[-1])):
+            strict, inclusive = out(pg.Threshold(cut)), out(pg.Threshold(cut, inclusive=True))
+            assert np.array_equal(strict, threshold(scores, cut, False)), (kind, cut)
+            assert np.array_equal(inclusive, threshold(scores, cut, True)), (kind, cut)
+            assert inclusive.sum() - strict.sum() == np.sum(x == cut) > 0, (kind, cut)
+        for inclusive in (False, True):
+            assert np.array_equal(out(pg.Threshold("gap", inclusive=inclusive)), threshold(scores, "gap", inclusive)), (kind, inclusive)
+
+
 def check_generic_route_equals_fused_route(pg):
     """The per-step backend-primitive route (reference structure) and the fused device loop agree."""
     import cases

@@ -953,4 +953,185 @@ def check_trimmed_gather_layout(pg):
             assert rc != 0 and b"gather vector" in lib.pgh_last_error()
 
 
+ORDER_LENGTHS = [0, 1, 2, 3, 255, 256, 257, 4099, 100003, (1 << 20) + 7]
+ORDER_KINDS = ("dense", "ppr", "dup", "const", "neg", "geometric", "one_positive", "one_positive_over_negatives")
+DUP_VALUES = np.array([-1.5, -0.0, 0.0, 1e-40, 2e-40, 0.25, 0.5, 1.0, 2.0, 4.0, 8.0]).astype(F32).astype(np.float64)
+
+
+def order_statistics_input(rng, n, kind):
+    """One f32-representable score vector (as f64) of the kinds the order statistics are checked on."""
+    if kind == "dense":
+        x = rng.random(n) - 0.3
+    elif kind == "ppr":                                      # most entries exactly 0: one large tie group, as a seed-set rank has
+        x = np.zeros(n)
+        hit = rng.choice(n, size=min(n, max(n // 20, 1)), replace=False) if n else np.zeros(0, dtype=np.int64)
+        x[hit] = rng.random(len(hit)) ** 8
+    elif kind == "dup":                                      # signed zeros, two subnormals, equal relative drops of 0.5
+        x = DUP_VALUES[rng.integers(0, len(DUP_VALUES), n)]
+    elif kind == "const":
+        x = np.full(n, 0.75)
+    elif kind == "neg":
+        x = -1.001 - 2.0 * rng.random(n)
+    elif kind == "geometric":                                # every drop of the descending order is 0.5 (or 0)
+        x = np.tile([8.0, 4.0, 2.0, 1.0], n // 4 + 1)[:n]
+    elif kind in ("one_positive", "one_positive_over_negatives"):
+        x = np.zeros(n)
+        if kind == "one_positive_over_negatives" and n:
+            below = rng.random(n) < 0.3
+            x[below] = -0.5 - rng.random(int(below.sum()))
+        if n:
+            x[int(rng.integers(0, n))] = 0.625
+    else:
+        raise KeyError(kind)
+    return x.astype(F32).astype(np.float64)
+
+
+def gap_threshold_reference(x64):
+    """Threshold("gap") of the reference (postprocess.py:335-344) without its Python loop: over the descending order,
+    d = (prev - cur) / prev where prev > 0; the score after the FIRST largest d when that d is > 0, else 0."""
+    v = np.sort(x64)[::-1]
+    if len(v) < 2:
+        return 0.0
+    prev, cur = v[:-1], v[1:]
+    d = np.zeros(len(prev))
+    live = prev > 0
+    d[live] = (prev[live] - cur[live]) / prev[live]
+    first = int(np.argmax(d))                                # numpy returns the first index of the maximum
+    return float(cur[first]) if d[first] > 0 else 0.0
+
+
+def auc_reference(scores64, labels):
+    """(S / (2 n_pos n_neg), n_pos) with S = sum over negatives of 2 #(positives above it) + #(positives equal to it), an integer."""
+    pos = np.sort(scores64[labels != 0])
+    neg = scores64[labels == 0]
+    lb = np.searchsorted(pos, neg, side="left")
+    ub = np.searchsorted(pos, neg, side="right")
+    S = int(np.sum(2 * (len(pos) - ub) + (ub - lb), dtype=np.int64))
+    return S / (2 * len(pos) * len(neg)), len(pos)
+
+
+def check_order_statistics_against_numpy(pg):
+    """pgh_vec_ordinals / pgh_vec_kth_largest / pgh_vec_gap_threshold / pgh_auc (one radix sort of (value, index) pairs each, then
+    k_auc_partials / k_gap_max / k_gap_first) against plain numpy in f64 on the same f32-representable scores: lengths on both sides
+    of the sort's single-block path and over several grid periods of the kernels behind it; ties in ascending index order, -0.0
+    tying with +0.0; subnormals that must neither merge with 0 nor with each other; constant and all-negative vectors; equal
+    drops, of which the first wins.  Every output is an integer, one of the inputs, or ONE rounding of a ratio of integers below
+    2^53 -- so every comparison is exact.  NaN scores are out of scope (the reference's sorted() has no defined order for them)."""
+    import pytest
+    from pygrank_amd import _lib as L
+    rng = np.random.default_rng(31)
+    for n in ORDER_LENGTHS:
+        for kind in (("dense", "ppr") if n > (1 << 20) else ORDER_KINDS):
+            x = order_statistics_input(rng, n, kind)
+            dx = _vec(pg, x)
+            back = _np(dx)
+            # the upload and the download keep every f32 value: subnormals (flushed to zero they would join the zero tie group) and the sign of zero
+            assert np.array_equal(back, x) and np.array_equal(np.signbit(back), np.signbit(x)), (n, kind)
+            if kind == "dup" and n >= 255:
+                assert 0.0 < DUP_VALUES[3] < DUP_VALUES[4] < 1e-38 and set(back[(back > 0) & (back < 1e-38)]) == set(DUP_VALUES[3:5]), n
+            # ---- Ordinals: positions in the stable descending order (ties: lower index first, -0.0 == +0.0)
+            want = np.empty(n)
+            want[np.argsort(-x, kind="stable")] = np.arange(1, n + 1)
+            assert np.array_equal(_np(dx.ordinals()), want), (n, kind)
+            # ---- kth_largest
+            descending = np.sort(x)[::-1]
+            for k in sorted({1, (n + 1) // 2, n} - {0}) if n else ():
+                assert dx.kth_largest(k) == descending[k - 1], (n, kind, k)
+            for k in (0, n + 1):
+                with pytest.raises(L.EngineError):
+                    dx.kth_largest(k)
+            # ---- gap_threshold: IEEE f64 operations on identical operands on both sides
+            assert dx.gap_threshold() == gap_threshold_reference(x), (n, kind)
+            if kind == "geometric" and n >= 2:
+                assert dx.gap_threshold() == 4.0, n         # the first of the equal drops: 8 -> 4
+            if kind == "one_positive" and n >= 2:
+                assert dx.gap_threshold() == 0.0, n         # the only drop is 0.625 -> 0: d = 1
+            # ---- AUC: both sides round the same rational S / (2 n_pos n_neg) once
+            for n_pos in sorted({1, n // 3, n - 1} - {0, n}) if n >= 2 else ():
+                labels = np.zeros(n)
+                chosen = rng.choice(n, size=n_pos, replace=False)
+                labels[chosen] = np.where(rng.random(n_pos) < 0.25, 2.0, 1.0)      # non-zero means positive
+                want_auc, want_pos = auc_reference(x, labels)
+                dl = _vec(pg, labels)
+                got, positives = C.c_double(-7.0), C.c_int64(-7)
+                L.check(L.lib().pgh_auc(dl._h, dx._h, C.byref(got), C.byref(positives)))
+                assert positives.value == want_pos == n_pos, (n, kind, n_pos)
+                assert got.value == want_auc, (n, kind, n_pos, got.value, want_auc)
+                assert float(pg.AUC(dl)(dx)) == want_auc, (n, kind, n_pos)
+            if n:
+                for same in (0.0, 2.0):                      # all labels equal: the measure raises
+                    with pytest.raises(Exception, match="all labels are the same"):
+                        pg.AUC(_vec(pg, np.full(n, same)))(dx)
+    empty = _vec(pg, np.zeros(0))
+    got, positives = C.c_double(-7.0), C.c_int64(-7)
+    L.check(L.lib().pgh_auc(empty._h, empty._h, C.byref(got), C.byref(positives)))
+    assert got.value == 0.0 and positives.value == 0
+
+
+SLAB_GEMM_SHAPES = [(1, 1, 1, 1, 1), (1000, 12, 5, 5, 7), (300, 64, 0, 3, 3), (513, 64, 41, 4, 4), (513, 64, 41, 8, 8), (513, 64, 41, 9, 12),
+                    (4097, 64, 64, 16, 16), (4097, 64, 64, 17, 17), (777, 64, 33, 32, 32), (777, 64, 33, 33, 40), (4097, 64, 64, 64, 64),
+                    (140001, 64, 3, 33, 33)]          # (n, b, count, probes, out.b); the last: more workgroups than the grid's cap at 16 lanes per row
+
+
+def check_slab_contractions_against_numpy(pg):
+    """pgh_mat_gemm / pgh_mat_gemv (a filter, or P filters, evaluated from stored powers) against numpy in f64 on the same
+    f32-representable slab: every lanes-per-row instantiation of k_mat_gemm on both sides of its probes boundary, a probes count
+    that is no multiple of 4, an `out` wider than the product, accumulation, fewer terms than slab columns, no terms at all, and
+    the 4-way unroll tail of k_mat_gemv.  Integer-valued data make every partial sum exact in any order: equality.  Random data are
+    held to the bound written at the assertion."""
+    from pygrank_amd.device import DeviceMatrix
+    rng = np.random.default_rng(37)
+
+    def bound(want, X, c, count, out0=None):
+        # |got - want| <= EPS32 |want|: the ONE rounding to f32 of the f64 sum; + count 2^-52 (|X| @ |c|): two f64 evaluations of a
+        # count-term sum in different orders, each within count 2^-53 (|X| @ |c|) of the exact value; + EPS32 |out| when accumulating
+        limit = EPS32 * np.abs(want) + count * 2.0 ** -52 * (np.abs(X[:, :count]) @ np.abs(c))
+        return limit if out0 is None else limit + EPS32 * np.abs(out0)
+
+    for n, b, count, probes, out_b in SLAB_GEMM_SHAPES:
+        for data in ("integer", "random"):
+            if data == "integer":
+                X = rng.integers(-8, 9, (n, b)).astype(np.float64)
+                c = rng.integers(-4, 5, (count, probes)).astype(np.float64)
+                out0 = rng.integers(-16, 17, (n, out_b)).astype(np.float64)
+            else:
+                X = (rng.random((n, b)) * 2 - 1).astype(F32).astype(np.float64)
+                c = rng.normal(size=(count, probes))
+                out0 = (rng.random((n, out_b)) * 2 - 1).astype(F32).astype(np.float64)
+            D = DeviceMatrix.from_host(X)
+            product = X[:, :count] @ c                              # zeros of shape [n, probes] when count == 0
+            for accumulate in (False, True):
+                out = DeviceMatrix.from_host(out0)
+                assert D.gemm(c, out=out, accumulate=accumulate) is out
+                got = np.asarray(out)
+                want = out0[:, :probes] + product if accumulate else product
+                label = (n, b, count, probes, out_b, data, accumulate)
+                assert np.array_equal(got[:, probes:], out0[:, probes:]), label       # columns at or beyond `probes` are not written
+                if data == "integer" or count == 0:                                  # (no terms: zeros, or `out` as it was)
+                    assert np.array_equal(got[:, :probes], want), label
+                else:
+                    assert np.all(np.abs(got[:, :probes] - want) <= bound(want, X, c, count, out0[:, :probes] if accumulate else None)), label
+                if not accumulate:
+                    plain = got
+            if out_b == probes:                                     # ... and into the slab that gemm() allocates by itself: the same bits
+                fresh = np.asarray(D.gemm(c))
+                assert fresh.shape == (n, probes) and np.array_equal(fresh, plain), (n, b, count, probes, data)
+    b = 70
+    for n in (1, 257, 70001):
+        for data in ("integer", "random"):
+            if data == "integer":
+                X = rng.integers(-8, 9, (n, b)).astype(np.float64)
+            else:
+                X = (rng.random((n, b)) * 2 - 1).astype(F32).astype(np.float64)
+            D = DeviceMatrix.from_host(X)
+            for count in (0, 1, 3, 4, 5, 64, 70):
+                c = rng.integers(-4, 5, count).astype(np.float64) if data == "integer" else rng.normal(size=count)
+                got = _np(D.gemv(c))
+                want = X[:, :count] @ c
+                if data == "integer" or count == 0:
+                    assert got.shape == (n,) and np.array_equal(got, want), (n, count, data)
+                else:
+                    assert np.all(np.abs(got - want) <= bound(want, X, c, count)), (n, count, data)
+
+
 ALL = [v for k, v in sorted(globals().items()) if k.startswith("check_") and callable(v)]
