@@ -50,6 +50,7 @@ struct pgh_graph_s {
     std::vector<float> degrees;
     std::vector<int32_t> part_perm;   // new id -> old id for row-partitioned graphs
     int64_t row_begin = 0;
+    bool has_src_scale = false;       // factored upload with a source scale: resident iterates carry a gather form (as the engine's value-free images do)
     // gather-vector layout of partitioned graphs (pgh_graph_gather_layout / pgh_graph_set_gather_bases)
     int32_t gather_blocks = 1;
     int64_t gather_blk = 0;
@@ -496,7 +497,9 @@ int pgh_graph_from_factored_csr(int64_t n_rows, int64_t n_cols, int64_t nnz, con
     for (int64_t r = 0; r < n_rows; ++r)
         for (int64_t k = indptr[r]; k < indptr[r + 1]; ++k)
             data[k] = ((left ? left[r] : 1.0) * w[k]) * (right ? right[indices[k]] : 1.0);      // preprocessing.py:113,138
-    return pgh_graph_from_csr(n_rows, n_cols, nnz, indptr, indices, data.data(), flags, out);
+    if (pgh_graph_from_csr(n_rows, n_cols, nnz, indptr, indices, data.data(), flags, out)) return 1;
+    (*out)->has_src_scale = left != nullptr;
+    return 0;
 }
 int pgh_graph_from_adjacency(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* indptr, const int32_t* indices,
                              const double* w, int32_t normalization, int flags, pgh_graph_t* out) {
@@ -684,7 +687,8 @@ int pgh_ppr_step(pgh_graph_t g, pgh_vec_t x, double xs, pgh_vec_t p, double alph
 }
 // ---- resident iterates (include/pgh.h): the double's "id space" is deliberately NOT the caller's -- ids reversed, three zero padding
 // slots behind them, a gather form that holds twice the iterate -- so that host logic that mixes the two spaces, forgets the padding or
-// gathers from the wrong form fails on the CPU
+// gathers from the wrong form fails on the CPU.  As on the engine, only graphs uploaded with a source scale have a gather form
+// (n_gather > 0); the others gather from x_int itself and take NULL for every xg / yg.
 static const int64_t kResidentPad = 3;
 static bool resident_ok(const pgh_graph_s* g) {
     const char* e = getenv("PGH_RESIDENT");
@@ -698,13 +702,14 @@ int pgh_last_build_profile(char* buf, int buflen) {
 int pgh_graph_resident_len(pgh_graph_t g, int64_t* n_int, int64_t* n_gather) {
     CHECK(g && n_int && n_gather, "pgh_graph_resident_len: null argument");
     *n_int = resident_ok(g) ? g->n_cols + kResidentPad : 0;
-    *n_gather = resident_ok(g) ? g->n_cols + kResidentPad + 1 : 0;
+    *n_gather = resident_ok(g) && g->has_src_scale ? g->n_cols + kResidentPad + 1 : 0;
     return 0;
 }
 int pgh_resident_in(pgh_graph_t g, pgh_vec_t x, double hole, pgh_vec_t x_int, pgh_vec_t xg) {
     CHECK(resident_ok(g), "pgh_resident_in: this graph's image has no resident form");
     const int64_t n = g->n_cols;
-    CHECK(x && x_int && x->n == n && x_int->n == n + kResidentPad && (xg == nullptr || xg->n == n + kResidentPad + 1), "pgh_resident_in: vector length mismatch");
+    CHECK(x && x_int && x->n == n && x_int->n == n + kResidentPad, "pgh_resident_in: vector length mismatch");
+    CHECK(xg == nullptr || (g->has_src_scale && xg->n == n + kResidentPad + 1), "pgh_resident_in: gather form mismatch");
     for (int64_t i = 0; i < n; ++i) x_int->data[i] = x->data[n - 1 - i];
     for (int64_t i = n; i < n + kResidentPad; ++i) x_int->data[i] = (float)hole;
     if (xg != nullptr)
@@ -712,7 +717,7 @@ int pgh_resident_in(pgh_graph_t g, pgh_vec_t x, double hole, pgh_vec_t x_int, pg
     return 0;
 }
 int pgh_resident_gather(pgh_graph_t g, pgh_vec_t x_int, pgh_vec_t xg) {
-    CHECK(resident_ok(g), "pgh_resident_gather: this graph's image has no resident form");
+    CHECK(resident_ok(g) && g->has_src_scale, "pgh_resident_gather: this graph's image has no gather form");
     const int64_t n = g->n_cols;
     CHECK(x_int && xg && x_int->n == n + kResidentPad && xg->n == n + kResidentPad + 1, "pgh_resident_gather: vector length mismatch");
     for (int64_t i = 0; i < n + kResidentPad; ++i) xg->data[i] = 2.f * x_int->data[i];
@@ -731,12 +736,14 @@ int pgh_resident_step(pgh_graph_t g, int32_t mode, pgh_vec_t x_int, pgh_vec_t xg
     const int64_t n = g->n_cols;
     CHECK(mode >= 0 && mode <= 2, "pgh_resident_step: mode 0, 1 or 2");
     CHECK(mode != 2 || (deg_int && lam_int && deg_int->n == n + kResidentPad && lam_int->n == n + kResidentPad), "pgh_resident_step: mode 2 needs the resident degrees and absorption");
-    CHECK(x_int && xg && y_int && yg && x_int->n == n + kResidentPad && y_int->n == n + kResidentPad && xg->n == n + kResidentPad + 1 &&
-              yg->n == n + kResidentPad + 1 && x_int->data != y_int->data && xg->data != yg->data,
+    CHECK(x_int && y_int && x_int->n == n + kResidentPad && y_int->n == n + kResidentPad && x_int->data != y_int->data,
           "pgh_resident_step: iterate length mismatch / aliasing");
+    const bool scaled = g->has_src_scale;
+    CHECK(!scaled || (xg && yg && xg->n == n + kResidentPad + 1 && yg->n == n + kResidentPad + 1 && xg->data != yg->data),
+          "pgh_resident_step: this image gathers from the gather form");
     CHECK(mode == 0 || (v_int && v_int->n == n + kResidentPad), "pgh_resident_step: modes 1 and 2 need the resident second operand");
     std::vector<float> x((size_t)n);
-    for (int64_t i = 0; i < n; ++i) x[(size_t)(n - 1 - i)] = 0.5f * xg->data[i];        // the step gathers from the gather form
+    for (int64_t i = 0; i < n; ++i) x[(size_t)(n - 1 - i)] = scaled ? 0.5f * xg->data[i] : x_int->data[i];      // the step gathers from the gather form
     double sum = 0;
     const float fa = (float)a, fb = (float)b;
     for (int64_t r = 0; r < n; ++r) {
@@ -750,7 +757,8 @@ int pgh_resident_step(pgh_graph_t g, int32_t mode, pgh_vec_t x_int, pgh_vec_t xg
         sum += v;
     }
     for (int64_t i = n; i < n + kResidentPad; ++i) y_int->data[i] = 0.f;
-    for (int64_t i = 0; i < n + kResidentPad; ++i) yg->data[i] = 2.f * y_int->data[i];
+    if (scaled)
+        for (int64_t i = 0; i < n + kResidentPad; ++i) yg->data[i] = 2.f * y_int->data[i];
     if (sum_y) *sum_y = sum;
     return 0;
 }

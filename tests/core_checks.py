@@ -521,24 +521,49 @@ def check_postprocessors_on_tie_laden_signals(pg):
 
 def check_generic_route_equals_fused_route(pg):
     """The per-step backend-primitive route (reference structure) and the fused device loop agree."""
+    import os
     import cases
+    from oracle import rmat_np
+    from pygrank_amd import _lib as L
     A, directed, p = cases.GRAPHS["rmat10_dir"]()
-    graph = pg.AdjacencyWrapper(A, directed=directed)
-    for make in (lambda **k: pg.PageRank(0.85, tol=1e-6, **k),
-                 lambda **k: pg.PageRank(0.85, use_quotient=False, error_type=pg.L1, tol=1e-6, max_iters=500, **k),
-                 lambda **k: pg.AbsorbingWalks(0.9, tol=1e-6, max_iters=500, **k),
-                 lambda **k: pg.HeatKernel(t=5, error_type="iters", max_iters=21, **k),
-                 lambda **k: pg.HeatKernel(t=5, coefficient_type="chebyshev", error_type="iters", max_iters=21, **k),
-                 lambda **k: pg.GenericGraphFilter([0.5, 0.3, 0, 0.2], tol=1e-7, **k)):
-        fused = make()
-        r_fused = fused.rank(graph, p.copy())
-        assert hasattr(fused, "last_loop")
-        generic = make()
-        generic._fused_loop = lambda *a, **k: False
-        r_generic = generic.rank(graph, p.copy())
-        assert generic.convergence.iteration == fused.convergence.iteration
-        got, want = np.asarray(r_fused.np), np.asarray(r_generic.np)
-        assert np.max(np.abs(got - want)) <= 2e-6 * np.max(np.abs(want))
+    graphs = [(pg.AdjacencyWrapper(A, directed=directed), p, {})]
+    keys = ("PGH_PB", "PGH_PB_FORCE", "PGH_PB_HEAVY", "PGH_PB_HUBMAX")
+    saved = {k: os.environ.get(k) for k in keys}
+    try:
+        if L.runtime_name().startswith("hip:"):
+            # ... and on a graph beyond the small-graph image, its cold tail forced into the propagation-blocking image (the switches of
+            # kernel_checks.check_propagation_blocking_image): both routes run on the one image the shared preprocessor built
+            A17 = rmat_np.rmat_csr(17, 16, seed=1)
+            p17 = np.zeros(A17.shape[0])
+            p17[rmat_np.seed_nodes(A17, 50, seed=4)] = 1.0
+            os.environ.update(PGH_PB="1", PGH_PB_FORCE="1", PGH_PB_HEAVY="256", PGH_PB_HUBMAX="2000")
+            pre = pg.preprocessor(assume_immutability=True)
+            graph17 = pg.AdjacencyWrapper(A17, directed=True)
+            adj = pre(graph17)
+            assert "propagation-blocking" in getattr(adj, "array", adj).format()
+            graphs.append((graph17, p17, dict(preprocessor=pre)))
+        for graph, p, extra in graphs:
+            for make in (lambda **k: pg.PageRank(0.85, tol=1e-6, **k),
+                         lambda **k: pg.PageRank(0.85, use_quotient=False, error_type=pg.L1, tol=1e-6, max_iters=500, **k),
+                         lambda **k: pg.AbsorbingWalks(0.9, tol=1e-6, max_iters=500, **k),
+                         lambda **k: pg.HeatKernel(t=5, error_type="iters", max_iters=21, **k),
+                         lambda **k: pg.HeatKernel(t=5, coefficient_type="chebyshev", error_type="iters", max_iters=21, **k),
+                         lambda **k: pg.GenericGraphFilter([0.5, 0.3, 0, 0.2], tol=1e-7, **k)):
+                fused = make(**extra)
+                r_fused = fused.rank(graph, p.copy())
+                assert hasattr(fused, "last_loop")
+                generic = make(**extra)
+                generic._fused_loop = lambda *a, **k: False
+                r_generic = generic.rank(graph, p.copy())
+                assert generic.convergence.iteration == fused.convergence.iteration
+                got, want = np.asarray(r_fused.np), np.asarray(r_generic.np)
+                assert np.max(np.abs(got - want)) <= 2e-6 * np.max(np.abs(want))
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def check_warm_start_and_propagate(pg):                      # abstract_filters.py:47,56; signals.py:225-226

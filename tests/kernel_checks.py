@@ -1134,4 +1134,290 @@ def check_slab_contractions_against_numpy(pg):
                     assert np.all(np.abs(got - want) <= bound(want, X, c, count)), (n, count, data)
 
 
+RESIDENT_REPORT = {}      # graph -> {"format", "n", "n_int", "n_gather", "ratio": {mode: worst |error| / bound}}; filled by the check below
+
+
+def _restore_env(saved):
+    import os
+    for k, v in saved.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+
+
+def lengths_of(g):
+    from pygrank_amd import _lib as L
+    n_int, n_gather = C.c_int64(-1), C.c_int64(-1)
+    L.check(L.lib().pgh_graph_resident_len(g._h, C.byref(n_int), C.byref(n_gather)))
+    return n_int.value, n_gather.value
+
+
+def _resident_graphs(pg):
+    """(name, graph, cold) of every image the resident calls are checked on; `cold`: built with the cold image forced, whose row
+    sums are fixed point (the bound of check_propagation_blocking_image).  Built one at a time: a generator."""
+    import os
+    from pygrank_amd import _lib as L
+    from pygrank_amd.device import DeviceGraph
+    for name, M in matrices():
+        if name in ("empty5", "single", "dense40", "sparse_3000", "hubs_5000", "rmat14", "rmat16_ef16"):
+            yield name, pg.scipy_sparse_to_backend(M), False
+    rng = np.random.default_rng(41)
+    A = rmat_np.rmat_csr(14, 8, seed=2)
+    W = sp.csr_array(A.copy())
+    W.data = W.data * (0.5 + rng.random(W.nnz))
+    yield "factored_col", DeviceGraph.from_adjacency(A, "col"), False                    # value-free: a gather form
+    yield "factored_col_real", DeviceGraph.from_adjacency(W, "col"), False               # the same structure, valued
+    yield "factored_symmetric", DeviceGraph.from_adjacency(sp.csr_array(A + A.T), "symmetric"), False
+    if not L.runtime_name().startswith("hip:"):
+        return
+    # graphs below 2 M nodes get ONE column block, whose id space has no padding: four blocks forced on row counts that are no multiple
+    # of the blocks' granule, so that the padding assertions have slots to look at on the engine too
+    small = dict(matrices())
+    odd = sp.csr_array(A[:16001, :16001])
+    saved = {"PGH_BLOCKS": os.environ.get("PGH_BLOCKS")}
+    try:
+        os.environ["PGH_BLOCKS"] = "4"
+        padded = [("sparse_3000_blocks4", pg.scipy_sparse_to_backend(small["sparse_3000"])),
+                  ("hubs_5000_blocks4", pg.scipy_sparse_to_backend(small["hubs_5000"])),
+                  ("factored_col_16001_blocks4", DeviceGraph.from_adjacency(odd, "col"))]
+    finally:
+        _restore_env(saved)
+    assert any(lengths_of(g)[0] > g.shape[0] for _, g in padded), [g.format() for _, g in padded]
+    while padded:
+        name, g = padded.pop(0)
+        yield name, g, False
+        del g
+    A = rmat_np.rmat_csr(17, 16, seed=1)                        # 131 K nodes: four times the LDS hot cache
+    W = sp.csr_array(A.copy())
+    W.data = W.data * (0.5 + rng.random(W.nnz))
+    keys = ("PGH_PB", "PGH_PB_FORCE", "PGH_PB_HEAVY", "PGH_PB_HUBMAX")
+    saved = {k: os.environ.get(k) for k in keys}
+    try:
+        for label, adj in (("int", A), ("real", W)):
+            for k in keys:
+                os.environ.pop(k, None)
+            os.environ["PGH_PB"] = "0"
+            g0 = DeviceGraph.from_adjacency(adj, "col")
+            os.environ.update(PGH_PB="1", PGH_PB_FORCE="1", PGH_PB_HEAVY="256", PGH_PB_HUBMAX="2000")     # hub bins and rows left in the stream, both
+            g1 = DeviceGraph.from_adjacency(adj, "col")
+            _restore_env(saved)
+            assert "propagation-blocking" in g1.format() and "propagation-blocking" not in g0.format(), (g0.format(), g1.format())
+            yield "rmat17_%s_stream" % label, g0, False
+            del g0
+            yield "rmat17_%s_cold" % label, g1, True
+            del g1
+    finally:
+        _restore_env(saved)
+
+
+def check_resident_iterates_on_every_image(pg):
+    """pgh_graph_resident_len / pgh_resident_in / _gather / _out / _step (modes 0, 1, 2: the backend-primitive route, include/pgh.h)
+    called directly, on every image launch_step dispatches on, against numpy in f64 on the matrix the engine stores and on the input the
+    engine holds (so every bound is that of ONE step): the id space is a permutation plus padding, the way in and out is exact, the
+    gather form a step writes is the one pgh_resident_gather makes, padding slots stay zero through every mode (signed operands: a
+    max or min cannot hide one), sum_y, agreement with pgh_ppr_step / pgh_absorb_step, determinism, refused arguments write nothing,
+    and images without a resident form refuse every call.  Bounds: those of check_fused_steps and check_propagation_blocking_image."""
+    import os
+    from pygrank_amd import _lib as L
+    from pygrank_amd.device import DeviceVector
+    from pygrank_amd.distributed import rmat_partitioned
+    lib = L.lib()
+    hip = L.runtime_name().startswith("hip:")
+    rng = np.random.default_rng(43)
+    a, b = 0.85 * 0.5, 0.15
+    SENTINEL = -7.25
+
+    lengths = lengths_of
+
+    def f32(vec):
+        return vec.numpy(F32)
+
+    def handle(vec):
+        return vec._h if vec is not None else None
+
+    def signed(n):
+        return (rng.random(n) * 2 - 1).astype(F32).astype(np.float64)
+
+    def reduce(kind, vec):
+        out = C.c_double()
+        L.check(lib.pgh_reduce(kind, vec._h, C.byref(out)))
+        return out.value
+
+    RESIDENT_REPORT.clear()
+    gather_lengths = set()
+    for name, g, cold in _resident_graphs(pg):
+        n = g.shape[0]
+        n_int, n_gather = lengths(g)
+        # ---- 1. lengths
+        assert n_int >= n and n_int > 0, (name, n, n_int)
+        assert n_gather == 0 or n_gather > n_int, (name, n_int, n_gather)
+        gather_lengths.add(n_gather > 0)
+        scaled = n_gather > 0
+
+        def bring(x, hole, gather=scaled):
+            x_int, xg, plain = DeviceVector.empty(n_int), DeviceVector.empty(n_gather) if gather else None, _vec(pg, x)
+            L.check(lib.pgh_resident_in(g._h, plain._h, float(hole), x_int._h, handle(xg)))
+            return x_int, xg
+
+        def out(y_int, factor=1.0):
+            y = DeviceVector.empty(n)
+            L.check(lib.pgh_resident_out(g._h, y_int._h, float(factor), y._h))
+            return f32(y)
+
+        def gather_of(x_int):
+            xg = DeviceVector.empty(n_gather)
+            L.check(lib.pgh_resident_gather(g._h, x_int._h, xg._h))
+            return xg
+
+        def step(mode, x_int, xg, v_int=None, deg=None, lam=None, want_sum=True):
+            y_int, yg, s = DeviceVector.empty(n_int), DeviceVector.empty(n_gather) if scaled else None, C.c_double(np.nan)
+            L.check(lib.pgh_resident_step(g._h, mode, x_int._h, handle(xg), a, handle(v_int), b, handle(deg), handle(lam), y_int._h, handle(yg),
+                                          C.byref(s) if want_sum else None))
+            return y_int, yg, s.value
+
+        # ---- 2. the id space is a permutation plus padding
+        mask = f32(bring(np.zeros(n), 1.0, gather=False)[0])
+        assert set(np.unique(mask)) <= {0.0, 1.0} and int(mask.sum()) == n_int - n, (name, n_int - n, float(mask.sum()))
+        pad = mask == 1.0
+        ids = f32(bring(np.arange(1, n + 1), 0.0, gather=False)[0])          # n < 2^24: exact in f32
+        assert np.all(ids[pad] == 0) and np.array_equal(np.sort(ids[~pad]), np.arange(1, n + 1)), name
+        # ---- 3. round trip
+        x, v = signed(n), signed(n)
+        if n > 1:
+            x[0], v[-1] = -0.75, -0.5                                        # the minimum over the live slots is negative
+        x_int, xg = bring(x, 0.0)
+        v_int = bring(v, 0.0, gather=False)[0]
+        assert np.all(f32(x_int)[pad] == 0), name
+        assert np.array_equal(out(x_int), x.astype(F32)), name
+        assert np.allclose(out(x_int, 0.37), x * 0.37, rtol=1.5 * EPS32, atol=0), name
+        deg = (rng.random(n) + 0.1).astype(F32).astype(np.float64)
+        lam = (rng.random(n) + 0.1).astype(F32).astype(np.float64)
+        deg_int, lam_int = bring(deg, 0.0, gather=False)[0], bring(lam, 1.0, gather=False)[0]
+        assert np.all(f32(lam_int)[pad] == 1) and np.all(f32(deg_int)[pad] == 0), name
+
+        N = sp.csr_array(g.download_transposed().astype(np.float64))
+        absN = abs(N)
+        nmax = float(np.max(np.abs(N.data))) if N.nnz else 0.0
+        if cold:          # fixed-point row sums: the bound of check_propagation_blocking_image
+            tol = lambda s, xin: 8 * EPS32 * s + 1e-11 * np.max(np.abs(xin)) * nmax           # noqa: E731
+        else:             # the bound of check_fused_steps
+            tol = lambda s, xin: 4 * EPS32 * s + 1e-30                                         # noqa: E731
+
+        def reference(mode, xin):
+            conv, conv_abs = a * (N @ xin), a * (absN @ np.abs(xin))
+            if mode == 0:
+                return conv, tol(conv_abs, xin)
+            if mode == 1:
+                return conv + b * v, tol(conv_abs + b * np.abs(v), xin)
+            return (conv * deg + v * lam) / (lam + deg), 2 * tol((conv_abs * deg + np.abs(v) * lam) / (lam + deg), xin)
+
+        def row_bound(mode, xin):          # the plain row bound of check_fused_steps, for route-against-route comparisons
+            conv_abs = a * (absN @ np.abs(xin))
+            return conv_abs + b * np.abs(v) if mode == 1 else (conv_abs * deg + np.abs(v) * lam) / (lam + deg)
+
+        ratios = {}
+
+        def verify(mode, label, xin_int, y_int, s):
+            """one step's outcome against f64 on the input the engine holds: values, padding, reductions, sum_y"""
+            xin = out(xin_int).astype(np.float64)
+            y_full = f32(y_int)
+            assert np.all(y_full[pad] == 0), (name, label, "padding", y_full[pad][y_full[pad] != 0][:4])                  # ---- 6.
+            y = out(y_int).astype(np.float64)
+            assert np.array_equal(np.sort(y_full[~pad]), np.sort(y.astype(F32))), (name, label)
+            ref, bound = reference(mode, xin)
+            err = np.abs(y - ref)
+            ratios[label] = max(ratios.get(label, 0.0), float(np.max(err / bound)) if n else 0.0)
+            assert np.all(err <= bound), (name, label, ratios[label])                                                    # ---- 5.
+            if n_int > n:
+                assert reduce(L.MAX, y_int) == max(y.max(), 0.0) and reduce(L.MIN, y_int) == min(y.min(), 0.0), (name, label)
+            else:
+                assert reduce(L.MAX, y_int) == y.max() and reduce(L.MIN, y_int) == y.min(), (name, label)
+            total = max(1.0, np.abs(y).sum())
+            assert abs(s - y.sum()) <= 1e-12 * total, (name, label, s, y.sum())                                          # ---- 7.
+            assert abs(reduce(L.SUM, y_int) - y.sum()) <= 1e-12 * total, (name, label)
+            return y
+
+        results = {}
+        for mode in (0, 1, 2):
+            args = dict(v_int=v_int if mode else None, deg=deg_int if mode == 2 else None, lam=lam_int if mode == 2 else None)
+            y_int, yg, s = step(mode, x_int, xg, **args)
+            results[mode] = verify(mode, "mode%d" % mode, x_int, y_int, s)
+            # ---- 9. determinism; 7. sum_y = NULL gives the same bits
+            again = step(mode, x_int, xg, **args)
+            assert np.array_equal(f32(again[0]), f32(y_int)) and again[2] == s, (name, mode)
+            assert np.array_equal(f32(step(mode, x_int, xg, want_sum=False, **args)[0]), f32(y_int)), (name, mode)
+            # ---- the chained step: its gather form is what the first step's epilogue wrote
+            z_int, zg, sz = step(mode, y_int, yg, **args)
+            verify(mode, "mode%d chained" % mode, y_int, z_int, sz)
+            if scaled:                                                                                                  # ---- 4.
+                assert np.array_equal(f32(step(mode, x_int, gather_of(x_int), **args)[0]), f32(y_int)), (name, mode)
+                other = step(mode, y_int, gather_of(y_int), **args)
+                assert np.array_equal(f32(other[0]), f32(z_int)) and other[2] == sz, (name, mode)
+                if mode == 1:
+                    first = step(1, x_int, gather_of(x_int), **args)
+                    assert first[2] == s, name
+        # ---- 8. the same result as the non-resident route
+        dx, dv, y_plain, s_plain = _vec(pg, x), _vec(pg, v), DeviceVector.empty(n), C.c_double()
+        L.check(lib.pgh_ppr_step(g._h, dx._h, 0.5, dv._h, 0.85, y_plain._h, C.byref(s_plain)))
+        assert np.all(np.abs(_np(y_plain) - results[1]) <= 4 * EPS32 * row_bound(1, x) + 1e-30), name
+        ddeg, dlam = _vec(pg, deg), _vec(pg, lam)
+        L.check(lib.pgh_absorb_step(g._h, dx._h, a, dv._h, ddeg._h, dlam._h, y_plain._h, C.byref(s_plain)))
+        assert np.all(np.abs(_np(y_plain) - results[2]) <= 4 * EPS32 * row_bound(2, x) + 1e-30), name
+        # ---- 10. refused arguments: non-zero, and nothing is written
+        y_int, yg = DeviceVector.full(n_int, SENTINEL), DeviceVector.full(n_gather, SENTINEL) if scaled else None
+        x_before = f32(x_int)
+        longer, shorter = DeviceVector.full(n_int + 1, SENTINEL), DeviceVector.full(max(n_int - 1, 0), SENTINEL)
+
+        def refused(mode, xi, xgi, vi, di, li, yi, ygi):
+            s = C.c_double(SENTINEL)
+            rc = lib.pgh_resident_step(g._h, mode, handle(xi), handle(xgi), a, handle(vi), b, handle(di), handle(li), handle(yi), handle(ygi), C.byref(s))
+            return rc != 0 and s.value == SENTINEL
+        assert refused(0, x_int, xg, None, None, None, x_int, yg), (name, "x_int aliased with y_int")
+        assert refused(3, x_int, xg, v_int, deg_int, lam_int, y_int, yg) and refused(-1, x_int, xg, v_int, deg_int, lam_int, y_int, yg), (name, "mode 3")
+        assert refused(2, x_int, xg, v_int, None, lam_int, y_int, yg) and refused(2, x_int, xg, v_int, deg_int, None, y_int, yg), (name, "mode 2 without deg / lam")
+        assert refused(1, x_int, xg, None, None, None, y_int, yg), (name, "mode 1 without v")
+        assert refused(0, x_int, xg, None, None, None, longer, yg) and refused(0, longer, xg, None, None, None, y_int, yg), (name, "long iterate")
+        assert refused(0, x_int, xg, None, None, None, shorter, yg) and refused(1, x_int, xg, shorter, None, None, y_int, yg), (name, "short operand")
+        assert refused(2, x_int, xg, v_int, shorter, lam_int, y_int, yg) and refused(2, x_int, xg, v_int, deg_int, longer, y_int, yg), (name, "deg / lam length")
+        if scaled:
+            assert refused(1, x_int, None, v_int, None, None, y_int, yg) and refused(1, x_int, xg, v_int, None, None, y_int, None), (name, "missing gather form")
+            assert refused(1, x_int, x_int, v_int, None, None, y_int, yg) and refused(1, x_int, xg, v_int, None, None, y_int, y_int), (name, "gather form length")
+            assert refused(1, x_int, xg, v_int, None, None, y_int, xg), (name, "xg aliased with yg")
+            assert lib.pgh_resident_gather(g._h, x_int._h, y_int._h) != 0 and lib.pgh_resident_gather(g._h, shorter._h, yg._h) != 0, name
+            assert np.all(f32(yg) == SENTINEL), name
+        else:
+            assert lib.pgh_resident_gather(g._h, x_int._h, longer._h) != 0 and b"no gather form" in lib.pgh_last_error(), name
+        assert lib.pgh_resident_in(g._h, dx._h, 0.0, longer._h, None) != 0 and lib.pgh_resident_in(g._h, longer._h, 0.0, y_int._h, None) != 0, name
+        assert lib.pgh_resident_in(g._h, dx._h, 0.0, y_int._h, y_int._h) != 0, (name, "a gather form of the wrong length (or on an image without one)")
+        assert lib.pgh_resident_out(g._h, longer._h, 1.0, dx._h) != 0 and lib.pgh_resident_out(g._h, x_int._h, 1.0, longer._h) != 0, name
+        assert np.all(f32(y_int) == SENTINEL) and np.all(f32(longer) == SENTINEL) and np.all(f32(shorter) == SENTINEL), name
+        assert np.array_equal(f32(x_int), x_before) and np.array_equal(_np(dx), x), name
+        RESIDENT_REPORT[name] = dict(format=g.format(), n=n, n_int=n_int, n_gather=n_gather, ratio=ratios)
+        del g
+    assert gather_lengths == {True, False}, gather_lengths          # both kinds of image were reached
+
+    # ---- images without a resident form report (0, 0) and refuse the calls
+    def refuses(label, g):
+        assert lengths(g) == (0, 0), (label, lengths(g))
+        rows = g.shape[0]
+        u, w = DeviceVector.full(rows, SENTINEL), DeviceVector.full(g.shape[1], SENTINEL)
+        s = C.c_double(SENTINEL)
+        for call in (lambda: lib.pgh_resident_in(g._h, u._h, 0.0, w._h, None), lambda: lib.pgh_resident_out(g._h, u._h, 1.0, w._h),
+                     lambda: lib.pgh_resident_step(g._h, 0, u._h, None, a, None, b, None, None, w._h, None, C.byref(s))):
+            assert call() != 0 and b"no resident form" in lib.pgh_last_error(), (label, lib.pgh_last_error())
+        assert np.all(f32(u) == SENTINEL) and np.all(f32(w) == SENTINEL) and s.value == SENTINEL, label
+
+    refuses("rect_30x70", pg.scipy_sparse_to_backend(dict(matrices())["rect_30x70"]))
+    refuses("partitioned", rmat_partitioned(12, 4, 0, 1).graph)
+    if hip:
+        saved = {"PGH_FORMAT": os.environ.get("PGH_FORMAT")}
+        try:
+            os.environ["PGH_FORMAT"] = "csr"
+            row_major = pg.scipy_sparse_to_backend(rmat_np.rmat_csr(10, 8, seed=1))
+        finally:
+            _restore_env(saved)
+        refuses("PGH_FORMAT=csr", row_major)
+
+
 ALL = [v for k, v in sorted(globals().items()) if k.startswith("check_") and callable(v)]
