@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
-include/pgh_tune.h).
+include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -222,6 +222,15 @@ TUNE_DECLINED = 2         # include/pgh_tune.h PGH_TUNE_DECLINED: nothing was wr
 TUNE_LDS_BYTES = 61440    # include/pgh_tune.h PGH_TUNE_LDS_BYTES
 TUNE_MAX_POSITIVES = 8192 # include/pgh_tune.h PGH_TUNE_MAX_POSITIVES
 
+# name -> (restype, argtypes); every symbol include/pgh_measure.h declares.  Bound apart like the tuner's entries (measure_entry): on a
+# library without them Conductance and Density take the reference's route, one backend primitive at a time.
+MEASURE_SIGNATURES = {
+    "pgh_mat_col_stats": (C.c_int, [c_mat, C.c_void_p]),
+    "pgh_cut_forms": (C.c_int, [c_graph, c_mat, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]),
+}
+MEASURE_DECLINED = 2      # include/pgh_measure.h PGH_MEASURE_DECLINED: nothing was written, the caller takes the per-column route
+CUT_ALL, CUT_INTERNAL = 0, 1                                                        # include/pgh_measure.h PGH_CUT_*
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -261,6 +270,21 @@ def bind_batch(cdll):
 def bind_tune(cdll):
     """Binds the include/pgh_tune.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, TUNE_SIGNATURES)
+
+
+def bind_measure(cdll):
+    """Binds the include/pgh_measure.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, MEASURE_SIGNATURES)
+
+
+def measure_entry(name):
+    """The bound include/pgh_measure.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_measure_entries", None)
+    if cache is None:
+        cache = bind_measure(cdll)
+        cdll._pgh_measure_entries = cache
+    return cache[name]
 
 
 def tune_entry(name):
