@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
-include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h).
+include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
+include/pgh_supervised.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -231,6 +232,15 @@ MEASURE_SIGNATURES = {
 MEASURE_DECLINED = 2      # include/pgh_measure.h PGH_MEASURE_DECLINED: nothing was written, the caller takes the per-column route
 CUT_ALL, CUT_INTERNAL = 0, 1                                                        # include/pgh_measure.h PGH_CUT_*
 
+# name -> (restype, argtypes); every symbol include/pgh_supervised.h declares.  Bound apart like the measures' entries
+# (supervised_entry): on a library without it every supervised measure takes the reference's route, one backend primitive at a time.
+SUPERVISED_SIGNATURES = {
+    "pgh_pair_forms": (C.c_int, [c_mat, c_vec, c_mat, c_vec, c_mat, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]),
+}
+PAIR_DECLINED = 2         # include/pgh_supervised.h PGH_PAIR_DECLINED: nothing was written, the caller takes the per-column route
+PAIR_SLOTS = 20           # include/pgh_supervised.h PGH_PAIR_SLOTS: doubles written per column
+PAIR_MOMENTS, PAIR_LOGS = 0, 1                                                      # include/pgh_supervised.h PGH_PAIR_*
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -275,6 +285,21 @@ def bind_tune(cdll):
 def bind_measure(cdll):
     """Binds the include/pgh_measure.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, MEASURE_SIGNATURES)
+
+
+def bind_supervised(cdll):
+    """Binds the include/pgh_supervised.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, SUPERVISED_SIGNATURES)
+
+
+def supervised_entry(name):
+    """The bound include/pgh_supervised.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_supervised_entries", None)
+    if cache is None:
+        cache = bind_supervised(cdll)
+        cdll._pgh_supervised_entries = cache
+    return cache[name]
 
 
 def measure_entry(name):

@@ -4,8 +4,16 @@ measures on vectors already in HBM (RMabs, MSQ, MSQRT, L2, Eucli
 Restates pygrank/measures/supervised.py:18-47 (Supervised.to_numpy), :93-98 (MaxDifference), :101-106 (Mabs),
 :133-138 (L1).  When both operands are HBM vectors the residual is ONE fused HIP reduction
 (pgh_residual: |a - b| folded into an f64 sum / max) instead of the reference's three passes
-(subtract, abs, sum).  AUC (supervised.py:255-263) is one device sort (pgh_auc); the other evaluation measures of the
-reference (NDCG, ...) are out of scope.
+(subtract, abs, sum).  AUC (supervised.py:255-263) is one device sort (pgh_auc).
+
+The other closed-form supervised measures of the reference are here too: Accuracy, TPR, TNR, PPV (supervised.py:225-271), pRule and
+L2Disparity (:290-333), BinaryCrossEntropy, CrossEntropy, KLDivergence, MKLDivergence (:157-205), PearsonCorrelation (:282-287) and
+MannWhitneyParity (:336-350).  Every supervised measure has ``evaluate_many(columns)`` for the columns of a batch.  All but the
+sort-based ones are functions of a handful of per-column sums over (score, known) pairs, and one streaming kernel takes every such sum
+for 64 columns while it reads each row of the slab once (include/pgh_supervised.h: pgh_pair_forms).  On a
+library without that entry -- the host test double -- the same classes take the reference's route one backend primitive at a time.
+AUC and MannWhitneyParity score a slab through the tuner's pgh_probe_auc (include/pgh_tune.h) with an identity coefficient matrix.
+NDCG, SpearmanCorrelation (a segmented sort per column), Mistreatment and measures/combination.py stay out of scope.
 
 The unsupervised measures Conductance and Density (pygrank/measures/unsupervised.py:8-145) score a ranking without ground truth.  They are
 the reference's only measures that run `conv` themselves: two passes over the adjacency per score column.  Here the columns of a batch
@@ -22,8 +30,8 @@ from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector, lazy_res
 from pygrank_amd.preprocessing import AdjacencyWrapper, preprocessor as default_preprocessor
 from pygrank_amd.signals import GraphSignal, to_signal
 
-# private: True sends Conductance / Density down the per-column route (backend.conv, dot, sum, max) even where the library has the slab
-# entries -- a GPU test compares the two routes with it
+# private: True sends Conductance / Density and the supervised measures' evaluate_many down the per-column route (one backend primitive
+# at a time) even where the library has the slab entries -- a GPU test compares the two routes with it
 _FORCE_PER_COLUMN = False
 
 
@@ -72,6 +80,131 @@ class Supervised(Measure):
             cls._best_direction = found
         return found
 
+    # ---- the columns of a batch -------------------------------------------------------------------------------------------------
+    _GROUP = L.PAIR_MOMENTS       # the slots of pgh_pair_forms the measure is derived from
+    _NORMALIZE = False            # KLDivergence, MKLDivergence: to_numpy(scores, normalization=True)
+    _from_slots = None            # (slots [20], eps) -> value on the slab route; None: no slab route through pgh_pair_forms
+    last_route = None             # "slab" or "columns": the route the last evaluate_many took
+
+    def _one(self, scores):
+        """What the columns route returns for one column."""
+        return self.evaluate(scores)
+
+    @staticmethod
+    def _dense(anchor, obj):
+        """The unfiltered backend vector of scores, known scores or exclude values."""
+        if anchor is not None:
+            return to_signal(anchor, obj).np
+        return backend.to_array([obj] if isinstance(obj, numbers.Number) else obj)
+
+    def _slab_available(self):
+        return self._from_slots is not None and L.supervised_entry("pgh_pair_forms") is not None
+
+    def _operand(self, anchor, side, rows, name):
+        """(vector, matrix) of the known scores or the exclude values for a slab of `rows` rows; one of them is None (both for None)."""
+        if side is None:
+            return None, None
+        if isinstance(side, DeviceMatrix):
+            if side.n != rows:
+                raise Exception(f"{name} of {side.n} rows cannot go with score columns of {rows} rows")
+            return None, side
+        vector = self._dense(anchor, side)
+        vector._h                           # noqa: B018 -- an unevaluated expression (device.LazyVector) is evaluated first
+        if len(vector) != rows:
+            raise Exception(f"a slab of {rows} rows cannot be scored against {name} of {len(vector)} nodes")
+        return vector, None
+
+    def _matrix(self, anchor, columns):
+        if isinstance(columns, DeviceMatrix):
+            return columns
+        return DeviceMatrix.from_columns([self._dense(anchor, column) for column in columns])
+
+    def _slab(self, anchor, columns, count):
+        """The slab route: one pgh_pair_forms call per 64 columns, the values derived on the host from its slots.  None when the engine
+        declines."""
+        import numpy as np
+        entry = L.supervised_entry("pgh_pair_forms")
+        matrix = self._matrix(anchor, columns)
+        known_vec, known_mat = self._operand(anchor, self.known_scores, matrix.n, "known scores")
+        exclude_vec, exclude_mat = self._operand(anchor, self.exclude, matrix.n, "exclude values")
+        eps = backend.epsilon()
+        factors = None
+        if self._NORMALIZE:
+            # supervised.py:182: the scores are normalised BEFORE the excluded nodes leave -- the L1 norm is taken over all rows
+            sums = matrix.col_abssum()
+            factors = np.where(sums != 0, 1.0 / np.where(sums != 0, sums, 1.0), 1.0)
+        out = []
+        for first in range(0, matrix.b, 64):
+            width = min(64, matrix.b - first)
+            whole = matrix.b <= 64
+            part = matrix if whole else matrix.get_cols(first, width)
+            kmat = known_mat if whole or known_mat is None else known_mat.get_cols(first, width)
+            emat = exclude_mat if whole or exclude_mat is None else exclude_mat.get_cols(first, width)
+            chunk = None if factors is None else np.ascontiguousarray(factors[first:first + width])
+            slots = np.empty((width, L.PAIR_SLOTS), dtype=np.float64)
+            status = entry(part._h, None if known_vec is None else known_vec._h, None if kmat is None else kmat._h,
+                           None if exclude_vec is None else exclude_vec._h, None if emat is None else emat._h,
+                           None if chunk is None else chunk.ctypes.data_as(C.c_void_p), eps, self._GROUP,
+                           slots.ctypes.data_as(C.c_void_p))
+            if status == L.PAIR_DECLINED:
+                return None
+            L.check(status)
+            out.extend(self._from_slots([float(v) for v in slots[j]], eps) for j in range(width))
+        return out
+
+    def _per_column(self, anchor, columns):
+        """The columns route: what a loop over evaluate returns."""
+        import copy
+        known, exclude = self.known_scores, self.exclude
+        vectors = columns.columns() if isinstance(columns, DeviceMatrix) else columns
+        out = []
+        for j, column in enumerate(vectors):
+            measure = self
+            if isinstance(known, DeviceMatrix) or isinstance(exclude, DeviceMatrix):
+                measure = copy.copy(self)
+                measure.known_scores = known.column(j) if isinstance(known, DeviceMatrix) else known
+                measure.exclude = exclude.column(j) if isinstance(exclude, DeviceMatrix) else exclude
+            if anchor is not None and not isinstance(column, GraphSignal):
+                column = to_signal(anchor, column)
+            out.append(measure._one(column))
+        return out
+
+    def evaluate_many(self, columns):
+        """What evaluate returns for every column, as a list of floats.  `columns` is a DeviceMatrix, or a list of graph signals or score
+        vectors of one graph.  known_scores and exclude are each one signal or vector shared by the columns, or a DeviceMatrix with one
+        column per score column.  On the slab route the columns share one pass (pgh_pair_forms, 64 columns at a time; AUC: pgh_probe_auc);
+        a column that evaluate would refuse raises here too (the first such column, as a loop over evaluate would)."""
+        known, exclude = self.known_scores, self.exclude
+        if isinstance(columns, DeviceMatrix):
+            count = columns.b
+            anchor = known if isinstance(known, GraphSignal) else None
+        else:
+            columns = list(columns)
+            count = len(columns)
+            if count == 0:
+                return []
+            anchor = next((column for column in columns if isinstance(column, GraphSignal)), None)
+            if anchor is None and isinstance(known, GraphSignal):
+                anchor = known
+            if anchor is not None and any(isinstance(column, GraphSignal) and column.graph is not anchor.graph for column in columns):
+                raise Exception("the score columns belong to different graphs")
+        for name, side in (("known_scores", known), ("exclude", exclude)):
+            if isinstance(side, DeviceMatrix) and side.b != count:
+                raise Exception(f"{name} holds {side.b} columns for {count} score columns")
+        if anchor is None and exclude is not None:
+            raise Exception("Needs to parse graph signal scores or known_scores to be able to exclude specific nodes")
+        if isinstance(columns, DeviceMatrix) and anchor is None and not isinstance(known, (DeviceMatrix, numbers.Number)) \
+                and len(known) != columns.n:
+            # said here once, for both routes, and not by whichever primitive meets the two lengths first
+            raise Exception(f"a slab of {columns.n} rows cannot be scored against known scores of {len(known)} nodes")
+        if not _FORCE_PER_COLUMN and self._slab_available():
+            out = self._slab(anchor, columns, count)
+            if out is not None:
+                self.last_route = "slab"
+                return out
+        self.last_route = "columns"
+        return self._per_column(anchor, columns)
+
     def evaluate(self, scores):
         known, scores = self.to_numpy(scores)
         if isinstance(known, DeviceVector) and isinstance(scores, DeviceVector):
@@ -85,16 +218,40 @@ class Supervised(Measure):
         raise Exception("residual measures expect backend vectors")
 
 
+def _ieee_div(a, b):
+    """a / b as IEEE arithmetic has it (nan for 0 / 0, an infinity for x / 0): what numpy returns where Python raises."""
+    if b != 0:
+        return a / b
+    return float("nan") if a == 0 or a != a else (float("inf") if a > 0 else float("-inf"))
+
+
+def _ieee_sqrt(a):
+    return a ** 0.5 if a >= 0 else float("nan")
+
+
+# The slots of pgh_pair_forms (include/pgh_supervised.h) per column, over the kept rows:
+#   0 count   1 sum s   2 sum s^2   3 sum k   4 sum k^2   5 sum k s   6 sum |k - s|   7 sum (k - s)^2   8 max |k - s|   9 max s   10 max k
+#   11 sum |k|   12 sum k log(s + eps)   13 sum (1 - k) log(1 - s + eps)   14 sum (s + eps) log(s + eps)   15 sum (s + eps) log(k + eps)
+#   16 sum s log(k)
 class MaxDifference(Supervised):                             # supervised.py:93-98
     _KIND = L.ERR_LINF
+
+    def _from_slots(self, s, eps):
+        return s[8]
 
 
 class Mabs(Supervised):                                      # supervised.py:101-106
     _KIND = L.ERR_MABS
 
+    def _from_slots(self, s, eps):
+        return _ieee_div(s[6], s[0])
+
 
 class L1(Supervised):                                        # supervised.py:133-138
     _KIND = L.ERR_L1
+
+    def _from_slots(self, s, eps):
+        return s[6]
 
 
 class _Pairwise(Supervised):
@@ -119,11 +276,17 @@ class RMabs(_Pairwise):                                      # supervised.py:109
         L.check(L.lib().pgh_residual(L.ERR_L1, known._h, scores._h, C.byref(out)))
         return out.value / known.abssum()
 
+    def _from_slots(self, s, eps):
+        return _ieee_div(s[6], s[11])
+
 
 class MSQ(_Pairwise):                                        # supervised.py:117-122
     def evaluate(self, scores):
         total, n = self._squared_distance(scores)
         return total / n
+
+    def _from_slots(self, s, eps):
+        return _ieee_div(s[7], s[0])
 
 
 class MSQRT(_Pairwise):                                      # supervised.py:125-130
@@ -131,15 +294,24 @@ class MSQRT(_Pairwise):                                      # supervised.py:125
         total, n = self._squared_distance(scores)
         return (total / n) ** 0.5
 
+    def _from_slots(self, s, eps):
+        return _ieee_sqrt(_ieee_div(s[7], s[0]))
+
 
 class L2(_Pairwise):                                         # supervised.py:141-146 (the squared distance, as the reference)
     def evaluate(self, scores):
         return self._squared_distance(scores)[0]
 
+    def _from_slots(self, s, eps):
+        return s[7]
+
 
 class Euclidean(_Pairwise):                                  # supervised.py:149-154
     def evaluate(self, scores):
         return self._squared_distance(scores)[0] ** 0.5
+
+    def _from_slots(self, s, eps):
+        return _ieee_sqrt(s[7])
 
 
 class Cos(_Pairwise):                                        # supervised.py:208-214
@@ -147,24 +319,298 @@ class Cos(_Pairwise):                                        # supervised.py:208
         known, scores = self._pair(scores)
         return backend.safe_div(known.dot(scores), (known.dot(known) * scores.dot(scores)) ** 0.5)
 
+    def _from_slots(self, s, eps):
+        return backend.safe_div(s[5], _ieee_sqrt(s[4] * s[2]))
+
+
+class _ProbePlan:
+    """The node classes of one (known scores, exclude) pair on the device (pgh_probe_plan_create, include/pgh_tune.h)."""
+
+    def __init__(self, known, exclude):
+        self._h = L.c_plan()
+        L.check(L.tune_entry("pgh_probe_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
+        positive, negative = C.c_int64(), C.c_int64()
+        L.check(L.tune_entry("pgh_probe_plan_info")(self._h, C.byref(positive), C.byref(negative)))
+        self.num_positive, self.num_negative = positive.value, negative.value
+
+    def __del__(self):
+        try:
+            if self._h is not None and L._lib is not None:
+                L.tune_entry("pgh_probe_plan_destroy")(self._h)
+        except Exception:
+            pass
+        self._h = None
+
 
 class AUC(_Pairwise):                                        # supervised.py:255-263 (sklearn roc_curve + auc in the reference)
     """Area under the ROC curve of the scores against binary known scores, ties at their mid-rank, with ONE device sort
-    (pgh_auc) instead of a trip through sklearn on the host."""
+    (pgh_auc) instead of a trip through sklearn on the host.  The columns of a slab that share their known scores and exclude values
+    are scored by pgh_probe_auc (include/pgh_tune.h) with an identity coefficient matrix (terms = probes = columns): the entry then
+    returns the AUC of each stored column, the value pgh_auc returns for it."""
+    _SAME_CLASS = "Cannot evaluate AUC when all labels are the same"
 
-    def evaluate(self, scores):
+    def _auc(self, scores):
         known, scores = self._pair(scores)
         out, positives = C.c_double(), C.c_int64()
         L.check(L.lib().pgh_auc(known._h, scores._h, C.byref(out), C.byref(positives)))
         if positives.value == 0 or positives.value == len(scores):
-            raise Exception("Cannot evaluate AUC when all labels are the same")
+            raise Exception(self._SAME_CLASS)
         return out.value
+
+    def _of_auc(self, auc):
+        return auc
+
+    def evaluate(self, scores):
+        return self._of_auc(self._auc(scores))
+
+    def _slab_available(self):
+        return all(L.tune_entry(name) is not None for name in L.TUNE_SIGNATURES)
+
+    def _slab(self, anchor, columns, count):
+        import numpy as np
+        if isinstance(self.known_scores, DeviceMatrix) or isinstance(self.exclude, DeviceMatrix):
+            return None                                      # known scores per column: one plan per column, no shared pass
+        matrix = self._matrix(anchor, columns)
+        known, _ = self._operand(anchor, self.known_scores, matrix.n, "known scores")
+        exclude, _ = self._operand(anchor, self.exclude, matrix.n, "exclude values")
+        plan = _ProbePlan(known, exclude)
+        if plan.num_positive == 0 or plan.num_negative == 0:
+            raise Exception(self._SAME_CLASS)
+        out = []
+        for first in range(0, matrix.b, 64):
+            width = min(64, matrix.b - first)
+            part = matrix if matrix.b <= 64 else matrix.get_cols(first, width)
+            identity = np.ascontiguousarray(np.eye(width, dtype=np.float64))
+            aucs = (C.c_double * width)()
+            status = L.tune_entry("pgh_probe_auc")(part._h, identity.ctypes.data_as(C.c_void_p), width, width, plan._h, aucs)
+            if status == L.TUNE_DECLINED:
+                return None
+            L.check(status)
+            out.extend(self._of_auc(float(v)) for v in aucs)
+        return out
 
 
 class Dot(_Pairwise):                                        # supervised.py:217-222
     def evaluate(self, scores):
         known, scores = self._pair(scores)
         return known.dot(scores)
+
+    def _from_slots(self, s, eps):
+        return s[5]
+
+
+class _ClosedForm(_Pairwise):
+    """The measures below: ``evaluate`` is the one-column case of ``evaluate_many``.  ``_value`` is the reference's formula over the
+    filtered vectors, one backend primitive at a time (the columns route); ``_from_slots`` derives the same value from the slots of
+    pgh_pair_forms (the slab route).  On the slab route every ``evaluate`` packs its scores into a one-column DeviceMatrix first: one
+    copy of the vector per call, which a caller that scores many vectors in a loop (a fairness postprocessor's loss) avoids by
+    handing them to ``evaluate_many`` together."""
+
+    def _value(self, known, scores):
+        raise NotImplementedError
+
+    def _one(self, scores):
+        known, scores = self.to_numpy(scores, normalization=self._NORMALIZE)
+        if not (isinstance(known, DeviceVector) and isinstance(scores, DeviceVector)):
+            raise Exception("supervised measures expect backend vectors")
+        return self._value(known, scores)
+
+    def evaluate(self, scores):
+        return self.evaluate_many([scores])[0]
+
+
+class Accuracy(_ClosedForm):                                 # supervised.py:266-271
+    """1 - the mean absolute difference of the scores and the known scores."""
+
+    def _value(self, known, scores):
+        return 1 - backend.sum(backend.abs(known - scores)) / backend.length(scores)
+
+    def _from_slots(self, s, eps):
+        return 1 - _ieee_div(s[6], s[0])
+
+
+class _Rates(_ClosedForm):
+    """TPR, TNR, PPV (supervised.py:225-252): both sides are divided by their maximum (a zero maximum leaves the scalar 0, as
+    backend.safe_div does), then A = sum k s, K = sum k, S = sum s of the divided sides."""
+
+    @staticmethod
+    def _scaled(known, scores):
+        return backend.safe_div(known, backend.max(known)), backend.safe_div(scores, backend.max(scores))
+
+    @staticmethod
+    def _aks(s):
+        return backend.safe_div(s[5], s[10] * s[9]), backend.safe_div(s[3], s[10]), backend.safe_div(s[1], s[9])
+
+
+class TPR(_Rates):                                           # supervised.py:225-232
+    """True positive rate (recall)."""
+
+    def _value(self, known, scores):
+        known, scores = self._scaled(known, scores)
+        return backend.safe_div(backend.sum(known * scores), backend.sum(known))
+
+    def _from_slots(self, s, eps):
+        a, k, _ = self._aks(s)
+        return backend.safe_div(a, k)
+
+
+class TNR(_Rates):                                           # supervised.py:235-242
+    """True negative rate."""
+
+    def _value(self, known, scores):
+        known, scores = self._scaled(known, scores)
+        return backend.safe_div(backend.sum((1 - known) * (1 - scores)), backend.sum(1 - known))
+
+    def _from_slots(self, s, eps):
+        # sum (1 - k)(1 - s) = n - K - S + A over the divided sides: a difference of sums, well conditioned while the negatives
+        # are not a vanishing share of the rows
+        a, k, t = self._aks(s)
+        return backend.safe_div(s[0] - k - t + a, s[0] - k)
+
+
+class PPV(_Rates):                                           # supervised.py:245-252
+    """Positive predictive value (precision)."""
+
+    def _value(self, known, scores):
+        known, scores = self._scaled(known, scores)
+        return backend.safe_div(backend.sum(known * scores), backend.sum(scores))
+
+    def _from_slots(self, s, eps):
+        a, _, t = self._aks(s)
+        return backend.safe_div(a, t)
+
+
+class pRule(_ClosedForm):                                    # supervised.py:290-311
+    """The ratio of the mean score of the sensitive nodes (the known scores, binary) and of the others, the smaller over the larger: 1
+    is statistical parity, usually above 0.8 counts as fair."""
+
+    @staticmethod
+    def _ratio(p1, p2, sensitive, n):
+        if p1 == 0 or p2 == 0:
+            return 0
+        p1 = abs(backend.safe_div(p1, sensitive))
+        p2 = abs(backend.safe_div(p2, n - sensitive))
+        if p1 <= p2:
+            return p1 / p2
+        return p2 / p1
+
+    def _value(self, sensitive, scores):
+        return self._ratio(backend.dot(scores, sensitive), backend.dot(scores, 1 - sensitive), backend.sum(sensitive),
+                           backend.length(sensitive))
+
+    def _from_slots(self, s, eps):
+        return self._ratio(s[5], s[1] - s[5], s[3], s[0])
+
+
+class L2Disparity(_ClosedForm):                              # supervised.py:314-333
+    def __init__(self, *args, target_pRule=0.8, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.target_pRule = target_pRule
+
+    @staticmethod
+    def _gap(p1, p2, sensitive, n):
+        p1 = backend.safe_div(p1, sensitive / float(n))
+        p2 = backend.safe_div(p2, 1. - sensitive / float(n))
+        return abs(p1 - p2) ** 2
+
+    def _value(self, sensitive, scores):
+        return self._gap(backend.dot(scores, sensitive), backend.dot(scores, 1 - sensitive), backend.sum(sensitive),
+                         backend.length(sensitive))
+
+    def _from_slots(self, s, eps):
+        return self._gap(s[5], s[1] - s[5], s[3], s[0])
+
+
+class BinaryCrossEntropy(_ClosedForm):                       # supervised.py:157-166
+    _GROUP = L.PAIR_LOGS
+
+    def _value(self, known, scores):
+        eps = backend.epsilon()
+        return -backend.dot(known, backend.log(scores + eps)) - backend.dot(1 - known, backend.log(1 - scores + eps))
+
+    def _from_slots(self, s, eps):
+        return -s[12] - s[13]
+
+
+class CrossEntropy(_ClosedForm):                             # supervised.py:169-175
+    _GROUP = L.PAIR_LOGS
+
+    def _value(self, known, scores):
+        return -backend.sum(scores * backend.log(known))
+
+    def _from_slots(self, s, eps):
+        return -s[16]
+
+
+class KLDivergence(_ClosedForm):                             # supervised.py:178-190
+    """The KL divergence of the scores from the known scores, both shifted by epsilon and divided by their sums.  On the slab route,
+    with S = sum (s + eps) and K = sum (k + eps):  sum ((s + eps) / S) log(((s + eps) / S) / ((k + eps) / K))
+    = (sum (s + eps) log(s + eps) - sum (s + eps) log(k + eps)) / S - log S + log K."""
+    _GROUP = L.PAIR_LOGS
+    _NORMALIZE = True
+
+    def _value(self, known, scores):
+        eps = backend.epsilon()
+        known = known + eps
+        known = backend.safe_div(known, backend.sum(known))
+        scores = scores + eps
+        scores = backend.safe_div(scores, backend.sum(scores))
+        return backend.sum(scores * backend.log(scores / known))
+
+    @staticmethod
+    def _kl(s, eps):
+        import math
+        total_s, total_k = s[1] + eps * s[0], s[3] + eps * s[0]
+        if not (total_s > 0 and total_k > 0):
+            return float("nan")
+        return (s[14] - s[15]) / total_s - math.log(total_s) + math.log(total_k)
+
+    def _from_slots(self, s, eps):
+        return self._kl(s, eps)
+
+
+class MKLDivergence(KLDivergence):                           # supervised.py:193-205
+    """Minus the KL divergence over the number of evaluated nodes."""
+
+    def _value(self, known, scores):
+        eps = backend.epsilon()
+        known = known + eps
+        known = known / backend.sum(known)
+        scores = scores + eps
+        scores = scores / backend.sum(scores)
+        return -backend.sum(scores * backend.log(scores / known)) / backend.length(scores)
+
+    def _from_slots(self, s, eps):
+        return _ieee_div(-self._kl(s, eps), s[0])
+
+
+class PearsonCorrelation(_ClosedForm):                       # supervised.py:282-287 (scipy.stats.pearsonr in the reference)
+    """The columns route is the centred two-pass form: the means first, then dots of the centred vectors.  Constant scores or known
+    scores give nan, as scipy does."""
+
+    def _value(self, known, scores):
+        n = backend.length(scores)
+        known = known - backend.sum(known) / n
+        scores = scores - backend.sum(scores) / n
+        return _ieee_div(backend.dot(known, scores), _ieee_sqrt(backend.dot(known, known) * backend.dot(scores, scores)))
+
+    def _from_slots(self, s, eps):
+        # the one-pass form n sum ks - sum k sum s over sqrt((n sum s^2 - (sum s)^2)(n sum k^2 - (sum k)^2)): each bracket is a difference
+        # of two f64 numbers of the size of n sum s^2, so it loses digits when a column's variance is far below its squared mean (about
+        # log10(mean^2 / variance) of the 16 an f64 sum holds); the columns route's centred form does not
+        n = s[0]
+        return _ieee_div(n * s[5] - s[1] * s[3], _ieee_sqrt((n * s[2] - s[1] * s[1]) * (n * s[4] - s[3] * s[3])))
+
+
+class MannWhitneyParity(AUC):                                # supervised.py:336-350 (scipy.stats.mannwhitneyu in the reference)
+    """1 - 2 |AUC - 0.5| with the sensitive nodes (known scores != 0) as the positives: 1 when a sensitive node is as likely to score
+    above another node as below it, 0 when it always scores above or always below.  The reference's
+    mannwhitneyu(x0, x1).statistic / (n0 n1) is 1 - AUC with ties at half, and the expression is the same for AUC and 1 - AUC.
+    Raises when either class is empty, as AUC does."""
+    _SAME_CLASS = "Cannot evaluate MannWhitneyParity when all nodes are in the same class"
+
+    def _of_auc(self, auc):
+        return 1 - 2 * abs(auc - 0.5)
 
 
 class Unsupervised(Measure):
