@@ -33,5 +33,6 @@ from pygrank_amd.filters import (AbsorbingWalks, ClosedFormGraphFilter, GenericG
                                  RecursiveGraphFilter, SymmetricAbsorbingRandomWalks)
 from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector
 from pygrank_amd.autotune import ParameterTuner, SelfClearDict, Tuner, optimize
+from pygrank_amd.fairness import AdHocFairness, FairPersonalizer
 
 __version__ = "0.1.0"

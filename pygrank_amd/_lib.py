@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
-include/pgh_supervised.h).
+include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -241,6 +241,15 @@ PAIR_DECLINED = 2         # include/pgh_supervised.h PGH_PAIR_DECLINED: nothing 
 PAIR_SLOTS = 20           # include/pgh_supervised.h PGH_PAIR_SLOTS: doubles written per column
 PAIR_MOMENTS, PAIR_LOGS = 0, 1                                                      # include/pgh_supervised.h PGH_PAIR_*
 
+# name -> (restype, argtypes); every symbol include/pgh_fair.h declares.  Bound apart like the supervised measures' entry (fair_entry):
+# on a library without it FairPersonalizer builds every candidate's edited prior from backend operations.
+FAIR_SIGNATURES = {
+    "pgh_prior_edit": (C.c_int, [c_vec, c_vec, c_vec, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_mat]),
+}
+FAIR_DECLINED = 2         # include/pgh_fair.h PGH_FAIR_DECLINED: nothing was written, the caller takes the per-candidate route
+FAIR_MAX_PROBES = 64      # include/pgh_fair.h PGH_FAIR_MAX_PROBES
+FAIR_MAX_BUCKETS = 4      # include/pgh_fair.h PGH_FAIR_MAX_BUCKETS
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -290,6 +299,21 @@ def bind_measure(cdll):
 def bind_supervised(cdll):
     """Binds the include/pgh_supervised.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, SUPERVISED_SIGNATURES)
+
+
+def bind_fair(cdll):
+    """Binds the include/pgh_fair.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, FAIR_SIGNATURES)
+
+
+def fair_entry(name):
+    """The bound include/pgh_fair.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_fair_entries", None)
+    if cache is None:
+        cache = bind_fair(cdll)
+        cdll._pgh_fair_entries = cache
+    return cache[name]
 
 
 def supervised_entry(name):
