@@ -1518,6 +1518,7 @@ int pgh_dist_combine_poly(pgh_graph_t g, pgh_vec_t term, pgh_vec_t term_out, dou
     CHECK(g && term && term_out && result && xg_local && state, "pgh_dist_combine_poly: null argument");
     CHECK(term->n == g->n_cols && term_out->n == g->n_cols && result->n == g->n_cols && xg_local->n == g->n_cols,
           "pgh_dist_combine_poly: local vector length mismatch");
+    CHECK(term->data != term_out->data, "pgh_dist_combine_poly: term_out must not alias term");      // (the engine refuses it too)
     DistState* st = reinterpret_cast<DistState*>(state);
     if (st->done) return 0;
     CHECK(g->pending_xg != nullptr, "pgh_dist_combine_poly: no pgh_dist_partial before it");

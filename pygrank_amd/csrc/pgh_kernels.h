@@ -738,7 +738,7 @@ DropView bsf_dropout_view(const int32_t* edge);
 bool dist_can_fuse(const pgh_graph_s* g);
 // where a partitioned run keeps this rank's slice of the next gather vector: packed for the exchange (BsfFormat::lg_*), 0 = by row
 int dist_set_local_layout(pgh_graph_s* g, int live, int hot, int cold = -1);
-int dist_prescale_packed(pgh_graph_s* g, const float* x_local, float* xg_local_out);
+int dist_prescale_packed(pgh_graph_s* g, const float* x_local, float* xg_local_out, const LoopState* state = nullptr);
 // pgh_dist_set_send_lists with the requested slots already on the device (the engine's loop receives them there)
 int dist_set_send_lists_device(pgh_graph_s* g, const uint32_t* slots_dev, const int32_t* local_block, const int64_t* seg_offsets, int32_t segments);
 int dist_aux_init(LoopAux* aux);

@@ -1120,7 +1120,8 @@ inline void local_layout(const BsfFormat& f, EpiParams& ep) {
     ep.xg_cold = f.lg_cold >= 0 ? f.lg_cold : local_blocks * f.lg_hot;
 }
 __global__ void k_prescale_packed(const float* __restrict__ x, const float* __restrict__ scale, int64_t n, float* __restrict__ out, int blk,
-                                  int live, int hot, int cold) {
+                                  int live, int hot, int cold, const LoopState* __restrict__ state) {
+    if (state != nullptr && state->done) return;      // behind a finish stage that a stopped loop turned into a no-op: write nothing either
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int slot = xg_slot((int)i, blk, live, hot, cold);
         if (slot >= 0) out[slot] = scale != nullptr ? x[i] * scale[i] : x[i];
@@ -1137,8 +1138,9 @@ int dist_set_local_layout(pgh_graph_s* g, int live, int hot, int cold) {
     g->bsf.lg_cold = cold;
     return 0;
 }
-// out = x_local * source scale in the layout the run asked for (by row when none was set)
-int dist_prescale_packed(pgh_graph_s* g, const float* x_local, float* xg_local_out) {
+// out = x_local * source scale in the layout the run asked for (by row when none was set); state: the loop state of the step whose
+// finish stage this call follows (a no-op on the device once `done` is set), or null
+int dist_prescale_packed(pgh_graph_s* g, const float* x_local, float* xg_local_out, const LoopState* state) {
     const BsfFormat& f = g->bsf;
     const float* scale = (f.enabled && f.src_scale != nullptr) ? f.src_scale + g->row_begin : nullptr;
     const int64_t n = g->n_cols;
@@ -1147,7 +1149,7 @@ int dist_prescale_packed(pgh_graph_s* g, const float* x_local, float* xg_local_o
     local_layout(f, ep);
     int64_t blocks = (n + 255) / 256;
     const int64_t cap = (int64_t)rt().num_cus * 16;
-    k_prescale_packed<<<(int)(blocks > cap ? cap : blocks), 256, 0, rt().stream>>>(x_local, scale, n, xg_local_out, ep.xg_blk, ep.xg_live, ep.xg_hot, ep.xg_cold);
+    k_prescale_packed<<<(int)(blocks > cap ? cap : blocks), 256, 0, rt().stream>>>(x_local, scale, n, xg_local_out, ep.xg_blk, ep.xg_live, ep.xg_hot, ep.xg_cold, state);
     PGH_HIP(hipGetLastError());
     return 0;
 }
@@ -1244,10 +1246,9 @@ extern "C" int pgh_graph_set_gather_bases(pgh_graph_t g, const int64_t* bases) {
     BsfFormat& f = g->bsf;
     PGH_CHECK(f.need_idx == nullptr, "pgh_graph_set_gather_bases: this slice numbers its cold sources compactly (pgh_dist_need_counts): lay the "
                                      "gather vector out with pgh_graph_set_gather_bases_split");
-    for (int b = 0; b < f.num_blocks; ++b) {
+    for (int b = 0; b < f.num_blocks; ++b)             // every base first: a refused layout is not applied in part
         PGH_CHECK(bases[b] >= 0 && bases[b] < (1LL << 31), "pgh_graph_set_gather_bases: base out of range");
-        f.xg_base[b] = f.xg_base_cold[b] = bases[b];
-    }
+    for (int b = 0; b < f.num_blocks; ++b) f.xg_base[b] = f.xg_base_cold[b] = bases[b];
     f.lg_live = f.lg_hot = 0, f.lg_cold = -1;          // a caller that lays the gather vector out itself exchanges slices stored by row
     return 0;
 }
@@ -1260,9 +1261,10 @@ extern "C" int pgh_graph_set_gather_bases_split(pgh_graph_t g, const int64_t* ho
     // hot; the cold image's phase A: slots from hot on)
     PGH_CHECK(f.colf16 != nullptr && f.pb.enabled, "pgh_graph_set_gather_bases_split: the stream of this graph is not hot-only");
     const int64_t hot = (int64_t)PGH_BSF_HOT < f.blk_size ? (int64_t)PGH_BSF_HOT : f.blk_size;
-    for (int b = 0; b < f.num_blocks; ++b) {
+    for (int b = 0; b < f.num_blocks; ++b)             // every base first: a refused layout is not applied in part
         PGH_CHECK(hot_bases[b] >= 0 && hot_bases[b] < (1LL << 31) && cold_bases[b] >= 0 && cold_bases[b] < (1LL << 31),
                   "pgh_graph_set_gather_bases_split: base out of range");
+    for (int b = 0; b < f.num_blocks; ++b) {
         f.xg_base[b] = hot_bases[b];
         f.xg_base_cold[b] = cold_bases[b] - hot;           // slot s >= hot of the block sits at cold_bases[b] + (s - hot)
     }
@@ -1473,7 +1475,7 @@ extern "C" int pgh_dist_combine(pgh_graph_t g, pgh_vec_t p_local, double alpha, 
     // runs, and the rows of the second launch hold no exchanged slot)
     const bool second_launch = pb_pending_finish_phase() == 2;
     PGH_TRY((bsf_launch_combine<EPI_AXPBY>(g, ep, reinterpret_cast<const LoopState*>(state), &count)));
-    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, y_local->data, xg_local_out->data));
+    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, y_local->data, xg_local_out->data, reinterpret_cast<const LoopState*>(state)));
     k_dist_fold<<<1, WG, 0, r.stream>>>(state, r.d_partials, count, 0, 2);
     PGH_HIP(hipGetLastError());
     return 0;
@@ -1505,7 +1507,7 @@ extern "C" int pgh_dist_combine_absorb(pgh_graph_t g, pgh_vec_t p_local, pgh_vec
     // runs, and the rows of the second launch hold no exchanged slot)
     const bool second_launch = pb_pending_finish_phase() == 2;
     PGH_TRY((bsf_launch_combine<EPI_ABSORB>(g, ep, reinterpret_cast<const LoopState*>(state), &count)));
-    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, y_local->data, xg_local_out->data));
+    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, y_local->data, xg_local_out->data, reinterpret_cast<const LoopState*>(state)));
     k_dist_fold<<<1, WG, 0, r.stream>>>(state, r.d_partials, count, 0, 2);
     PGH_HIP(hipGetLastError());
     return 0;
@@ -1540,7 +1542,7 @@ extern "C" int pgh_dist_combine_poly(pgh_graph_t g, pgh_vec_t term_local, pgh_ve
     // runs, and the rows of the second launch hold no exchanged slot)
     const bool second_launch = pb_pending_finish_phase() == 2;
     PGH_TRY((bsf_launch_combine<EPI_POLY>(g, ep, reinterpret_cast<const LoopState*>(state), &count)));
-    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, term_out_local->data, xg_local_out->data));
+    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, term_out_local->data, xg_local_out->data, reinterpret_cast<const LoopState*>(state)));
     k_dist_fold<<<1, WG, 0, r.stream>>>(state, r.d_partials + kMaxPartials, count, err_linf ? 1 : 0, 1);
     PGH_HIP(hipGetLastError());
     return 0;
@@ -1701,7 +1703,7 @@ int dist_combine_fused(pgh_graph_s* g, const float* p_local, double alpha, float
     const int rc = bsf_launch_combine<EPI_AXPBY>(g, ep, reinterpret_cast<const LoopState*>(state), &count);
     pb_set_residual(nullptr);               // consumed by the launch; never left armed behind a failed one
     if (rc != 0) return rc;
-    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, y_local, xg_local_out));
+    if (f.src_scale == nullptr && !second_launch) PGH_TRY(dist_prescale_packed(g, y_local, xg_local_out, reinterpret_cast<const LoopState*>(state)));
     PGH_HIP(hipGetLastError());
     *num_partials = count;
     return 0;

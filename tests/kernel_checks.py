@@ -1420,4 +1420,424 @@ def check_resident_iterates_on_every_image(pg):
         refuses("PGH_FORMAT=csr", row_major)
 
 
+class DistState:
+    """The 64 bytes of a partitioned loop's state (include/pgh.h) in a 16-float DeviceVector: device memory on the engine, host
+    memory on the double.  read(): the 8 doubles; bits(): the 16 words (NaN-safe comparisons); done / steps / converged: the flags."""
+
+    def __init__(self, init=True):
+        from pygrank_amd import _lib as L
+        from pygrank_amd.device import DeviceVector
+        self.vec = DeviceVector.empty(16)
+        self.ptr = C.c_void_p(L.lib().pgh_vec_ptr(self.vec._h))
+        if init:
+            L.check(L.lib().pgh_dist_state_init(self.ptr))
+
+    def bits(self):
+        return self.vec.numpy(F32).view(np.uint32).copy()
+
+    def read(self):
+        return self.bits().view(np.float64).copy()
+
+    def flags(self):
+        ints = self.bits().view(np.int32)
+        return dict(done=int(ints[6]), steps=int(ints[7]), converged=int(ints[8]))
+
+    def write(self, doubles):
+        from pygrank_amd import _lib as L
+        raw = np.ascontiguousarray(np.asarray(doubles, dtype=np.float64)).view(F32)
+        L.check(L.lib().pgh_vec_h2d_f32(self.vec._h, raw.ctypes.data_as(C.c_void_p), 16))
+
+    def set(self, field, value):
+        d = self.read()
+        d[field] = value
+        self.write(d)
+
+    def clone(self):
+        other = DistState(init=False)
+        other.write(self.bits().view(np.float64))
+        return other
+
+
+def partition_test_graph(rng, n=3001):
+    """A directed 0/1 adjacency built by hand for the partitioned checks: ~15 % of the ids without an entry in either direction,
+    five sink-only and five source-only ids, two hub destinations (rows of M^T) of which one is a hub source too.
+    Returns (A, isolated ids)."""
+    ids = rng.permutation(n)
+    n_iso = int(0.15 * n)
+    iso, sinks, sources, live = ids[:n_iso], ids[n_iso:n_iso + 5], ids[n_iso + 5:n_iso + 10], ids[n_iso + 10:]
+    senders, receivers = np.concatenate((live, sources)), np.concatenate((live, sinks))
+    rows, cols = [], []
+    for s in senders:
+        k = int(rng.integers(1, 9))
+        rows.append(np.full(k, s))
+        cols.append(rng.choice(receivers, k, replace=False))
+    for t in sinks:                                                   # every sink is pointed at
+        rows.append(rng.choice(live, 3, replace=False))
+        cols.append(np.full(3, t))
+    for hub in live[:2]:                                              # hub rows of M^T
+        who = rng.choice(senders, len(senders) * 2 // 5, replace=False)
+        rows.append(who)
+        cols.append(np.full(len(who), hub))
+    to = rng.choice(receivers, len(receivers) // 3, replace=False)    # ... and one hub row of M
+    rows.append(np.full(len(to), live[0]))
+    cols.append(to)
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    A = sp.csr_array((np.ones(len(rows)), (rows, cols)), shape=(n, n))
+    A.sum_duplicates()
+    A.data[:] = 1.0
+    A.sort_indices()
+    touched = np.zeros(n, dtype=bool)
+    touched[rows], touched[cols] = True, True
+    assert np.array_equal(np.sort(np.flatnonzero(~touched)), np.sort(iso))
+    return A, np.sort(iso)
+
+
+def row_normalised(W):
+    """diag(1 / row sums) W: what the preprocessor's "col" normalisation hands to scipy_sparse_to_backend (x @ M is the step)."""
+    sums = np.asarray(W.sum(axis=1)).ravel()
+    inv = np.divide(1.0, sums, out=np.zeros_like(sums), where=sums != 0)
+    M = sp.csr_array(sp.diags(inv) @ W)
+    M.sort_indices()
+    return M
+
+
+def relabelled(M, perm):
+    """M in the new id space of a partition (perm: new id -> original id, -1 = padding id: an empty row and column)."""
+    n_pad = len(perm)
+    iperm = np.full(M.shape[0], -1, dtype=np.int64)
+    iperm[perm[perm >= 0]] = np.flatnonzero(perm >= 0)
+    assert np.all(iperm >= 0)
+    coo = sp.coo_array(M)
+    return sp.csc_array((coo.data, (iperm[coo.row], iperm[coo.col])), shape=(n_pad, n_pad))
+
+
+def check_partitioned_steps_against_numpy(pg):
+    """Every call of the row-partitioned step (include/pgh.h: pgh_dist_prescale / _partial / _partial_stage 0 / _combine / _combine_absorb /
+    _combine_poly / _close_sum / _residual / _close_err, pgh_graph_gather_layout / _set_gather_bases) with a per-call reference: all W
+    slices of a matrix built here (partition_scipy; W = 1, 2, 4) live in ONE process, the exchange is a numpy copy of the gather slices
+    into each slice's gather vector (stored in full, and trimmed to the referenced prefix of every block), the scalars are all-reduced in
+    Python, and every result of two consecutive iterations is held against numpy in f64 on the relabelled matrix and on the iterate the
+    engine holds -- so every bound is that of ONE step: check_fused_steps' bounds, one more EPS32 on value-free slices.  Then: once
+    `done` is set every call leaves its outputs and the state alone, and refused arguments write nothing.  The dense gather layout only
+    (what the host double implements); compact slices, split regions, stages and the isolated-row watch: tests/test_gpu_partitioned_kernels.py."""
+    from pygrank_amd import _lib as L
+    from pygrank_amd.device import DeviceVector
+    from pygrank_amd.distributed import partition_scipy, rmat_partitioned
+    lib = L.lib()
+    hip = L.runtime_name().startswith("hip:")
+    rng = np.random.default_rng(47)
+    alpha, SENTINEL = 0.85, -7.25
+
+    def f32(vec):
+        return vec.numpy(F32)
+
+    def dev(a):
+        return DeviceVector.from_host(np.ascontiguousarray(a, dtype=F32))
+
+    def signed(m):
+        return (rng.random(m) * 4 - 2).astype(F32).astype(np.float64)
+
+    def same_bits(a, b):
+        return np.array_equal(np.asarray(a, dtype=F32).view(np.uint32), np.asarray(b, dtype=F32).view(np.uint32))
+
+    A, iso = partition_test_graph(rng)
+    Wt = sp.csr_array(A.copy())
+    Wt.data = rng.uniform(0.5, 2.0, Wt.nnz)                          # weights that do not factor: the valued stream
+    R = rmat_np.rmat_csr(11, 8, seed=3)
+    cases = [("unit", row_normalised(A), iso, lambda M, r, W: partition_scipy(M, r, W)),
+             ("real", row_normalised(Wt), iso, lambda M, r, W: partition_scipy(M, r, W)),
+             # a generated partition: the slices whose stream is value-free on the engine (the gather value carries the source scale)
+             ("rmat11", sp.csr_array(orc.normalize(R, "col", True)), None, lambda M, r, W: rmat_partitioned(11, 8, r, W, seed=3))]
+    for name, M, isolated, build in cases:
+        n = M.shape[0]
+        if isolated is None:
+            touched = (np.diff(M.indptr) > 0) | (np.bincount(M.indices, minlength=n) > 0)
+            isolated = np.flatnonzero(~touched)
+        assert len(isolated) > 0, name
+        M32 = sp.csr_array(M.astype(F32).astype(np.float64))
+        for W in (1, 2, 4):
+            label = "%s/W=%d" % (name, W)
+            slices = [build(M, r, W) for r in range(W)]
+            perm = slices[0].perm.astype(np.int64)
+            n_pad, m = slices[0].n, slices[0].n_local
+            assert all(np.array_equal(s.perm, perm) and s.n == n_pad and s.n_local == m for s in slices) and m * W == n_pad, label
+            assert np.array_equal(np.sort(perm[perm >= 0]), np.arange(n)), label
+            if name != "rmat11":
+                assert n_pad > n and slices[0].n_nodes == n, (label, n, n_pad)          # padding ids exist
+            pad = perm < 0
+            formats = [s.graph.format() for s in slices]
+            value_free = ["value-free" in fmt for fmt in formats]
+            assert len(set(value_free)) == 1, (label, formats)
+            if hip and name == "rmat11":
+                assert value_free[0], (label, formats)                # the case that is here for the value-free branch below
+            # value-free slices: the gather value is x * source scale, rounded to f32 once more -- one more EPS32 of the row bound, and the
+            # matrix the engine holds is then the f64 one (integer multiplicities and two scales), not its f32 rounding
+            k_eps = 4 + (1 if value_free[0] else 0)
+            tol = lambda bound: k_eps * EPS32 * bound + 1e-30                                  # noqa: E731  (check_fused_steps' bound)
+            Mn, absMn = relabelled(M if value_free[0] else M32, perm), None
+            absMn = abs(Mn)
+            where = (label, formats)
+
+            def to_new(v):
+                out = np.zeros(n_pad)
+                out[~pad] = np.asarray(v, dtype=np.float64)[perm[~pad]]
+                return out
+
+            def to_old(v_new):
+                out = np.zeros(n)
+                out[perm[~pad]] = np.asarray(v_new)[~pad]
+                return out
+
+            cut = lambda v, r: v[r * m:(r + 1) * m]                                            # noqa: E731
+            # ---- layouts: block b at b * blk, and trimmed to the 64-rounded maximum of live[] over the slices
+            nb, blk = C.c_int32(), C.c_int64()
+            lives = np.zeros((W, 8), dtype=np.int32)
+            for r, s in enumerate(slices):
+                L.check(lib.pgh_graph_gather_layout(s.graph._h, C.byref(nb), C.byref(blk), lives[r].ctypes.data_as(C.c_void_p)))
+                assert nb.value * blk.value == n_pad and nb.value % W == 0, where
+            nb, blk = nb.value, blk.value
+            top = int((lives.max() + 63) // 64 * 64)
+            if name != "rmat11":
+                assert top < blk, (where, top, blk)                   # isolated and sink-only ids sort last: a real trim
+
+            def gather_vector(layout, xg_slices):
+                xg_all = np.concatenate(xg_slices).astype(F32)
+                if layout == "full":
+                    return np.arange(nb) * blk, dev(xg_all)
+                trimmed = np.zeros(nb * top + 32768, dtype=F32)      # (+ the hot cache's read-ahead, as check_trimmed_gather_layout)
+                for b in range(nb):
+                    trimmed[b * top:b * top + min(top, blk)] = xg_all[b * blk:b * blk + min(top, blk)]
+                return np.arange(nb) * top, dev(trimmed)
+
+            def set_bases(s, layout_bases):
+                bases = np.zeros(8, dtype=np.int64)
+                bases[:nb] = layout_bases
+                L.check(lib.pgh_graph_set_gather_bases(s.graph._h, bases.ctypes.data_as(C.c_void_p)))
+
+            def prescale(s, vec):
+                out = DeviceVector.full(m, SENTINEL)
+                L.check(lib.pgh_dist_prescale(s.graph._h, vec._h, out._h))
+                return out
+
+            def partial(s, xg_full, state, staged):
+                if staged:
+                    L.check(lib.pgh_dist_partial_stage(s.graph._h, xg_full._h, state.ptr, 0))
+                else:
+                    L.check(lib.pgh_dist_partial(s.graph._h, xg_full._h, state.ptr))
+
+            # ---- operands (original ids): signed iterate; a personalization that is zero on half of the rows, non-zero on an isolated row
+            # and on the last id in front of a block's padding
+            x0 = signed(n)
+            p = signed(n) * (rng.random(n) < 0.5)
+            p[isolated[0]] = 1.5
+            adjacent = [i for i in range(n_pad) if not pad[i] and (i + 1 == n_pad or pad[i + 1])]
+            if pad.any():
+                assert adjacent, where
+                p[perm[adjacent[0]]] = -0.75
+            assert np.any(p == 0) and p[isolated[0]] != 0
+            p_new = to_new(p)
+            deg_new, lam_new = (rng.random(n_pad) + 0.1).astype(F32).astype(np.float64), (rng.random(n_pad) + 0.1).astype(F32).astype(np.float64)
+            deg_new[rng.random(n_pad) < 0.1] = 0.0                     # rows with deg == 0 and lam > 0
+            deg_new[pad], lam_new[pad] = 0.0, 1.0                      # padding rows: (0 * 0 + 0 * 1) / (1 + 0) = 0
+            d_p = [dev(cut(p_new, r)) for r in range(W)]
+            d_deg = [dev(cut(deg_new, r)) for r in range(W)]
+            d_lam = [dev(cut(lam_new, r)) for r in range(W)]
+
+            def whole_graph(kind, x_all, s_scale, y_all):
+                """the slices' results, back in original ids, against ONE whole-graph reference (the relabelling itself is under test here)"""
+                Mo, x_old = (M if value_free[0] else M32), to_old(x_all)
+                conv, conv_abs = s_scale * (x_old @ Mo), abs(s_scale) * (np.abs(x_old) @ abs(Mo))
+                if kind == "ppr":
+                    ref, bound = (1 - alpha) * p + alpha * conv, tol((1 - alpha) * np.abs(p) + alpha * conv_abs)
+                else:
+                    dg, lm = to_old(deg_new), to_old(lam_new)
+                    ref, bound = (conv * dg + p * lm) / (lm + dg), 2 * tol((conv_abs * dg + np.abs(p) * lm) / (lm + dg))
+                err = np.abs(to_old(y_all) - ref)
+                assert np.all(err <= bound), (where, kind, "whole graph", float(np.max(err / bound)))
+                assert np.all(np.asarray(y_all)[pad] == 0), (where, kind, "padding ids")
+
+            for layout in ("full", "trimmed"):
+                # =========== pgh_dist_partial + pgh_dist_combine / _combine_absorb: two iterations with the L1 quotient in between
+                for kind in ("ppr", "absorb"):
+                    states = [DistState() for _ in range(W)]
+                    y_old = [dev(cut(to_new(x0), r)) for r in range(W)]
+                    xg = [prescale(s, y) for s, y in zip(slices, y_old)]
+                    for it in (1, 2):
+                        bases, xg_full = gather_vector(layout, [f32(v) for v in xg])
+                        x_all = np.concatenate([f32(v) for v in y_old]).astype(np.float64)        # the iterate the engine holds
+                        y_new, xg_new, sums = [], [], []
+                        for r, s in enumerate(slices):
+                            before = states[r].read()
+                            scale = before[0]
+                            assert (scale == 1.0) == (it == 1) and before[5] == 1.0, (where, it, before)     # the second step: d[0] != d[5]
+                            set_bases(s, bases)
+                            partial(s, xg_full, states[r], staged=(it == 2))
+                            y, xo = DeviceVector.full(m, SENTINEL), DeviceVector.full(m, SENTINEL)
+                            if kind == "ppr":
+                                L.check(lib.pgh_dist_combine(s.graph._h, d_p[r]._h, alpha, y._h, xo._h, states[r].ptr))
+                            else:
+                                L.check(lib.pgh_dist_combine_absorb(s.graph._h, d_p[r]._h, d_deg[r]._h, d_lam[r]._h, y._h, xo._h, states[r].ptr))
+                            got = f32(y).astype(np.float64)
+                            Mr, absMr = Mn[:, r * m:(r + 1) * m], absMn[:, r * m:(r + 1) * m]
+                            conv, conv_abs = scale * (x_all @ Mr), abs(scale) * (np.abs(x_all) @ absMr)
+                            pr = cut(p_new, r)
+                            if kind == "ppr":         # (1 - alpha) p + alpha s (x @ M): check_fused_steps' bound (k_eps: see above)
+                                ref, bound = (1 - alpha) * pr + alpha * conv, tol((1 - alpha) * np.abs(pr) + alpha * conv_abs)
+                            else:                     # ((s (x @ M)) deg + p lam) / (lam + deg): twice that bound, as check_fused_steps
+                                dg, lm = cut(deg_new, r), cut(lam_new, r)
+                                ref, bound = (conv * dg + pr * lm) / (lm + dg), 2 * tol((conv_abs * dg + np.abs(pr) * lm) / (lm + dg))
+                            err = np.abs(got - ref)
+                            assert np.all(err <= bound), (where, layout, kind, it, r, float(np.max(err / np.maximum(bound, 1e-300))))
+                            assert np.all(got[cut(pad, r)] == 0), (where, layout, kind, it, r, "padding ids")
+                            after = states[r].read()
+                            # d[2]: the f64 sum of the returned y (both engines add the rows in double), as check_fused_steps holds pgh_ppr_step's sum
+                            assert abs(after[2] - got.sum()) <= 1e-12 * max(1.0, np.abs(got).sum()), (where, layout, kind, it, r, after[2], got.sum())
+                            assert same_bits(np.delete(after, 2), np.delete(before, 2)), (where, layout, kind, it, r, before, after)
+                            assert same_bits(f32(xo), f32(prescale(s, y))), (where, layout, kind, it, r, "xg_local_out != prescale(y)")
+                            y_new.append(y)
+                            xg_new.append(xo)
+                            sums.append(after[2])
+                        y_all = np.concatenate([f32(v) for v in y_new]).astype(np.float64)
+                        whole_graph(kind, x_all, scale, y_all)
+                        # ---- the all-reduce of sum(y) is the test's; pgh_dist_close_sum turns it into the lazy quotient
+                        S = float(np.sum(sums))
+                        for r in range(W):
+                            states[r].set(2, S)
+                            before = states[r].read()
+                            for quotient, s_value, want in ((1, S, 1.0 / S if S != 0 else 0.0), (0, S, 1.0), (1, 0.0, 0.0)):
+                                probe = states[r].clone()
+                                probe.set(2, s_value)
+                                L.check(lib.pgh_dist_close_sum(probe.ptr, quotient))
+                                d = probe.read()
+                                assert d[5] == before[0] and d[0] == want and probe.flags() == dict(done=0, steps=it, converged=0), (where, it, r, quotient, d)
+                                assert d[1] == before[1] and d[2] == s_value and d[6] == before[6], (where, it, r, quotient, d)
+                            L.check(lib.pgh_dist_close_sum(states[r].ptr, 1))
+                        # ---- pgh_dist_residual, every kind: |s_new y_new - s_old y_old| summed or maxed over the slice (1e-12, as
+                        # pgh_scaled_residual is held); then the all-reduce, and the rule of pgh_dist_close_err on copies of the state
+                        for err_kind in (L.ERR_L1, L.ERR_MABS, L.ERR_LINF):
+                            shares = []
+                            for r in range(W):
+                                d = states[r].read()
+                                L.check(lib.pgh_dist_residual(err_kind, y_new[r]._h, y_old[r]._h, states[r].ptr))
+                                diff = np.abs(d[0] * f32(y_new[r]).astype(np.float64) - d[5] * f32(y_old[r]).astype(np.float64))
+                                want = float(diff.max()) if err_kind == L.ERR_LINF else float(diff.sum())
+                                after = states[r].read()
+                                assert abs(after[1] - want) <= 1e-12 * max(1.0, want), (where, layout, kind, it, r, err_kind, after[1], want)
+                                assert same_bits(np.delete(after, 1), np.delete(d, 1)), (where, it, r, err_kind)
+                                shares.append(after[1])
+                            E = float(np.max(shares)) if err_kind == L.ERR_LINF else float(np.sum(shares))
+                            e = E / n if err_kind == L.ERR_MABS else E          # Mabs: over the CALLER's node count, padding ids are no nodes
+                            assert e > 0, (where, err_kind)
+                            for r in range(W):
+                                for tolerance, stops in ((e, True), (float(np.nextafter(e, 0.0)), False), (0.0, False)):
+                                    probe = states[r].clone()
+                                    probe.set(1, E)
+                                    before = probe.read()
+                                    L.check(lib.pgh_dist_close_err(probe.ptr, err_kind, tolerance, n))
+                                    d = probe.read()
+                                    assert d[6] == e, (where, err_kind, r, d[6], e, "the rule's value")
+                                    assert probe.flags() == dict(done=int(stops), steps=it, converged=int(stops)), (where, err_kind, r, tolerance, probe.flags())
+                                    assert same_bits(d[[0, 1, 2, 5, 7]], before[[0, 1, 2, 5, 7]]), (where, err_kind, r)
+                        if it == 2:
+                            # =========== `done` is final: what a loop enqueues behind a close that stopped it -- the next step into the OTHER
+                            # iterate buffer, its close, its residual -- writes nothing
+                            bases, xg_next = gather_vector(layout, [f32(v) for v in xg_new])
+                            for r, s in enumerate(slices):
+                                stopped = states[r].clone()
+                                L.check(lib.pgh_dist_close_err(stopped.ptr, L.ERR_L1, 1e300, n))
+                                assert stopped.flags()["done"] == 1, where
+                                frozen = stopped.bits()
+                                older, held, res = f32(y_old[r]), f32(xg_new[r]), signed(m).astype(F32)
+                                yb, xb, rb = dev(older), dev(held), dev(res)
+                                set_bases(s, bases)
+                                partial(s, xg_next, stopped, staged=False)
+                                partial(s, xg_next, stopped, staged=True)
+                                L.check(lib.pgh_dist_combine(s.graph._h, d_p[r]._h, alpha, yb._h, xb._h, stopped.ptr))
+                                L.check(lib.pgh_dist_combine_absorb(s.graph._h, d_p[r]._h, d_deg[r]._h, d_lam[r]._h, yb._h, xb._h, stopped.ptr))
+                                L.check(lib.pgh_dist_combine_poly(s.graph._h, y_new[r]._h, yb._h, 2.0, -1.0, rb._h, -0.5, 0, xb._h, stopped.ptr))
+                                L.check(lib.pgh_dist_close_sum(stopped.ptr, 1))
+                                L.check(lib.pgh_dist_residual(L.ERR_L1, y_new[r]._h, yb._h, stopped.ptr))
+                                L.check(lib.pgh_dist_close_err(stopped.ptr, L.ERR_LINF, 0.0, n))
+                                assert same_bits(f32(yb), older), (where, layout, kind, r, "y written after done")
+                                assert same_bits(f32(xb), held), (where, layout, kind, r, "xg_local_out written after done")
+                                assert same_bits(f32(rb), res), (where, layout, kind, r, "result written after done")
+                                assert np.array_equal(stopped.bits(), frozen), (where, layout, kind, r, "state written after done")
+                        y_old, xg = y_new, xg_new
+
+                # =========== pgh_dist_combine_poly: term_out = a (M^T term) + b term, result += c term_out; two consecutive terms
+                for a, b, c in ((1.0, 0.0, 0.25), (2.0, -1.0, -0.5)):
+                    for linf in (0, 1):
+                        states = [DistState() for _ in range(W)]
+                        term = [dev(cut(to_new(x0), r)) for r in range(W)]
+                        result = [dev(cut(to_new(signed(n)), r)) for r in range(W)]
+                        xg = [prescale(s, t) for s, t in zip(slices, term)]
+                        for it in (1, 2):
+                            bases, xg_full = gather_vector(layout, [f32(v) for v in xg])
+                            t_all = np.concatenate([f32(v) for v in term]).astype(np.float64)
+                            term_next, xg_new = [], []
+                            for r, s in enumerate(slices):
+                                before = states[r].read()
+                                set_bases(s, bases)
+                                partial(s, xg_full, states[r], staged=(it == 2))
+                                tout, xo = DeviceVector.full(m, SENTINEL), DeviceVector.full(m, SENTINEL)
+                                res_old = f32(result[r]).astype(np.float64)
+                                L.check(lib.pgh_dist_combine_poly(s.graph._h, term[r]._h, tout._h, a, b, result[r]._h, c, linf, xo._h, states[r].ptr))
+                                got_t, got_r = f32(tout).astype(np.float64), f32(result[r]).astype(np.float64)
+                                Mr, absMr = Mn[:, r * m:(r + 1) * m], absMn[:, r * m:(r + 1) * m]
+                                t_ref = a * (t_all @ Mr) + b * cut(t_all, r)
+                                t_bound = abs(a) * (np.abs(t_all) @ absMr) + abs(b) * np.abs(cut(t_all, r))
+                                err = np.abs(got_t - t_ref)
+                                assert np.all(err <= tol(t_bound)), (where, layout, (a, b, c), it, r, float(np.max(err / np.maximum(tol(t_bound), 1e-300))))
+                                r_ref = res_old + c * got_t                    # check_fused_steps' bound of the accumulation
+                                assert np.all(np.abs(got_r - r_ref) <= 2 * EPS32 * np.abs(r_ref) + 1e-30), (where, layout, (a, b, c), it, r)
+                                assert np.all(got_t[cut(pad, r)] == 0) and np.all(got_r[cut(pad, r)] == 0), (where, layout, (a, b, c), it, r, "padding ids")
+                                after = states[r].read()
+                                change = np.abs(got_r - res_old)
+                                if linf:               # a maximum of f64 differences of f32 values: exact
+                                    assert after[1] == change.max(), (where, layout, (a, b, c), it, r, after[1], change.max())
+                                else:                  # check_fused_steps' bound of pgh_poly_step's delta
+                                    assert abs(after[1] - change.sum()) <= 1e-9 * max(1.0, np.abs(r_ref).sum()), (where, layout, (a, b, c), it, r)
+                                assert same_bits(after[[0, 5, 6, 7]], before[[0, 5, 6, 7]]) and states[r].flags() == dict(done=0, steps=it - 1, converged=0), (where, it, r)
+                                assert same_bits(f32(xo), f32(prescale(s, tout))), (where, layout, (a, b, c), it, r, "xg_local_out != prescale(term_out)")
+                                L.check(lib.pgh_dist_close_sum(states[r].ptr, 0))          # counts the step; the closed forms keep scale = 1
+                                d = states[r].read()
+                                assert d[0] == 1.0 and d[5] == 1.0 and states[r].flags()["steps"] == it, (where, it, r, d)
+                                term_next.append(tout)
+                                xg_new.append(xo)
+                            term, xg = term_next, xg_new
+
+                # =========== refusals: non-zero, outputs and state untouched
+                bases, xg_full = gather_vector(layout, [f32(v) for v in xg])
+                for r, s in enumerate(slices):
+                    state = DistState()
+                    set_bases(s, bases)
+                    partial(s, xg_full, state, staged=False)
+                    frozen = state.bits()
+                    y, xo, res = DeviceVector.full(m, SENTINEL), DeviceVector.full(m, SENTINEL), DeviceVector.full(m, SENTINEL)
+                    longer, shorter = DeviceVector.full(m + 1, SENTINEL), DeviceVector.full(m - 1, SENTINEL)
+                    g, t = s.graph._h, term[r]
+                    t_before = f32(t)
+                    refused = [lib.pgh_dist_combine(g, longer._h, alpha, y._h, xo._h, state.ptr),
+                               lib.pgh_dist_combine(g, d_p[r]._h, alpha, shorter._h, xo._h, state.ptr),
+                               lib.pgh_dist_combine(g, d_p[r]._h, alpha, y._h, longer._h, state.ptr),
+                               lib.pgh_dist_combine_absorb(g, d_p[r]._h, shorter._h, d_lam[r]._h, y._h, xo._h, state.ptr),
+                               lib.pgh_dist_combine_absorb(g, d_p[r]._h, d_deg[r]._h, longer._h, y._h, xo._h, state.ptr),
+                               lib.pgh_dist_combine_absorb(g, d_p[r]._h, d_deg[r]._h, d_lam[r]._h, longer._h, xo._h, state.ptr),
+                               lib.pgh_dist_combine_poly(g, shorter._h, y._h, 1.0, 0.0, res._h, 0.25, 0, xo._h, state.ptr),
+                               lib.pgh_dist_combine_poly(g, t._h, y._h, 1.0, 0.0, longer._h, 0.25, 0, xo._h, state.ptr),
+                               lib.pgh_dist_combine_poly(g, t._h, y._h, 1.0, 0.0, res._h, 0.25, 0, shorter._h, state.ptr),
+                               lib.pgh_dist_combine_poly(g, t._h, t._h, 2.0, -1.0, res._h, 0.25, 0, xo._h, state.ptr),          # term == term_out
+                               lib.pgh_dist_residual(L.ERR_L1, y._h, longer._h, state.ptr)]
+                    assert all(rc != 0 for rc in refused), (where, layout, r, refused)
+                    if hip:                            # a gather vector shorter than the layout (the double reads what is there)
+                        short = DeviceVector.full(max(int(bases[-1]), 1), SENTINEL)
+                        assert lib.pgh_dist_partial(g, short._h, state.ptr) != 0 and b"gather vector" in lib.pgh_last_error(), (where, layout, r)
+                        assert lib.pgh_dist_partial_stage(g, short._h, state.ptr, 0) != 0 and b"gather vector" in lib.pgh_last_error(), (where, layout, r)
+                    assert lib.pgh_dist_partial_stage(g, xg_full._h, state.ptr, 3) != 0, (where, layout, r, "stage 3")
+                    for vec in (y, xo, res, longer, shorter):
+                        assert np.all(f32(vec) == SENTINEL), (where, layout, r, "a refused call wrote")
+                    assert same_bits(f32(t), t_before) and np.array_equal(state.bits(), frozen), (where, layout, r)
+            del slices
+
+
 ALL = [v for k, v in sorted(globals().items()) if k.startswith("check_") and callable(v)]
