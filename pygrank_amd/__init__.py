@@ -32,7 +32,8 @@ from pygrank_amd.filters import (AbsorbingWalks, ClosedFormGraphFilter, GenericG
                                  ImpulseGraphFilter, LowPassRecursiveGraphFilter, PageRank, PageRankClosed,
                                  RecursiveGraphFilter, SymmetricAbsorbingRandomWalks)
 from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector
-from pygrank_amd.autotune import ParameterTuner, SelfClearDict, Tuner, optimize
+from pygrank_amd.autotune import AlgorithmSelection, ParameterTuner, SelfClearDict, Tuner, optimize
+from pygrank_amd.comparables import create_demo_filters, create_many_filters, create_variations
 from pygrank_amd.fairness import AdHocFairness, FairPersonalizer
 
 __version__ = "0.1.0"

@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
-include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h).
+include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -250,6 +250,15 @@ FAIR_DECLINED = 2         # include/pgh_fair.h PGH_FAIR_DECLINED: nothing was wr
 FAIR_MAX_PROBES = 64      # include/pgh_fair.h PGH_FAIR_MAX_PROBES
 FAIR_MAX_BUCKETS = 4      # include/pgh_fair.h PGH_FAIR_MAX_BUCKETS
 
+# name -> (restype, argtypes); every symbol include/pgh_mixed.h declares.  Bound apart like the prior-editing entry (mixed_entry): on a
+# library without them AlgorithmSelection runs every candidate filter one by one.
+MIXED_SIGNATURES = {
+    "pgh_ppr_run_batch_mixed": (C.c_int, [c_graph, c_mat, c_mat, C.POINTER(LoopCfg), C.c_void_p, C.c_void_p, C.POINTER(LoopResult)]),
+    "pgh_poly_run_batch_mixed": (C.c_int, [c_graph, c_mat, C.c_void_p, C.c_int32, c_mat, C.POINTER(LoopCfg), C.c_void_p,
+                                           C.POINTER(LoopResult)]),
+}
+MIXED_DECLINED = 2        # include/pgh_mixed.h PGH_MIXED_DECLINED: nothing was written, the caller runs the columns one by one
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -304,6 +313,21 @@ def bind_supervised(cdll):
 def bind_fair(cdll):
     """Binds the include/pgh_fair.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, FAIR_SIGNATURES)
+
+
+def bind_mixed(cdll):
+    """Binds the include/pgh_mixed.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, MIXED_SIGNATURES)
+
+
+def mixed_entry(name):
+    """The bound include/pgh_mixed.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_mixed_entries", None)
+    if cache is None:
+        cache = bind_mixed(cdll)
+        cdll._pgh_mixed_entries = cache
+    return cache[name]
 
 
 def fair_entry(name):

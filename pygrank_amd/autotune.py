@@ -1,7 +1,8 @@
-"""Parameter tuning: the coordinate descent of [krasanakis2022autogf] and the tuner built on it.
+"""Parameter tuning: the coordinate descent of [krasanakis2022autogf], the tuner built on it and the selection among ready filters.
 
-Restates pygrank/algorithms/autotune/optimization.py:9-25,64-212 (``optimize``), autotune/tuning.py:5-23 (``Tuner``) and
-autotune/parameterized.py:9-177 (``default_tuning_optimization``, ``SelfClearDict``, ``ParameterTuner``).
+Restates pygrank/algorithms/autotune/optimization.py:9-25,64-212 (``optimize``), autotune/tuning.py:5-23 (``Tuner``),
+autotune/parameterized.py:9-177 (``default_tuning_optimization``, ``SelfClearDict``, ``ParameterTuner``) and
+autotune/selection.py:10-91 (``AlgorithmSelection``).
 
 One addition to the reference.  A coordinate step of ``optimize`` scores ``partitions`` candidates that differ in ONE weight.  When
 the loss object has a callable attribute ``many`` the step hands it the whole candidate list in one call.  ``ParameterTuner`` builds
@@ -366,3 +367,189 @@ class ParameterTuner(Tuner):
                 ret[i] = desc
                 return ret
         return ret + [desc]
+
+
+def _convergence_key(ranker):
+    """What two filters must share to be columns of one device loop: the stopping rule the engine evaluates."""
+    cm = ranker.convergence
+    return (cm.device_error_kind(), float(cm.effective_tolerance()), int(cm.max_iters), int(cm.end_modulo))
+
+
+class AlgorithmSelection(Tuner):
+    """selection.py:10-91: the best of a list of rankers, found by holding part of the personalization back and scoring how well every
+    ranker recovers it from the rest.
+
+    rankers: the candidates, visited in order (default: ``create_demo_filters().values()``).  Filters that share a preprocessor share
+        the uploaded graph.
+    measure: known scores, exclude -> supervised measure (default AUC); the training part is always excluded.
+    fraction_of_training: one ``split`` argument, or an iterable of them (one split each, seeds 0, 1, ...).  A ranker's value is the
+        LEAST of ``best_direction * measure`` over the splits; the first ranker of the greatest value is selected.
+    combined_prediction: rank() applies the selected ranker to the whole personalization (default) or to the last training part.
+    tuning_backend: None or "hip" (this package drives one engine).
+    batch: True (default) runs the candidates that are plain filters as mixed batches (include/pgh_mixed.h), columns = (ranker, split)
+        pairs, 64 at a time.  Bare ``PageRank`` instances that share the preprocessor, ``use_quotient`` and the stopping rule form one
+        group (pgh_ppr_run_batch_mixed: an alpha per column); bare taylor-form ``HeatKernel`` / ``PageRankClosed`` /
+        ``GenericGraphFilter`` instances that share the preprocessor and the stopping rule form another (pgh_poly_run_batch_mixed: a
+        coefficient schedule per column).  Everything else -- a ranker inside a postprocessor, a filter that runs in f64 (``tol`` below
+        fp32 eps), AbsorbingWalks, the chebyshev form, a group of one ranker or of fewer than ``min_batch_width`` columns, a library
+        without the entries, a graph the entries decline -- is ranked exactly as ``batch=False`` ranks everything: one ``rank()`` per
+        ranker and split.  The columns of one split are scored together by the measure's ``evaluate_many`` where it has one.
+    min_batch_width: the least number of columns (rankers x splits) a group is batched at; None (default): ``MIN_BATCH_WIDTH``.
+
+    After a run ``last_selection`` holds ``rankers`` (per ranker: ``values`` per split and the ``route`` taken: "mixed_ppr",
+    "mixed_poly" or "single"), ``mixed_calls`` (per engine call: ``kind``, ``width``, the per-column ``iterations`` and the loop's
+    ``loop_ms``) and
+    ``selected`` (the index of the chosen ranker)."""
+
+    # Measured on an MI355X at RMAT scale 23 under the L1 rule (tools/select_bench.py, profiles/selection/): a selection whose groups are
+    # 4 columns wide takes 1.23 times as long batched as one by one (disjoint spreads); at 8, 12 and 16 columns 0.98, 0.96 and 0.90 (inside
+    # the spreads).  Widths 5 to 7 are not measured.
+    MIN_BATCH_WIDTH = 8
+
+    def __init__(self, rankers=None, measure=AUC, fraction_of_training=0.9, combined_prediction=True, tuning_backend=None, batch=True,
+                 min_batch_width=None):
+        if tuning_backend not in (None, "hip"):
+            raise Exception("tuning_backend is None or 'hip': this package drives one engine")
+        if rankers is None:
+            from pygrank_amd.comparables import create_demo_filters
+            rankers = create_demo_filters().values()
+        self.rankers = rankers
+        self.measure = measure
+        self.fraction_of_training = fraction_of_training
+        self.combined_prediction = combined_prediction
+        self.tuning_backend = tuning_backend
+        self.batch = batch
+        self.min_batch_width = min_batch_width
+        self.last_selection = None
+
+    # ---- the batch route -----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _group_key(ranker):
+        """(kind, what the group shares) of a ranker a mixed batch can hold, or None."""
+        from pygrank_amd.convergence import ConvergenceManager
+        from pygrank_amd.filters import GenericGraphFilter, GraphFilter, HeatKernel, PageRank, PageRankClosed
+        from pygrank_amd.postprocess import Tautology
+        if type(ranker) is PageRank:
+            if not ranker._plain_quotient():
+                return None
+            kind, extra = "mixed_ppr", (bool(ranker.use_quotient),)
+        elif type(ranker) in (HeatKernel, PageRankClosed, GenericGraphFilter):
+            if ranker.coefficient_type != "taylor" or ranker.optimization_dict is not None or ranker.krylov_dims is not None:
+                return None
+            kind, extra = "mixed_poly", ()
+        else:
+            return None
+        if type(ranker.convergence) is not ConvergenceManager or ranker._loop_cfg() is None or ranker._f64_wanted():
+            return None
+        # every member's own rank() must be the plain f32 loop on the raw personalization (the test of GraphFilter._batch_graph): a
+        # personalization transform or a graph hook of ANY member keeps that member out, not only the group's first
+        transform = ranker.personalization_transform
+        if not (isinstance(transform, Tautology) and transform.ranker is None) or type(ranker)._prepare_graph is not GraphFilter._prepare_graph:
+            return None
+        return (kind, id(ranker.preprocessor)) + extra + _convergence_key(ranker)
+
+    def _run_group(self, kind, members, rankers, splits, columns_of, calls):
+        """Ranks the (ranker, split) pairs of one group as mixed batches.  columns_of[split] gains (ranker index, ranks vector) pairs;
+        returns False (nothing gained) when the entry is missing or declines."""
+        from pygrank_amd.device import DeviceMatrix
+        entry = L.mixed_entry("pgh_ppr_run_batch_mixed" if kind == "mixed_ppr" else "pgh_poly_run_batch_mixed")
+        if entry is None:
+            return False
+        first = rankers[members[0]]
+        g = first._batch_graph(splits[0][0].graph, (), {})
+        if g is None:
+            return False
+        pairs = [(r, s) for r in members for s in range(len(splits))]
+        gained = []
+        for start in range(0, len(pairs), 64):
+            chunk = pairs[start:start + 64]
+            slab = DeviceMatrix.from_columns([splits[s][0].np for _, s in chunk])
+            norms = slab.col_abssum()
+            P = slab.div_cols(norms)                            # abstract_filters.py:52-55 per column; zero columns stay zero
+            R = DeviceMatrix.empty(slab.n, slab.b)
+            results = (L.LoopResult * slab.b)()
+            scales = (C.c_double * slab.b)(*[(float(nrm) if rankers[r].preserve_norm else 1.0) for (r, _), nrm in zip(chunk, norms)])
+            if kind == "mixed_ppr":
+                cfg = first._loop_cfg(0.0, bool(first.use_quotient), 1.0)
+                cfg.start_from_p = 1
+                alphas = (C.c_double * slab.b)(*[float(rankers[r].alpha) for r, _ in chunk])
+                status = entry(g._h, P._h, R._h, C.byref(cfg), alphas, scales, results)
+            else:
+                cfg = first._loop_cfg(0.0, False, 1.0)
+                cfg.start_from_p = 1
+                terms = max(int(first.convergence.max_iters) - 1, 0)
+                schedule = {r: rankers[r]._coefficient_schedule(terms) for r in members}
+                coeffs = np.ascontiguousarray(np.array([schedule[r] for r, _ in chunk], dtype=np.float64).T.reshape(terms, slab.b))
+                status = entry(g._h, P._h, coeffs.ctypes.data_as(C.c_void_p), terms, R._h, C.byref(cfg), scales, results)
+            if status == L.MIXED_DECLINED and not gained:
+                return False
+            L.check(status)
+            calls.append(dict(kind=kind, width=slab.b, iterations=[res.iterations for res in results], loop_ms=results[0].loop_ms))
+            for j, ((r, s), res, nrm) in enumerate(zip(chunk, results, norms)):
+                if nrm != 0:
+                    rankers[r].convergence.start()
+                    rankers[r].convergence.finish_device_loop(res.iterations, res.converged)   # raises like the ranker's own rank()
+                gained.append((s, r, R.column(j)))
+        for s, r, column in gained:
+            columns_of[s].append((r, column))
+        return True
+
+    def _batch_values(self, rankers, splits, values, routes, calls):
+        """Fills values[ranker][split] (best_direction * measure) and routes[ranker] for every ranker a mixed batch served."""
+        groups = {}
+        for index, ranker in enumerate(rankers):
+            key = self._group_key(ranker)
+            if key is not None:
+                groups.setdefault(key, []).append(index)
+        columns_of = [[] for _ in splits]
+        least = self.MIN_BATCH_WIDTH if self.min_batch_width is None else self.min_batch_width
+        for key, members in groups.items():
+            if len(members) >= 2 and len(members) * len(splits) >= least \
+                    and self._run_group(key[0], members, rankers, splits, columns_of, calls):
+                for r in members:
+                    routes[r] = key[0]
+        for s, (training, validation) in enumerate(splits):
+            if not columns_of[s]:
+                continue
+            measure = self.measure(validation, training)
+            signals = [to_signal(training, column) for _, column in columns_of[s]]
+            many = getattr(measure, "evaluate_many", None)
+            scores = many(signals) if callable(many) else [measure.evaluate(signal) for signal in signals]
+            for (r, _), score in zip(columns_of[s], scores):
+                values[r][s] = measure.best_direction() * score
+
+    def _tune(self, graph=None, personalization=None, *args, **kwargs):
+        personalization = to_signal(graph, personalization)
+        tuning_kwargs = dict(kwargs, graph_dropout=0)            # selection.py:64-65: no dropout while the candidates are compared
+        fractions = self.fraction_of_training if isinstance(self.fraction_of_training, Iterable) else [self.fraction_of_training]
+        splits = [split(personalization, fraction, seed=seed) for seed, fraction in enumerate(fractions)]
+        rankers = list(self.rankers)
+        values = [[None] * len(splits) for _ in rankers]
+        routes = ["single"] * len(rankers)
+        calls = []
+        if self.batch and not args and set(kwargs) <= {"graph_dropout"}:
+            self._batch_values(rankers, splits, values, routes, calls)
+        best_value, best_ranker, selected = -float('inf'), None, None
+        for index, ranker in enumerate(rankers):
+            for s, (training, validation) in enumerate(splits):
+                if values[index][s] is None:
+                    measure = self.measure(validation, training)
+                    values[index][s] = measure.best_direction() * measure.evaluate(ranker.rank(training, *args, **tuning_kwargs))
+            value = min(values[index])
+            if value > best_value:                               # strict: the first of equally good rankers is kept
+                best_value, best_ranker, selected = value, ranker, index
+        self.last_selection = dict(rankers=[dict(values=list(v), route=route) for v, route in zip(values, routes)],
+                                   mixed_calls=calls, selected=selected)
+        training = splits[-1][0] if splits else personalization
+        return best_ranker, personalization if self.combined_prediction else training
+
+    def references(self):
+        withheld = self.fraction_of_training
+        withheld = f"{1 - withheld:.3f}" if not isinstance(withheld, Iterable) else \
+            "/".join(f"{1 - fraction:.3f}" for fraction in withheld)
+        name = getattr(self.measure, "__name__", type(self.measure).__name__)
+        desc = "selected the best among the following algorithms \\cite{krasanakis2022autogf} that optimizes " + name \
+               + f" while withholding {withheld} of nodes for validation: \\\\\n"
+        for ranker in self.rankers:
+            desc += "  - " + ranker.cite() + " \\\\\n"
+        return [desc]

@@ -14,7 +14,9 @@
 // epilogue per column and writes the next gather slab; k_mm_residual / k_mm_close keep the per-column loop state.
 #include "pgh_kernels.h"
 #include "pgh_batch.h"
+#include "pgh_mixed.h"
 
+#include <type_traits>
 #include <vector>
 
 using namespace pgh;
@@ -566,13 +568,23 @@ struct StepParams {
     const float* zero;       // [ld] zeros: what a row without the operand reads instead (no load sits under a branch)
 };
 
+// The step of a batch whose columns are PageRanks at different alpha (pgh_ppr_run_batch_mixed): the uniform step's arguments plus one
+// alpha per column.  They travel as kernel arguments (512 bytes): a lane reads its four once, before its first row.
+struct StepParamsMixed : StepParams {
+    double col_alpha[kLanes];
+};
+template <bool MIXED> using StepArgs = typename std::conditional<MIXED, StepParamsMixed, StepParams>::type;
+__device__ __forceinline__ double mixed_alpha(const StepParams& c, int) { return c.alpha; }
+__device__ __forceinline__ double mixed_alpha(const StepParamsMixed& c, int j) { return c.col_alpha[j]; }
+
 // TRACK: the form that also writes the non-zero map.  It needs 134+ registers (three wavefronts per SIMD instead of four: 900 us instead of
 // 690 for the pass at scale 23), so it is a kernel of its own that runs only while the iterate is sparse; both forms are launched for
 // every step and the one the device-side test does not select returns at once (as the two forms of k_mm_partial do).
 // WALK: the row-affine step of the absorbing walks (pgh_absorb_run_batch / pgh_sarw_run_batch): the row word is the walk's
 // {u * dst scale, s'', 1 / s'', v} (k_mm_walk_rowops) and the personalization term is v_r * p instead of (1 - alpha) * p.
-template <bool TRACK, bool WALK = false>
-__global__ __launch_bounds__(WG) void k_mm_step(StepParams c, int64_t n, int ld, int b, const BatchState* __restrict__ state,
+// MIXED: column j takes c.col_alpha[j] instead of c.alpha (StepParamsMixed): its two factors are formed from it in the same way.
+template <bool TRACK, bool WALK = false, bool MIXED = false>
+__global__ __launch_bounds__(WG) void k_mm_step(StepArgs<MIXED> c, int64_t n, int ld, int b, const BatchState* __restrict__ state,
                                                  double* __restrict__ partials /* [4][grid][64]: S, T, R', D */) {
     __shared__ double s_red[4][WG / 64][kLanes];
     if (state->all_done | state->paused) return;
@@ -591,6 +603,15 @@ __global__ __launch_bounds__(WG) void k_mm_step(StepParams c, int64_t n, int ld,
         if (!col || state->done[c4 + k] != 0) frozen[k] = 1.f;
     }
     const float bc = (float)(1.0 - c.alpha);
+    float bcm[4] = {bc, bc, bc, bc};                       // MIXED: the lane's four columns have their own factors
+    if (MIXED) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double alpha_k = mixed_alpha(c, c4 + k < b ? c4 + k : 0);
+            a[k] = (float)(alpha_k * scl[k]);
+            bcm[k] = (float)(1.0 - alpha_k);
+        }
+    }
     double S[4] = {0.0, 0.0, 0.0, 0.0}, T[4] = {0.0, 0.0, 0.0, 0.0}, R[4] = {0.0, 0.0, 0.0, 0.0}, D[4] = {0.0, 0.0, 0.0, 0.0};
     bool neg = false;
     int nz_count = 0;
@@ -642,7 +663,7 @@ __global__ __launch_bounds__(WG) void k_mm_step(StepParams c, int64_t n, int ld,
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float yo = xo[u][k] * op[u][2];                       // the previous iterate's y (one rounding)
-                const float y = a[k] * (sum[u][k] * op[u][0]) + (WALK ? op[u][3] : bc) * pv[u][k];
+                const float y = a[k] * (sum[u][k] * op[u][0]) + (WALK ? op[u][3] : (MIXED ? bcm[k] : bc)) * pv[u][k];
                 if (frozen[k] != 0.f) {
                     out[k] = xo[u][k];                                       // a stopped column keeps its row bit for bit
                     continue;
@@ -834,7 +855,14 @@ struct CloseParams {
     int* nz_total;           // <- their sum
     int nz_parts;
 };
-__global__ void k_mm_close2(BatchState* __restrict__ state, const double* __restrict__ folded, const double* __restrict__ err_folded, CloseParams cp) {
+struct CloseParamsMixed : CloseParams {                     // pgh_ppr_run_batch_mixed: the lane's own alpha forms its prediction
+    double col_alpha[kLanes];
+};
+template <bool MIXED> using CloseArgs = typename std::conditional<MIXED, CloseParamsMixed, CloseParams>::type;
+__device__ __forceinline__ double mixed_alpha(const CloseParams& c, int) { return c.alpha; }
+__device__ __forceinline__ double mixed_alpha(const CloseParamsMixed& c, int j) { return c.col_alpha[j]; }
+template <bool MIXED = false>
+__global__ void k_mm_close2(BatchState* __restrict__ state, const double* __restrict__ folded, const double* __restrict__ err_folded, CloseArgs<MIXED> cp) {
     const int lane = threadIdx.x;
     if (state->all_done | (cp.resume ? 0 : state->paused)) return;
     const bool live = lane < state->b && !state->done[lane];
@@ -842,7 +870,8 @@ __global__ void k_mm_close2(BatchState* __restrict__ state, const double* __rest
     const double scale_new = cp.use_quotient ? (S != 0.0 ? 1.0 / S : 0.0) : 1.0;
     const double sum_p = cp.mode == 2 ? D : state->sum_p[lane];
     // with the factors as k_mm_step forms them: (float)(alpha * scale), (float)(1 - alpha)
-    const double next_raw = (double)(float)(cp.alpha * scale_new) * T + (double)(float)(1.0 - cp.alpha) * sum_p;
+    const double alpha_l = MIXED ? mixed_alpha(cp, lane) : cp.alpha;
+    const double next_raw = (double)(float)(alpha_l * scale_new) * T + (double)(float)(1.0 - alpha_l) * sum_p;
     const double raw_now = state->pred_raw[lane];
     const double ratio = (cp.mode == 1 && raw_now != 0.0) ? S / raw_now : 1.0;
     const double S_next = next_raw * ((ratio == ratio && fabs(ratio - 1.0) < 1e-4) ? ratio : 1.0);
@@ -1037,6 +1066,19 @@ __global__ __launch_bounds__(WG) void k_mm_permute_in2(PermuteIn2 q, const int32
 // deg x0 + b * sum p with the factors as k_mm_step forms them
 __global__ void k_mm_first_pred(BatchState* __restrict__ state, const double* __restrict__ t0, const double* __restrict__ sp, double alpha, int use_quotient) {
     const int lane = threadIdx.x;
+    const double raw = (double)(float)alpha * t0[lane] + (double)(float)(1.0 - alpha) * sp[lane];
+    state->sum_p[lane] = sp[lane];
+    state->pred_raw[lane] = raw;
+    state->pred_inv[lane] = use_quotient ? (raw != 0.0 ? 1.0 / raw : 0.0) : 1.0;
+}
+// ... for a batch with an alpha per column (pgh_ppr_run_batch_mixed)
+struct ColAlphas {
+    double v[kLanes];
+};
+__global__ void k_mm_first_pred_mixed(BatchState* __restrict__ state, const double* __restrict__ t0, const double* __restrict__ sp, ColAlphas alphas,
+                                      int use_quotient) {
+    const int lane = threadIdx.x;
+    const double alpha = alphas.v[lane];
     const double raw = (double)(float)alpha * t0[lane] + (double)(float)(1.0 - alpha) * sp[lane];
     state->sum_p[lane] = sp[lane];
     state->pred_raw[lane] = raw;
@@ -1340,7 +1382,8 @@ int make_drop(pgh_graph_s* g, double rate, uint64_t seed, MMDrop* out, const MMD
 }
 int spmm_impl(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y, double rate, uint64_t seed);
 int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, double rate, uint64_t seed0,
-               pgh_loop_result* results, const f32x4* walk_rowop = nullptr);
+               pgh_loop_result* results, const f32x4* walk_rowop = nullptr, const double* col_alphas = nullptr,
+               const char* who = "pgh_ppr_run_batch");
 }  // namespace
 
 extern "C" int pgh_spmm(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y) { return spmm_impl(g, x, y, 0.0, 0); }
@@ -1427,11 +1470,13 @@ int poll_ring(PollRing** out) {
 
 // walk_rowop (null for PageRank): the row words of an absorbing walk (k_mm_walk_rowops); the step is then k_mm_step<., true> with
 // a = the quotient alone, and the residual comes from the separate kernel (the in-kernel prediction is PageRank's column sums)
+// col_alphas (null for the uniform loops): [b] host, one alpha per column (pgh_ppr_run_batch_mixed): the MIXED forms of the step, its close
+// and the first prediction run instead of the uniform ones, everything else is shared
 int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, double rate, uint64_t seed0,
-               pgh_loop_result* results, const f32x4* walk_rowop) {
-    PGH_CHECK(g && p && ranks && cfg && results, "pgh_ppr_run_batch: null argument");
-    PGH_CHECK(g->n_rows == g->n_cols && p->n == g->n_cols && ranks->n == g->n_cols && p->b == ranks->b, "pgh_ppr_run_batch: shape mismatch");
-    PGH_CHECK(p->b >= 1 && p->b <= kLanes, "pgh_ppr_run_batch: the batch width must be in [1, 64]");
+               pgh_loop_result* results, const f32x4* walk_rowop, const double* col_alphas, const char* who) {
+    PGH_CHECK(g && p && ranks && cfg && results, std::string(who) + ": null argument");
+    PGH_CHECK(g->n_rows == g->n_cols && p->n == g->n_cols && ranks->n == g->n_cols && p->b == ranks->b, std::string(who) + ": shape mismatch");
+    PGH_CHECK(p->b >= 1 && p->b <= kLanes, std::string(who) + ": the batch width must be in [1, 64]");
     PGH_CHECK(cfg->end_modulo >= 1, "end_modulo must be >= 1");
     PGH_TRY(ensure_mm_layout(g));
     Runtime& r = rt();
@@ -1442,6 +1487,9 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     const bool walk = walk_rowop != nullptr;
     const f32x4* rowop = walk ? walk_rowop : reinterpret_cast<const f32x4*>(f.mm_rowop);
     const double alpha = walk ? 1.0 : cfg->alpha;                   // a walk's step: a = its quotient
+    const bool mixed = col_alphas != nullptr;
+    ColAlphas mixed_alphas{};                                       // (lanes beyond b: 0, their columns are frozen from the start)
+    for (int j = 0; mixed && j < b; ++j) mixed_alphas.v[j] = col_alphas[j];
     DevBytes pint, xg0, xg1, sums, partial, folded, state_mem, factors, row_flags, nz_maps, nz_counts, zero_row;
     PGH_TRY(zero_row.alloc(sizeof(float) * (size_t)(ld + 4)));
     PGH_HIP(hipMemsetAsync(zero_row.p, 0, sizeof(float) * (size_t)(ld + 4), r.stream));
@@ -1506,6 +1554,8 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
             double* fold0 = folded.as<double>();
             k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), in_grid, 0, state, fold0 + 5 * kLanes, 0);
             k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>() + (int64_t)in_grid * kLanes, in_grid, 0, state, fold0 + 6 * kLanes, 0);
+            if (mixed) k_mm_first_pred_mixed<<<1, kLanes, 0, r.stream>>>(state, fold0 + 5 * kLanes, fold0 + 6 * kLanes, mixed_alphas, cfg->use_quotient);
+            else
             k_mm_first_pred<<<1, kLanes, 0, r.stream>>>(state, fold0 + 5 * kLanes, fold0 + 6 * kLanes, cfg->alpha, cfg->use_quotient);
         }
         step1_predicted = first_pred;
@@ -1522,6 +1572,17 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     cp.n_orig = n;
     cp.use_quotient = cfg->use_quotient;
     cp.err_kind = cfg->err_kind;
+    // the close of a step: the uniform form, or the MIXED one with the columns' alphas behind the same arguments
+    auto launch_close = [&](const CloseParams& c2) {
+        if (mixed) {
+            CloseParamsMixed cm{};
+            static_cast<CloseParams&>(cm) = c2;
+            memcpy(cm.col_alpha, mixed_alphas.v, sizeof(cm.col_alpha));
+            k_mm_close2<true><<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, cm);
+        } else {
+            k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
+        }
+    };
     auto check_of = [&](int k) { const int it = k + 1; return (cfg->err_kind != PGH_ERR_ITERS) && (it < cfg->max_iters) && (it % cfg->end_modulo == 0); };
     // the separate residual of step k + its close (first step, max rule, dropout, a paused step)
     auto close_plain = [&](int k, int mode, int resume) -> int {
@@ -1539,7 +1600,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         c2.nz_part = sparse_gate ? nz_part : nullptr;
         c2.nz_parts = cgrid;
         c2.nz_total = nz_cnt + (k & 1);
-        k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
+        launch_close(c2);
         PGH_HIP(hipGetLastError());
         return 0;
     };
@@ -1572,7 +1633,13 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         c.zero = zero_row.as<float>();
         {
             ProfScope prof(PGH_K_COMBINE);
-            if (walk) {
+            if (mixed) {
+                StepParamsMixed cm{};
+                static_cast<StepParams&>(cm) = c;
+                memcpy(cm.col_alpha, mixed_alphas.v, sizeof(cm.col_alpha));
+                k_mm_step<false, false, true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial.as<double>());
+                if (sparse_gate) k_mm_step<true, false, true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial.as<double>());
+            } else if (walk) {
                 k_mm_step<false, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
                 if (sparse_gate) k_mm_step<true, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
             } else {
@@ -1588,7 +1655,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
             c2.nz_part = sparse_gate ? nz_part : nullptr;
             c2.nz_parts = cgrid;
             c2.nz_total = nz_cnt + (k & 1);
-            k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
+            launch_close(c2);
         } else {
             PGH_TRY(close_plain(k, mode, 0));
         }
@@ -1698,7 +1765,14 @@ __global__ __launch_bounds__(WG) void k_mm_walk_rowops(const float* __restrict__
 // the closed-form filters' first term: result_1 = c_1 * p in place over the internal personalization (rows whose p is zero become
 // zeros: every row of the result slab is written), and per workgroup the column's |result_1| (sum or max) -- the single-vector loop's
 // delta_1 = |result_1 - 0|
-__global__ __launch_bounds__(WG) void k_mm_poly_init(float* __restrict__ res, const uint8_t* __restrict__ row_flags, int64_t n, int ld, float c1,
+// C: float (one coefficient for the batch) or ColCoefs (pgh_poly_run_batch_mixed: one per column, as kernel arguments)
+struct ColCoefs {
+    float v[kLanes];
+};
+__device__ __forceinline__ float coef4(float c, int) { return c; }
+__device__ __forceinline__ f32x4 coef4(const ColCoefs& c, int c4) { return f32x4{c.v[c4], c.v[c4 + 1], c.v[c4 + 2], c.v[c4 + 3]}; }
+template <typename C = float>
+__global__ __launch_bounds__(WG) void k_mm_poly_init(float* __restrict__ res, const uint8_t* __restrict__ row_flags, int64_t n, int ld, C c1,
                                                       int linf, double* __restrict__ partial) {
     __shared__ double s_red[WG / 64][kLanes];
     const int lane = threadIdx.x & 63, wave_in_wg = threadIdx.x >> 6;
@@ -1710,7 +1784,7 @@ __global__ __launch_bounds__(WG) void k_mm_poly_init(float* __restrict__ res, co
     const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
     for (int64_t r = first; live && r < n; r += stride) {
         f32x4* at = reinterpret_cast<f32x4*>(res + r * ld + c4);
-        const f32x4 v = (row_flags[r] & 1) ? *at * c1 : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 v = (row_flags[r] & 1) ? *at * coef4(c1, live ? c4 : 0) : f32x4{0.f, 0.f, 0.f, 0.f};
         *at = v;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1770,7 +1844,14 @@ struct PolyStepParams {
     float          c;          // (float) c_k
     int            linf;
 };
-__global__ __launch_bounds__(WG) void k_mm_poly_step(PolyStepParams c, int64_t n, int ld, int b, const BatchState* __restrict__ state,
+struct PolyStepParamsMixed : PolyStepParams {               // pgh_poly_run_batch_mixed: (float) c_k of every column instead of c
+    float col_c[kLanes];
+};
+template <bool MIXED> using PolyStepArgs = typename std::conditional<MIXED, PolyStepParamsMixed, PolyStepParams>::type;
+__device__ __forceinline__ float mixed_coef(const PolyStepParams& c, int) { return c.c; }
+__device__ __forceinline__ float mixed_coef(const PolyStepParamsMixed& c, int j) { return c.col_c[j]; }
+template <bool MIXED = false>
+__global__ __launch_bounds__(WG) void k_mm_poly_step(PolyStepArgs<MIXED> c, int64_t n, int ld, int b, const BatchState* __restrict__ state,
                                                       double* __restrict__ partials) {
     __shared__ double s_red[WG / 64][kLanes];
     if (state->all_done) return;
@@ -1779,11 +1860,13 @@ __global__ __launch_bounds__(WG) void k_mm_poly_step(PolyStepParams c, int64_t n
     const int l = lane & (lpr - 1), c4 = 4 * l;
     const bool live = c4 < b;
     bool frozen[4], want[4];
+    float ck[4];                                           // the step's coefficient of the lane's four columns (MIXED: their own)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const bool col = c4 + k < b;
         frozen[k] = !col || state->done[c4 + k] != 0;
         want[k] = !frozen[k];
+        ck[k] = MIXED ? mixed_coef(c, col ? c4 + k : 0) : c.c;
     }
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + wave_in_wg) * rows_per_wave + lane / lpr;
@@ -1816,7 +1899,7 @@ __global__ __launch_bounds__(WG) void k_mm_poly_step(PolyStepParams c, int64_t n
             for (int k = 0; k < 4; ++k) {
                 const float y = sum[u][k] * ds[u];
                 xg[k] = y * sp[u];
-                rn[k] = frozen[k] ? ro[u][k] : ro[u][k] + c.c * y;
+                rn[k] = frozen[k] ? ro[u][k] : ro[u][k] + ck[k] * y;
                 const double d = frozen[k] ? 0.0 : fabs((double)rn[k] - (double)ro[u][k]);
                 acc[k] = c.linf ? fmax(acc[k], d) : acc[k] + d;
             }
@@ -1897,14 +1980,20 @@ extern "C" int pgh_sarw_run_batch(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, c
 // The Taylor form of pgh_poly_run for b columns: iteration `it` uses coeffs[it - 1] (0 beyond num_coeffs), iteration 1 is result_1 =
 // c_1 p with the check of iteration 2 on |result_1|, step k (iteration k + 1) adds c_{k+1} (M^T)^k p, the check of iteration k + 2
 // compares result_{k+1} with result_k.  Column j: iterations = 2 + its steps, as pgh_poly_run reports them.
-extern "C" int pgh_poly_run_batch(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
-                                  const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results) {
-    PGH_CHECK(results && (coeffs || num_coeffs == 0), "pgh_poly_run_batch: null argument");
-    PGH_TRY(check_batch_shapes(g, p, result, cfg, "pgh_poly_run_batch"));
+// mixed: coeffs is [num_coeffs][b], column j has its own schedule (pgh_poly_run_batch_mixed): the MIXED forms of the first term and of
+// the step run instead of the uniform ones, everything else is shared
+namespace {
+int poly_batch_impl(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result, const pgh_loop_cfg* cfg,
+                    const double* out_scales, pgh_loop_result* results, bool mixed) {
     Runtime& r = rt();
     const int b = p->b, ld = (b + 3) & ~3;
     const int64_t n = g->n_cols;
     auto coeff = [&](int it) -> double { return (it >= 1 && it <= num_coeffs) ? coeffs[it - 1] : 0.0; };
+    auto col_coeffs = [&](int it) {                         // mixed: (float) c_it of every column (lanes beyond b: 0)
+        ColCoefs cc{};
+        for (int j = 0; j < b && it >= 1 && it <= num_coeffs; ++j) cc.v[j] = (float)coeffs[(size_t)(it - 1) * b + j];
+        return cc;
+    };
     for (int j = 0; j < b; ++j) memset(&results[j], 0, sizeof(pgh_loop_result));
     if (cfg->max_iters <= 1) {            // convergence.py:86-89: stops before the first step, the sum is empty
         PGH_HIP(hipMemsetAsync(result->data, 0, sizeof(float) * (size_t)n * b, r.stream));
@@ -1961,6 +2050,9 @@ extern "C" int pgh_poly_run_batch(pgh_graph_t g, pgh_mat_t p, const double* coef
         k_mm_permute_in2<<<in_grid, WG, 0, r.stream>>>(q, f.perm, n_int, n, b, ld);
     }
     const int linf = cfg->err_kind == PGH_ERR_LINF;
+    if (mixed) k_mm_poly_init<ColCoefs><<<cgrid, WG, 0, r.stream>>>(res_slab.as<float>(), row_flags.as<uint8_t>(), n_int, ld, col_coeffs(1), linf,
+                                                                    partial.as<double>());
+    else
     k_mm_poly_init<<<cgrid, WG, 0, r.stream>>>(res_slab.as<float>(), row_flags.as<uint8_t>(), n_int, ld, (float)coeff(1), linf,
                                                partial.as<double>());
     k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, 0);
@@ -1985,10 +2077,17 @@ extern "C" int pgh_poly_run_batch(pgh_graph_t g, pgh_mat_t p, const double* coef
         c.result = res_slab.as<float>();
         c.xg_new = buf[k & 1];
         c.zero = zero_row.as<float>();
-        c.c = (float)coeff(k + 1);
+        c.c = mixed ? 0.f : (float)coeff(k + 1);
         c.linf = linf;
         {
             ProfScope prof(PGH_K_COMBINE);
+            if (mixed) {
+                PolyStepParamsMixed cm{};
+                static_cast<PolyStepParams&>(cm) = c;
+                const ColCoefs cc = col_coeffs(k + 1);
+                memcpy(cm.col_c, cc.v, sizeof(cm.col_c));
+                k_mm_poly_step<true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial.as<double>());
+            } else
             k_mm_poly_step<<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
         }
         const int it = k + 2;
@@ -2037,4 +2136,40 @@ extern "C" int pgh_poly_run_batch(pgh_graph_t g, pgh_mat_t p, const double* coef
         results[j].loop_ms = (double)ms;
     }
     return 0;
+}
+}  // namespace
+
+extern "C" int pgh_poly_run_batch(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
+                                  const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results) {
+    PGH_CHECK(results && (coeffs || num_coeffs == 0), "pgh_poly_run_batch: null argument");
+    PGH_TRY(check_batch_shapes(g, p, result, cfg, "pgh_poly_run_batch"));
+    return poly_batch_impl(g, p, coeffs, num_coeffs, result, cfg, out_scales, results, false);
+}
+
+// =================================================================================================
+// Batches whose columns are different filters (include/pgh_mixed.h): the two loops above with the parameter per column.
+// =================================================================================================
+namespace {
+// null arguments and widths outside [1, 64] are errors; a graph the multi-seed loops do not serve is declined with nothing written
+int check_mixed(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop_cfg* cfg, const void* params, pgh_loop_result* results, const char* who) {
+    PGH_CHECK(g && p && out && cfg && params && results, std::string(who) + ": null argument");
+    PGH_CHECK(p->b >= 1 && p->b <= kLanes, std::string(who) + ": the batch width must be in [1, 64]");
+    static_assert(PGH_MIXED_DECLINED == PGH_BATCH_DECLINED, "declined() reports both");
+    return check_batch_shapes(g, p, out, cfg, who);
+}
+}  // namespace
+
+extern "C" int pgh_ppr_run_batch_mixed(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* alphas,
+                                       const double* out_scales, pgh_loop_result* results) {
+    PGH_TRY(check_mixed(g, p, ranks, cfg, alphas, results, "pgh_ppr_run_batch_mixed"));
+    for (int j = 0; j < p->b; ++j) PGH_CHECK(std::isfinite(alphas[j]), "pgh_ppr_run_batch_mixed: a non-finite alpha");
+    return batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, alphas, "pgh_ppr_run_batch_mixed");
+}
+
+extern "C" int pgh_poly_run_batch_mixed(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
+                                        const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results) {
+    PGH_CHECK(num_coeffs >= 0, "pgh_poly_run_batch_mixed: a negative schedule length");
+    PGH_TRY(check_mixed(g, p, result, cfg, num_coeffs == 0 ? (const void*)cfg : (const void*)coeffs, results, "pgh_poly_run_batch_mixed"));
+    for (size_t i = 0; i < (size_t)num_coeffs * p->b; ++i) PGH_CHECK(std::isfinite(coeffs[i]), "pgh_poly_run_batch_mixed: a non-finite coefficient");
+    return poly_batch_impl(g, p, coeffs, num_coeffs, result, cfg, out_scales, results, true);
 }
