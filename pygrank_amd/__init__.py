@@ -29,7 +29,7 @@ from pygrank_amd.convergence import ConvergenceManager
 from pygrank_amd.postprocess import (LinearSweep, Normalize, Ordinals, Postprocessor, Sweep, Tautology, Threshold, Top,
                                      Transformer)
 from pygrank_amd.filters import (AbsorbingWalks, ClosedFormGraphFilter, GenericGraphFilter, GraphFilter, HeatKernel,
-                                 ImpulseGraphFilter, LowPassRecursiveGraphFilter, PageRank, PageRankClosed,
+                                 ImpulseGraphFilter, LFPR, LowPassRecursiveGraphFilter, PageRank, PageRankClosed,
                                  RecursiveGraphFilter, SymmetricAbsorbingRandomWalks)
 from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector
 from pygrank_amd.autotune import AlgorithmSelection, ParameterTuner, SelfClearDict, Tuner, optimize

@@ -1,6 +1,7 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
-include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h).
+include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h, the locally fair PageRank's entries of
+include/pgh_lfpr.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -259,6 +260,15 @@ MIXED_SIGNATURES = {
 }
 MIXED_DECLINED = 2        # include/pgh_mixed.h PGH_MIXED_DECLINED: nothing was written, the caller runs the columns one by one
 
+# name -> (restype, argtypes); every symbol include/pgh_lfpr.h declares.  Bound apart like the mixed batches (lfpr_entry): on a library
+# without them LFPR takes the reference's route, one backend primitive at a time.
+LFPR_SIGNATURES = {
+    "pgh_lfpr_setup": (C.c_int, [c_vec, c_vec, c_vec, c_vec, C.c_double, c_vec, c_vec, c_vec, c_vec, c_vec, c_f64p]),
+    "pgh_lfpr_close": (C.c_int, [c_vec, c_vec, C.c_double, c_vec, c_vec, c_vec, c_vec, c_vec, C.c_double, C.c_double, C.c_double,
+                                 C.c_int32, c_vec, c_vec, c_f64p]),
+}
+LFPR_DECLINED = 2         # include/pgh_lfpr.h PGH_LFPR_DECLINED: nothing was written, the caller takes the backend-primitive route
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -318,6 +328,21 @@ def bind_fair(cdll):
 def bind_mixed(cdll):
     """Binds the include/pgh_mixed.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, MIXED_SIGNATURES)
+
+
+def bind_lfpr(cdll):
+    """Binds the include/pgh_lfpr.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, LFPR_SIGNATURES)
+
+
+def lfpr_entry(name):
+    """The bound include/pgh_lfpr.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_lfpr_entries", None)
+    if cache is None:
+        cache = bind_lfpr(cdll)
+        cdll._pgh_lfpr_entries = cache
+    return cache[name]
 
 
 def mixed_entry(name):

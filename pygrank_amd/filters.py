@@ -513,6 +513,258 @@ class AbsorbingWalks(RecursiveGraphFilter):
         return super().propagate(graph, features, *args, **kwargs)
 
 
+class LFPR(RecursiveGraphFilter):
+    """adhoc.py:196-314: the locally fair PageRank of [tsioutsiouliklis2021fairness].  With outR = conv(sensitive, W) and
+    outB = conv(1 - sensitive, W) on the RAW adjacency W, a row scaling d and two residual vectors dR, dB (LFPR.normalization, _start) a
+    step is ``(conv(ranks, Q W) + deltaR xR + deltaB xB) alpha + personalization (1 - alpha)`` with Q = diag(d), deltaR = sum(ranks dR),
+    deltaB = sum(ranks dB); _end takes ``personalization (1 - alpha)`` off again.
+
+    The reference builds Q @ W on the host and normalises it on every rank(), because Q depends on the sensitive attribute.  Here
+    conv(x, Q W) = W^T (d x): the loop runs on the raw-adjacency device graph (normalization="none", the image Conductance uses) and
+    scales the iterate by d in front of each product, so the device graph does not depend on `sensitive`.
+
+    preprocessor: by default ``preprocessor(normalization="none", assume_immutability=False)`` as in the reference, which overwrites
+    whatever preprocessor it is given.  An extension of this backend: a caller may hand in
+    ``preprocessor=pg.preprocessor(normalization="none", assume_immutability=True)`` and reuse the device image over many rank() calls
+    with different sensitive groups.  The normalization must stay "none".  (redistributor="original" still builds its col-normalised
+    graph per rank(), as adhoc.py:270-274 does.)
+
+    fused=True (the default; an extension): per step ONE pgh_resident_step on the resident iterate, ONE pgh_lfpr_close
+    (include/pgh_lfpr.h) and, on images with a gather form, one pgh_resident_gather; two host reads.  fused=False: the reference's
+    _formula in backend primitives on the same graph.  The primitives also run where the library lacks the entries, the image has no
+    resident form, an entry declines, use_quotient is a postprocessor, converge_to_eigenvectors is set, the convergence manager is
+    not a plain ConvergenceManager with Mabs / L1 / MaxDifference / "iters", or graph_dropout / warm_start is given.  Both routes
+    share _start.  Iterates are f32 on either route: a tolerance below fp32 eps is clamped there (convergence.py:101).
+
+    Not here: f64 iterates, a batch of sensitive attributes, partitioned graphs."""
+
+    def __init__(self, alpha=0.85, redistributor=None, target_prule=1, fix_personalization=True, *args, fused=True, **kwargs):
+        self.alpha = alpha
+        if kwargs.get("preprocessor") is None:
+            kwargs["preprocessor"] = default_preprocessor(assume_immutability=False, normalization="none")
+        self.target_prule = target_prule
+        self.redistributor = redistributor
+        self.fix_personalization = fix_personalization
+        self.fused = fused
+        self._warm = False
+        super().__init__(*args, **kwargs)
+
+    def rank(self, graph=None, personalization=None, warm_start=None, graph_dropout=0, *args, **kwargs):
+        self._warm = warm_start is not None
+        try:
+            return super().rank(graph, personalization, warm_start, graph_dropout, *args, **kwargs)
+        finally:
+            self._warm = False
+
+    def _prepare_graph(self, graph, personalization, sensitive, *args, **kwargs):    # adhoc.py:243-254
+        personalization = to_signal(graph, personalization)
+        sensitive = to_signal(personalization, sensitive)
+        self.sensitive = sensitive
+        self.phi = backend.sum(sensitive.np) / backend.length(sensitive.np) * self.target_prule
+        return graph
+
+    def _original_ranks(self, personalization):                                      # adhoc.py:268-276
+        rule = self.redistributor
+        if rule is None or (isinstance(rule, str) and rule == "uniform"):
+            return None
+        if isinstance(rule, str) and rule == "original":
+            cm = self.convergence
+            inner = PageRank(alpha=self.alpha, tol=cm.tol, convergence=cm,
+                             preprocessor=default_preprocessor(assume_immutability=False, normalization="col"))(personalization).np
+            cm.last_ranks = inner            # what the inner loop's last has_converged call leaves behind in the shared manager
+            return inner
+        if isinstance(rule, NodeRanking):
+            return rule(personalization).np
+        raise Exception("LFPR redistributor: None, 'uniform', 'original' or a node ranking algorithm, not " + repr(rule))
+
+    def _start(self, M, personalization, ranks, sensitive, *args, **kwargs):         # adhoc.py:227-241, 256-282
+        s = to_signal(ranks, sensitive).np
+        phi = float(backend.sum(s) / backend.length(s) * self.target_prule)
+        out_r, out_b = backend.conv(s, M), backend.conv(1. - s, M)
+        original = self._original_ranks(personalization)
+        setup = L.lfpr_entry("pgh_lfpr_setup") if self.fused else None
+        if setup is not None and all(isinstance(v, DeviceVector) for v in (s, out_r, out_b)) \
+                and (original is None or isinstance(original, DeviceVector)):
+            made = [DeviceVector.empty(len(s)) for _ in range(5)]
+            sums = (C.c_double * 2)()
+            status = setup(s._h, out_r._h, out_b._h, None if original is None else original._h, phi, *[v._h for v in made], sums)
+            if status == 0:
+                self.d, self.dR, self.dB, self.xR, self.xB = made
+                self.sum_xR, self.sum_xB = float(sums[0]), float(sums[1])
+                return
+            if status != L.LFPR_DECLINED:
+                L.check(status)
+        case1 = out_r < (out_r + out_b) * phi
+        case2 = (1 - case1) * (out_r != 0)
+        case3 = (1 - case1) * (1 - case2)
+        inv_r, inv_b = backend.safe_inv(out_r), backend.safe_inv(out_b)
+        self.d = case1 * inv_b * (1 - phi) + case2 * inv_r * phi + case3
+        self.dR = case1 * (phi - (1 - phi) * inv_b * out_r) + case3 * phi
+        self.dB = case2 * ((1 - phi) - phi * inv_r * out_b) + case3 * (1 - phi)
+        # (xR, xB stay un-normalised with their sums beside them: deltaR * xR / sum(xR) is formed per step on either route)
+        self.xR = s * 1. if original is None else original * s
+        self.xB = 1. - s if original is None else original * (1. - s)
+        self.sum_xR, self.sum_xB = float(backend.sum(self.xR)), float(backend.sum(self.xB))
+
+    def _formula(self, M, personalization, ranks, sensitive, *args, **kwargs):       # adhoc.py:284-293
+        # (alpha is multiplied into the two coefficients and the rank-two correction is added as ONE vector: every addition of a
+        # vector rounds the seeds' large entries to f32 once more, and _end takes most of such an entry off again)
+        x = ranks.np
+        cR = self.alpha * backend.safe_div(backend.sum(x * self.dR), self.sum_xR)
+        cB = self.alpha * backend.safe_div(backend.sum(x * self.dB), self.sum_xB)
+        correction = self.xR * cR + self.xB * cB
+        return backend.conv(x * self.d, M) * self.alpha + personalization.np * (1 - self.alpha) + correction
+
+    def _end(self, M, personalization, ranks, *args, **kwargs):                      # adhoc.py:295-305
+        ranks.np = ranks.np - personalization.np * (1 - self.alpha)
+        self._forget()
+        super()._end(M, personalization, ranks, *args, **kwargs)
+
+    def _forget(self):
+        for name in ("xR", "xB", "dR", "dB", "d", "sum_xR", "sum_xB", "sensitive", "phi"):
+            if hasattr(self, name):
+                delattr(self, name)
+
+    def references(self):                                                             # adhoc.py:307-314
+        refs = super().references()
+        refs[0] = "fairness-aware PageRank \\cite{tsioutsiouliklis2021fairness}"
+        refs.insert(1, f"diffusion rate {self.alpha:.3f}")
+        redistributor = "uniform" if self.redistributor is None else self.redistributor
+        redistributor = redistributor if isinstance(redistributor, str) else redistributor.cite()
+        refs.insert(2, f"{redistributor} rank redistribution strategy")
+        return refs
+
+    def _fused_route(self, M, personalization):
+        """(device graph, pgh_lfpr_close) when this run takes the fused route, else None."""
+        close = L.lfpr_entry("pgh_lfpr_close") if self.fused and not self._warm else None
+        cm = self.convergence
+        g = _device_graph(M)
+        if close is None or g is None or g.shape[0] != g.shape[1] or g.shape[0] == 0 or not self._plain_quotient() \
+                or type(cm) is not ConvergenceManager or cm.device_error_kind() is None \
+                or not isinstance(personalization.np, DeviceVector) or len(personalization.np) != g.shape[0]:
+            return None
+        if any(getattr(type(self), hook) is not getattr(LFPR, hook) for hook in ("_formula", "_start", "_end")) \
+                or type(self)._step is not RecursiveGraphFilter._step:
+            return None
+        return (g, close) if g._resident_lengths() else None
+
+    def _primitive_loop(self, M, personalization, ranks, out_scale, args, kwargs):
+        """The rest of a run whose _start has run, in backend primitives (an entry declined)."""
+        while not self.convergence.has_converged(ranks.np):
+            self._step(M, personalization, ranks, *args, **kwargs)
+        self._end(M, personalization, ranks, *args, **kwargs)
+        if out_scale != 1.0:
+            ranks.np = ranks.np * out_scale
+        return True
+
+    def _fused_loop(self, M, personalization, ranks, out_scale, *args, **kwargs):
+        route = self._fused_route(M, personalization)
+        if route is None:
+            return False
+        g, close = route
+        self._start(M, personalization, ranks, *args, **kwargs)
+        operands = (self.d, self.dR, self.dB, self.xR, self.xB)
+        cm = self.convergence
+        self.last_loop = None
+        if not all(type(v) is DeviceVector for v in operands):          # pgh_lfpr_setup declined
+            return self._primitive_loop(M, personalization, ranks, out_scale, args, kwargs)
+        if cm.has_converged(ranks.np):
+            return self._finish_fused(M, personalization, ranks, out_scale, args, kwargs)
+        lib = L.lib()
+        n, n_int, n_gather = len(personalization.np), g._n_int, g._n_gather
+
+        def bring(vec):
+            out = DeviceVector.empty(n_int)
+            L.check(lib.pgh_resident_in(g._h, vec._h, 0.0, out._h, None))
+            return out
+        p_int, x = bring(personalization.np), bring(ranks.np)
+        d, dR, dB, xR, xB = [bring(v) for v in operands]
+        u, y = DeviceVector.empty(n_int), DeviceVector.empty(n_int)
+        ug = DeviceVector.empty(n_gather) if n_gather else None
+        # (on images with a gather form the step entry insists on writing the gather form of ITS outcome y0, which nobody reads here:
+        # the next product gathers from u = d * y, whose gather form pgh_resident_gather makes -- one wasted n_gather write per step)
+        yg = DeviceVector.empty(n_gather) if n_gather else None
+        L.check(lib.pgh_ewise_vv(L.MUL, x._h, d._h, u._h))
+        got = C.c_double()
+        L.check(lib.pgh_dot(x._h, dR._h, C.byref(got)))
+        delta_r = got.value
+        L.check(lib.pgh_dot(x._h, dB._h, C.byref(got)))
+        delta_b = got.value
+        alpha, quotient = float(self.alpha), bool(self.use_quotient)
+        kind = cm.device_error_kind()
+        counts_only = kind == L.ERR_ITERS
+        tol = float(cm.effective_tolerance())
+        sums = (C.c_double * 5)()
+        x_scale, step_sums, err, steps, converged = 1.0, [], float("nan"), 0, False
+        while True:
+            if ug is not None:
+                L.check(lib.pgh_resident_gather(g._h, u._h, ug._h))
+            L.check(lib.pgh_resident_step(g._h, 1, u._h, None if ug is None else ug._h, alpha * x_scale, p_int._h, 1.0 - alpha, None, None,
+                                          y._h, None if yg is None else yg._h, C.byref(got)))
+            cR = alpha * backend.safe_div(delta_r, self.sum_xR)
+            cB = alpha * backend.safe_div(delta_b, self.sum_xB)
+            predicted = got.value + cR * self.sum_xR + cB * self.sum_xB
+            y_scale = backend.safe_inv(predicted) if quotient else 1.0
+            status = close(y._h, x._h, x_scale, xR._h, xB._h, d._h, dR._h, dB._h, cR, cB, y_scale,
+                           L.ERR_L1 if counts_only else kind, y._h, u._h, sums)
+            if status == L.LFPR_DECLINED:
+                # the iterate before this step goes back to the caller's ids; the step is taken again there
+                out = DeviceVector.empty(n)
+                L.check(lib.pgh_resident_out(g._h, x._h, x_scale, out._h))
+                ranks.np = out
+                cm.last_ranks = out
+                self._step(M, personalization, ranks, *args, **kwargs)
+                return self._primitive_loop(M, personalization, ranks, out_scale, args, kwargs)
+            L.check(status)
+            steps += 1
+            total = sums[0]
+            scale = backend.safe_inv(total) if quotient else 1.0
+            err = sums[3] if kind == L.ERR_LINF else sums[3] + (scale - y_scale) * sums[4]
+            if kind == L.ERR_MABS:
+                err /= n
+            delta_r, delta_b = scale * sums[1], scale * sums[2]
+            step_sums.append(total)
+            x, y, x_scale = y, x, scale
+            # ConvergenceManager.has_converged (convergence.py:77-101), asked before the next step
+            cm.iteration += 1
+            cm._stamp()
+            if cm.iteration >= cm.max_iters:
+                if not counts_only and cm.iter_exception is not None:
+                    self.last_loop = dict(iterations=cm.iteration, converged=False, steps=steps, last_error=err, step_sums=step_sums)
+                    raise cm.iter_exception(cm._out_of_iterations())
+                break
+            if not counts_only and cm.iteration % cm.end_modulo == 0 and err <= tol:
+                converged = True
+                break
+        self.last_loop = dict(iterations=cm.iteration, converged=converged, steps=steps, last_error=err, step_sums=step_sums)
+        # _end in the id space: x_scale x - (1 - alpha) p = x_scale (x - (1 - alpha) / x_scale p), the bracket by one more close (f64, ONE
+        # rounding).  _end takes most of a seed's entry off again, so whatever was done to that entry before shows in what is left: the
+        # step's epilogue applied (1 - alpha) as an f32 coefficient, and the same f32 value is taken off here.  x_scale and
+        # preserve_norm ride on the way out of the id space, which runs once
+        out = DeviceVector.empty(n)
+        status = L.LFPR_DECLINED
+        if x_scale != 0.0:
+            # the close as an f64 axpy, y <- x + c p:  y0 = x,  xR = p with cR = c,  xB with cB = 0 adds nothing;  the residual operand
+            # (x again), d / dR / dB, the five sums and u are by-products nobody reads
+            c = -float(np.float32(1.0 - alpha)) / x_scale
+            status = close(x._h, x._h, 1.0, p_int._h, p_int._h, d._h, dR._h, dB._h, c, 0.0, 1.0, L.ERR_L1, y._h, u._h, sums)
+        if status == L.LFPR_DECLINED:                      # (a zero quotient, or the entry declined: _end in backend primitives)
+            L.check(lib.pgh_resident_out(g._h, x._h, x_scale, out._h))
+            ranks.np = out
+            return self._finish_fused(M, personalization, ranks, out_scale, args, kwargs)
+        L.check(status)
+        L.check(lib.pgh_resident_out(g._h, y._h, x_scale * out_scale, out._h))
+        ranks.np = out
+        self._forget()
+        return True
+
+    def _finish_fused(self, M, personalization, ranks, out_scale, args, kwargs):
+        self._end(M, personalization, ranks, *args, **kwargs)
+        if out_scale != 1.0:
+            ranks.np = ranks.np * out_scale
+        return True
+
+
 class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
     """adhoc.py:317-369: symmetric partially absorbing random walks.  With d = degrees(M) and the per-node absorption
     a = (1 + sqrt(1 + 4 d)) / 2 a step is ``conv(ranks / a, M) * d / (a + d) + personalization * a / (a + d)``
