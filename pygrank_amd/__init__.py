@@ -35,5 +35,6 @@ from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector
 from pygrank_amd.autotune import AlgorithmSelection, ParameterTuner, SelfClearDict, Tuner, optimize
 from pygrank_amd.comparables import create_demo_filters, create_many_filters, create_variations
 from pygrank_amd.fairness import AdHocFairness, FairPersonalizer
+from pygrank_amd.oversampling import BoostedSeedOversampling, SeedOversampling
 
 __version__ = "0.1.0"

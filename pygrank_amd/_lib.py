@@ -1,7 +1,7 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
 include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h, the locally fair PageRank's entries of
-include/pgh_lfpr.h).
+include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -269,6 +269,17 @@ LFPR_SIGNATURES = {
 }
 LFPR_DECLINED = 2         # include/pgh_lfpr.h PGH_LFPR_DECLINED: nothing was written, the caller takes the backend-primitive route
 
+# name -> (restype, argtypes); every symbol include/pgh_oversample.h declares.  Bound apart like LFPR's entries (oversample_entry): on a
+# library without them SeedOversampling and BoostedSeedOversampling take the backend-primitive route.
+OVERSAMPLE_SIGNATURES = {
+    "pgh_seed_floor": (C.c_int, [c_mat, c_mat, c_f64p, c_i64p]),
+    "pgh_seed_resample": (C.c_int, [c_mat, c_f64p, C.c_int32, c_mat, c_mat, c_i64p]),
+    "pgh_boost_forms": (C.c_int, [c_mat, c_mat, c_mat, c_f64p]),
+    "pgh_boost_update": (C.c_int, [c_mat, c_mat, c_f64p, c_mat, c_f64p, c_i64p]),
+}
+OVERSAMPLE_DECLINED = 2   # include/pgh_oversample.h PGH_OVERSAMPLE_DECLINED: nothing was written, the caller takes the backend-primitive route
+OVERSAMPLE_MAX_COLS = 64  # include/pgh_oversample.h PGH_OVERSAMPLE_MAX_COLS
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -333,6 +344,21 @@ def bind_mixed(cdll):
 def bind_lfpr(cdll):
     """Binds the include/pgh_lfpr.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, LFPR_SIGNATURES)
+
+
+def bind_oversample(cdll):
+    """Binds the include/pgh_oversample.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, OVERSAMPLE_SIGNATURES)
+
+
+def oversample_entry(name):
+    """The bound include/pgh_oversample.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_oversample_entries", None)
+    if cache is None:
+        cache = bind_oversample(cdll)
+        cdll._pgh_oversample_entries = cache
+    return cache[name]
 
 
 def lfpr_entry(name):

@@ -2,7 +2,8 @@
 
 The filters of one family share their preprocessor (one uploaded graph image per normalisation), which is also what lets
 ``AlgorithmSelection`` run a family's PageRanks as one mixed batch and its closed-form filters as another (include/pgh_mixed.h).
-``create_many_variation_types`` needs SeedOversampling, which this package does not have: it is left out.
+``create_variations`` takes ``{"+SO": SeedOversampling, "+BSO": BoostedSeedOversampling}`` (pygrank_amd/oversampling.py);
+``create_many_variation_types`` is not restated.
 """
 from pygrank_amd.filters import AbsorbingWalks, HeatKernel, PageRank
 from pygrank_amd.preprocessing import preprocessor as _preprocessor

@@ -5,8 +5,8 @@ the callable form of ``use_quotient`` (abstract_filters.py:131-132; the referenc
 ``Normalize``, tests/test_filters.py:41-82).  ``Ordinals`` / ``Top`` / ``Threshold`` / ``Transformer`` / ``Sweep`` /
 ``LinearSweep`` are SURVEY.md 8f-3: elementwise kernels, device reductions and one device radix sort instead of the
 reference's per-node Python dictionaries.  Behaviour follows pygrank/algorithms/postprocess/postprocess.py:7-80,106-290,
-353-450.  The fairness postprocessors are in pygrank_amd/fairness.py; the remaining ones (oversampling, subgraph extraction) re-invoke
-the hot path and stay out of scope."""
+353-450.  The fairness postprocessors are in pygrank_amd/fairness.py, the seed oversampling ones in pygrank_amd/oversampling.py;
+subgraph extraction stays out of scope."""
 from pygrank_amd import backend
 from pygrank_amd.device import DeviceVector
 from pygrank_amd.signals import NodeRanking, to_signal
