@@ -77,6 +77,7 @@ void register_warm_kernel(const void* kernel);
     }
 void build_clock_reset();
 void build_mark(const char* label);
+void build_phase_add(const char* label, double ms);      // a phase that ran after the build (images built on first use)
 
 // Stream-ordered caching allocator for vectors, slabs and loop work buffers.  hipMalloc / hipFree synchronise the
 // device and cost 100+ us each; a PageRank run allocates ~10 n-vectors.  A released block is reused by the next
@@ -357,6 +358,24 @@ struct BsfFormat {
     int64_t   device_bytes = 0;
 };
 
+// Out-edge index of a graph (pgh_push.hip): the entries of CSR(M^T) listed by SOURCE, so that the first step of a seed-set run walks
+// the seeds' out-edges instead of the whole image.  Built on the first run that can use it, freed with the graph.
+struct PushIndex {
+    int32_t*   out_ptr = nullptr;   // [n_rows + 1] caller id of a source -> its range of out_row / out_val
+    int32_t*   out_row = nullptr;   // [nnz] output row of the entry, internal ids
+    float*     out_val = nullptr;   // [nnz] the value the image multiplies with (value-free images: the multiplicity)
+    long long* acc = nullptr;       // [n_int] fixed-point row sums of a sparse step; all zero between two steps
+    int32_t*   owner = nullptr;     // [n_int] smallest item that touched the row; all INT_MAX between two steps
+    int32_t*   item_row = nullptr;  // [max_seeds + max_edges] the items of a step: row ...
+    float*     item_val = nullptr;  // ... and contribution
+    int32_t*   seed = nullptr;      // [max_seeds] the run's seeds in ascending caller id
+    int32_t*   seed_off = nullptr;  // [max_seeds + 1] prefix of their out-degrees
+    void*      ctl = nullptr;       // device words of a step (PushCtl) followed by the LoopState that gates its residual launch
+    int        max_seeds = 0, max_edges = 0;
+    bool       failed = false;      // the build ran out of memory once: not tried again
+    int64_t    device_bytes = 0;
+};
+
 struct pgh_graph_s {
     int64_t n_rows = 0;      // rows of M   (= columns of the stored M^T)
     int64_t n_cols = 0;      // columns of M (= rows of the stored M^T = length of conv output)
@@ -392,6 +411,7 @@ struct pgh_graph_s {
     int32_t* part_perm = nullptr;    // [n_rows] new id -> original id (same on every rank), or null
     int64_t  part_live_nodes = -1;   // generated partitions: ids with any edge (they sort first; -1 = unknown)
     int64_t  row_begin = 0;
+    PushIndex push;                  // out-edge index of the sparse first step (pgh_push.hip), built on first use
 };
 
 // ---------------------------------------------------------------- device helpers

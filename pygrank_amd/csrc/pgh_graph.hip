@@ -717,6 +717,7 @@ extern "C" int pgh_graph_destroy(pgh_graph_t g) {
     bsf_destroy(g->bsf);
     bsf_destroy(g->bsf_mm);
     bsf_destroy(g->bsf64);
+    push_destroy(g);
     (void)pooled_free(g->keep_mult);
     (void)pooled_free(g->src_counts);
     (void)pooled_free(g->keep_src);

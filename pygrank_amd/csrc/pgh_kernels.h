@@ -51,7 +51,7 @@ struct LoopState {
     int    done;        // convergence flag: once set every later kernel of the loop is a no-op
     int    steps;       // propagation steps executed so far
     int    converged;   // 1 when the tolerance was met
-    int    pad;
+    int    pad;         // 1: step 1 of the run went over the seeds' out-edges (pgh_push.hip), else 0
 };
 
 // Residual of a PageRank step INSIDE the finish kernel (k_pb_finish<..., RES>; L1 / Mabs rules).  The residual
@@ -555,8 +555,8 @@ __device__ __forceinline__ void publish_state(int* progress, const LoopState* st
     unsigned long long* w = reinterpret_cast<unsigned long long*>(progress) + 2;
     const unsigned long long a = (unsigned long long)__double_as_longlong(st->scale), b = (unsigned long long)__double_as_longlong(st->err),
                              c = (unsigned long long)__double_as_longlong(aux != nullptr ? aux->in_norm : 0.0),
-                             d = ((unsigned long long)(unsigned)st->steps << 32) | ((unsigned long long)(unsigned)(st->done & 0xff) << 8) |
-                                 (unsigned long long)(unsigned)(st->converged & 0xff),
+                             d = ((unsigned long long)(unsigned)st->steps << 32) | ((unsigned long long)(unsigned)(st->pad & 0xff) << 16) |
+                                 ((unsigned long long)(unsigned)(st->done & 0xff) << 8) | (unsigned long long)(unsigned)(st->converged & 0xff),
                              e = aux != nullptr ? __builtin_amdgcn_s_memrealtime() - aux->t_begin : 0ULL;
     __hip_atomic_store(w + 0, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(w + 1, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -793,5 +793,13 @@ int bsf64_walk_operands(pgh_graph_s* g, int mode, const float* p, const float* d
                         double* src_w, double* term);
 int bsf64_scale_by(pgh_graph_s* g, double* x, const double* w);
 int finish_graph(pgh_graph_s* g);
+// pgh_push.hip: the first step of a seed-set PageRank run over the seeds' out-edges
+bool push_switched_on();                     // PGH_SEED_PUSH=0 switches the feature off (nothing is built either)
+int push_ensure(pgh_graph_s* g);             // the out-edge index, built on first use (g->push.out_ptr stays null when it cannot be)
+void push_destroy(pgh_graph_s* g);
+int push_partials();                         // partial sums a pushed step leaves in every region it writes
+int push_launch_step(pgh_graph_s* g, const EpiParams& ep, const int32_t* seed_list, const int* seed_count, const float* deg, LoopState* state);
+const LoopState* push_gate(const pgh_graph_s* g);      // done == 0 only behind a pushed step: the state its residual launch is given
+int push_launch_close(pgh_graph_s* g, const PendingClose& dense, const PendingClose& pushed);
 
 }  // namespace pgh

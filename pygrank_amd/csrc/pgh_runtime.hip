@@ -186,6 +186,15 @@ void pgh::build_mark(const char* label) {
     g_build_phases.emplace_back(label, ms);
 }
 
+void pgh::build_phase_add(const char* label, double ms) {
+    for (auto& ph : g_build_phases)
+        if (ph.first == label) {
+            ph.second += ms;
+            return;
+        }
+    g_build_phases.emplace_back(label, ms);
+}
+
 extern "C" int pgh_last_build_profile(char* buf, int buflen) {
     PGH_CHECK(buf != nullptr && buflen > 0, "pgh_last_build_profile: null buffer");
     std::string out;

@@ -742,6 +742,7 @@ bool published_state(int enq, unsigned long long tag, double* loop_ms) {
                 g_state_host->steps = p_steps;
                 g_state_host->done = p_done;
                 g_state_host->converged = p_conv;
+                g_state_host->pad = (int)((dd >> 16) & 0xffu);
                 return true;
             }
         }
@@ -2004,6 +2005,18 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
     // (k_small_tail, pgh_bsf.hip) -- two launches per iteration instead of four.  PGH_SMALL_TAIL=0 keeps the general sequence.
     const bool small_tail = (MODE == EPI_AXPBY || MODE == EPI_ABSORB) && sp.blocked && !overlap && bsf_small_tail_usable(g);
     if (!state_inited) k_state_init<<<1, 1, 0, r.stream>>>(g_state, 1.0, g_aux);
+    // A PageRank run that starts from its personalization, with the seeds listed by the way in: step 1 may go over the seeds' out-edges
+    // instead of the whole image (pgh_push.hip).  Whether it does is decided on the device, from that list -- the host enqueues the
+    // pushed step AND the dense one, and one of the two returns at once.  PGH_SEED_PUSH=0: nothing of this is built or enqueued.
+    bool pushing = MODE == EPI_AXPBY && sp.blocked && pair && x0 != nullptr && state_inited && !dropping && pre_scale == nullptr && !overlap &&
+                   !small_tail && g->part_perm == nullptr && g->row_begin == 0 && g->bsf.seed_list != nullptr && max_steps >= 1 &&
+                   push_switched_on();
+    if (pushing) {
+        PGH_TRY(push_ensure(g));
+        pushing = g->push.out_ptr != nullptr;
+    }
+    const int32_t* const push_list = g->bsf.seed_list;
+    const int* const push_count = pushing ? g->bsf.seed_count + (1 - g->bsf.seed_turn) : nullptr;      // the counter this run's scan filled
     pending_close_slot().active = 0;
     int count_seen = 0;   // partials per step (the same for every step of a run)
     static unsigned long long run_counter = 0ULL;
@@ -2075,6 +2088,9 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
             fp.first_pred = 1;
             pending_close_slot() = fp;
         }
+        const bool push_now = pushing && k == 1;
+        // (in front of the dense launches: a run that qualifies is held, and they pass as they do behind a converged step)
+        if (push_now) PGH_TRY(push_launch_step(g, epk, push_list, push_count, fused ? g->bsf.deg_int : nullptr, g_state));
         const int rc_step = launch_step<MODE>(g, epk, use_xg ? g->bsf.xg : xin, g_state, &count, (overlap && k > 1) ? g_ev_closed : nullptr);
         if (fused) pb_set_residual(nullptr);     // consumed by the finish launch; never left armed behind a step that failed before it
         PGH_TRY(rc_step);
@@ -2097,7 +2113,21 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
             k_step_residual<<<rgrid, WG, 0, r.stream>>>(yout, xin, n_int, vec_ok, cfg->use_quotient, linf, g_state,
                                                         r.d_partials, count, pres, iso_tail);
         }
-        if (defer) {
+        if (push_now) {
+            // residual and close of a pushed step 1: the path of a step whose residual is not fused -- the separate kernel (it runs only
+            // behind a pushed step: its state is the gate), then the close that also makes step 2's prediction (res_mode 2).  One
+            // launch closes either form of the step, so nothing is deferred into step 2.
+            PendingClose pushed = pc;
+            pushed.res_mode = fused ? 2 : 0;
+            pushed.num_sum = push_partials();
+            if (pushed.check) {
+                ProfScope prof(PGH_K_RESIDUAL);
+                k_step_residual<<<rgrid, WG, 0, r.stream>>>(yout, xin, n_int, aligned16(yout) && aligned16(xin), cfg->use_quotient, linf,
+                                                            push_gate(g), r.d_partials, push_partials(), pres, iso_tail);
+            }
+            ProfScope prof(PGH_K_FINAL);
+            PGH_TRY(push_launch_close(g, pc, pushed));
+        } else if (defer) {
             pending_close_slot() = pc;
         } else {
             ProfScope prof(PGH_K_FINAL);
@@ -2175,6 +2205,10 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
         if (!(poll && published_state(enq, run_tag, &published_ms))) PGH_TRY(fetch_state());
     }
     const int steps = g_state_host->steps;
+    // bit 3: step 1 went over the seeds' out-edges.  Bits 0-2 stay what the run's dense form reports (tests/test_gpu_fullsize.py holds a
+    // seed-set run at scale 23 to "fused from the first step on, never paused"): nothing paused, the in-kernel residual is the rule of
+    // every dense step -- with bit 3 set, step 1 is not one of them and its residual came from the separate kernel
+    if (pushing && g_state_host->pad == 1) res->flags |= 8;
     // result lives in buf[steps & 1]; apply the pending quotient and preserve_norm factor
     const double norm_used = norm_on_device ? g_aux_host->in_norm : host_norm;
     if (norm_wanted) res->in_norm = norm_used;
