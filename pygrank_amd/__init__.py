@@ -22,9 +22,10 @@ from pygrank_amd.signals import GraphSignal, NodeRanking, to_signal
 from pygrank_amd.preprocessing import (Adjacency, AdjacencyWrapper, MethodHasher, obj2id, preprocessor,
                                        to_sparse_matrix)
 from pygrank_amd.utils import call, ensure_used_args, remove_used_args
-from pygrank_amd.measures import (AUC, L1, L2, MSQ, MSQRT, Accuracy, BinaryCrossEntropy, Conductance, Cos, CrossEntropy, Density, Dot,
-                                  Euclidean, KLDivergence, L2Disparity, Mabs, MannWhitneyParity, MaxDifference, MKLDivergence,
-                                  PearsonCorrelation, PPV, RMabs, Supervised, TNR, TPR, Unsupervised, pRule, split)
+from pygrank_amd.measures import (AM, AUC, GM, L1, L2, MSQ, MSQRT, NDCG, Accuracy, BinaryCrossEntropy, Conductance, Cos, CrossEntropy,
+                                  Density, Disparity, Dot, Euclidean, KLDivergence, L2Disparity, Mabs, MannWhitneyParity,
+                                  MaxDifference, MeasureCombination, MKLDivergence, Parity, PearsonCorrelation, PPV, RMabs,
+                                  SpearmanCorrelation, Supervised, TNR, TPR, Unsupervised, pRule, split)
 from pygrank_amd.convergence import ConvergenceManager
 from pygrank_amd.postprocess import (LinearSweep, Normalize, Ordinals, Postprocessor, Sweep, Tautology, Threshold, Top,
                                      Transformer)

@@ -1,7 +1,7 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
 include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h, the locally fair PageRank's entries of
-include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h).
+include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h, the rank-based measures' entries of include/pgh_rank.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -280,6 +280,23 @@ OVERSAMPLE_SIGNATURES = {
 OVERSAMPLE_DECLINED = 2   # include/pgh_oversample.h PGH_OVERSAMPLE_DECLINED: nothing was written, the caller takes the backend-primitive route
 OVERSAMPLE_MAX_COLS = 64  # include/pgh_oversample.h PGH_OVERSAMPLE_MAX_COLS
 
+# name -> (restype, argtypes); every symbol include/pgh_rank.h declares.  Bound apart like the oversampling passes (rank_entry): on a
+# library without them NDCG and SpearmanCorrelation take the columns route.
+c_rank_plan = C.c_void_p
+RANK_SIGNATURES = {
+    "pgh_rank_plan_create": (C.c_int, [c_vec, c_vec, C.POINTER(c_rank_plan)]),
+    "pgh_rank_plan_info": (C.c_int, [c_rank_plan, c_i64p, c_i64p, c_i32p]),
+    "pgh_rank_plan_destroy": (C.c_int, [c_rank_plan]),
+    "pgh_ndcg": (C.c_int, [c_mat, c_rank_plan, C.c_int64, C.c_int32, c_f64p, c_f64p]),
+    "pgh_spearman": (C.c_int, [c_mat, c_rank_plan, c_f64p]),
+    "pgh_ndcg_vec": (C.c_int, [c_vec, c_rank_plan, C.c_int64, C.c_int32, c_f64p, c_f64p]),
+    "pgh_spearman_vec": (C.c_int, [c_vec, c_rank_plan, c_f64p]),
+}
+RANK_DECLINED = 2         # include/pgh_rank.h PGH_RANK_DECLINED: nothing was written, the caller takes the columns route
+RANK_MAX_RELEVANT = 8192  # include/pgh_rank.h PGH_RANK_MAX_RELEVANT
+RANK_LDS_BYTES = 61440    # include/pgh_rank.h PGH_RANK_LDS_BYTES
+RANK_AUTO, RANK_STREAMING, RANK_SORTED = 0, 1, 2                                    # include/pgh_rank.h PGH_RANK_*
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -349,6 +366,21 @@ def bind_lfpr(cdll):
 def bind_oversample(cdll):
     """Binds the include/pgh_oversample.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, OVERSAMPLE_SIGNATURES)
+
+
+def bind_rank(cdll):
+    """Binds the include/pgh_rank.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, RANK_SIGNATURES)
+
+
+def rank_entry(name):
+    """The bound include/pgh_rank.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_rank_entries", None)
+    if cache is None:
+        cache = bind_rank(cdll)
+        cdll._pgh_rank_entries = cache
+    return cache[name]
 
 
 def oversample_entry(name):

@@ -13,7 +13,10 @@ sort-based ones are functions of a handful of per-column sums over (score, known
 for 64 columns while it reads each row of the slab once (include/pgh_supervised.h: pgh_pair_forms).  On a
 library without that entry -- the host test double -- the same classes take the reference's route one backend primitive at a time.
 AUC and MannWhitneyParity score a slab through the tuner's pgh_probe_auc (include/pgh_tune.h) with an identity coefficient matrix.
-NDCG, SpearmanCorrelation (a segmented sort per column), Mistreatment and measures/combination.py stay out of scope.
+NDCG (supervised.py:68-90) and SpearmanCorrelation (:274-279) score a slab through include/pgh_rank.h: the DCG
+of 64 columns in one streaming pass, Spearman's rho with one device sort per column, both through a plan shared by every call.  The
+combinations of measures/combination.py (AM, GM, Disparity, Parity) live in pygrank_amd/combination.py and are re-exported here.
+Mistreatment and measures/multigroup.py stay out of scope.
 
 The unsupervised measures Conductance and Density (pygrank/measures/unsupervised.py:8-145) score a ranking without ground truth.  They are
 the reference's only measures that run `conv` themselves: two passes over the adjacency per score column.  Here the columns of a batch
@@ -348,6 +351,7 @@ class AUC(_Pairwise):                                        # supervised.py:255
     are scored by pgh_probe_auc (include/pgh_tune.h) with an identity coefficient matrix (terms = probes = columns): the entry then
     returns the AUC of each stored column, the value pgh_auc returns for it."""
     _SAME_CLASS = "Cannot evaluate AUC when all labels are the same"
+    _MANY_IS_EXACT = True         # evaluate_many equals a loop over evaluate to the bit (pair counts are integers): see combination.py
 
     def _auc(self, scores):
         known, scores = self._pair(scores)
@@ -613,6 +617,176 @@ class MannWhitneyParity(AUC):                                # supervised.py:336
         return 1 - 2 * abs(auc - 0.5)
 
 
+class _RankPlan:
+    """What the columns of every NDCG / SpearmanCorrelation call share on the device (pgh_rank_plan_create, include/pgh_rank.h)."""
+
+    def __init__(self, known, exclude):
+        self._h = L.c_rank_plan()
+        L.check(L.rank_entry("pgh_rank_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
+        kept, relevant, negative = C.c_int64(), C.c_int64(), C.c_int32()
+        L.check(L.rank_entry("pgh_rank_plan_info")(self._h, C.byref(kept), C.byref(relevant), C.byref(negative)))
+        self.num_kept, self.num_relevant, self.has_negative = kept.value, relevant.value, bool(negative.value)
+
+    def __del__(self):
+        try:
+            if self._h is not None and L._lib is not None:
+                L.rank_entry("pgh_rank_plan_destroy")(self._h)
+        except Exception:
+            pass
+        self._h = None
+
+
+class _Ranked(_Pairwise):
+    """NDCG and SpearmanCorrelation: measures of a column's ORDER.  With the entries of include/pgh_rank.h ``evaluate`` scores a vector
+    as the b = 1 case on its own storage and ``evaluate_many`` scores a slab 64 columns at a time, both through one plan per (known
+    scores, exclude) pair: the plan is kept on the measure while ``known_scores`` and ``exclude`` are the same objects (and the graph
+    and the number of rows are the same).  On a library without the entries -- or when the entry declines, or with known scores or
+    exclude values per column -- every column takes ``_columns_value``: backend primitives over the filtered vectors."""
+    _ENTRIES = ()
+    _plan_cache = None
+    _MANY_IS_EXACT = True         # evaluate is the one-column case of the same entry, whose per-column result does not depend on the width
+
+    def _slab_available(self):
+        return all(L.rank_entry(name) is not None for name in ("pgh_rank_plan_create", "pgh_rank_plan_info", "pgh_rank_plan_destroy")
+                   + self._ENTRIES)
+
+    def _plan_for(self, anchor, rows):
+        graph = None if anchor is None else anchor.graph
+        cached = self._plan_cache
+        if cached is not None and cached[0] is self.known_scores and cached[1] is self.exclude and cached[2] is graph and cached[3] == rows:
+            return cached[4]
+        known, _ = self._operand(anchor, self.known_scores, rows, "known scores")
+        exclude, _ = self._operand(anchor, self.exclude, rows, "exclude values")
+        plan = _RankPlan(known, exclude)
+        self._plan_cache = (self.known_scores, self.exclude, graph, rows, plan)
+        return plan
+
+    def _of_entry(self, handle, plan, width, vector):
+        """The values of `width` columns behind `handle` (a slab, or with `vector` a vector's own storage); None when declined."""
+        raise NotImplementedError
+
+    def _columns_value(self, known, scores):
+        raise NotImplementedError
+
+    def _slab(self, anchor, columns, count):
+        if isinstance(self.known_scores, DeviceMatrix) or isinstance(self.exclude, DeviceMatrix):
+            return None                                      # known scores per column: one plan per column, no shared pass
+        matrix = self._matrix(anchor, columns)
+        plan = self._plan_for(anchor, matrix.n)
+        out = []
+        for first in range(0, matrix.b, 64):
+            width = min(64, matrix.b - first)
+            part = matrix if matrix.b <= 64 else matrix.get_cols(first, width)
+            values = self._of_entry(part._h, plan, width, False)
+            if values is None:
+                return None
+            out.extend(values)
+        return out
+
+    def evaluate(self, scores):
+        if _FORCE_PER_COLUMN or not self._slab_available() or isinstance(self.known_scores, DeviceMatrix) \
+                or isinstance(self.exclude, DeviceMatrix):
+            return self._columns_value(*self._pair(scores))
+        known = self.known_scores
+        if all(isinstance(value, numbers.Number) for value in (scores, known)):
+            anchor, vector = None, backend.to_array([scores])
+        else:
+            anchor = next((value for value in (scores, known) if isinstance(value, GraphSignal)), None)
+            if anchor is None and self.exclude is not None:
+                raise Exception("Needs to parse graph signal scores or known_scores to be able to exclude specific nodes")
+            vector = self._dense(anchor, scores)
+        vector._h                           # noqa: B018 -- an unevaluated expression (device.LazyVector) is evaluated first
+        values = self._of_entry(vector._h, self._plan_for(anchor, len(vector)), 1, True)
+        if values is None:
+            return self._columns_value(*self._pair(scores))
+        return values[0]
+
+
+class NDCG(_Ranked):                                         # supervised.py:68-90
+    """NDCG@k of the scores against the known scores: the known scores of the first k nodes in descending order of score (ties in node
+    order, as Python's stable sort leaves them), each divided by log2(position + 1), over the same sum in descending order of the
+    known scores.  k is the number of known scores when None, is not reduced by the exclusion, and a k above that number raises.
+    The quotient is the reference's: nan for 0 / 0 (no relevant node among the evaluated ones), and ZeroDivisionError when no node is
+    evaluated at all (both sums are then Python's integer 0).
+
+    With include/pgh_rank.h the DCG of up to 64 columns is one streaming pass over the slab.  The columns route
+    is filter_out, DeviceVector.ordinals() and one masked sum in f32."""
+    _ENTRIES = ("pgh_ndcg", "pgh_ndcg_vec")
+
+    def __init__(self, known_scores, exclude=None, k=None):
+        super().__init__(known_scores, exclude=exclude)
+        if k is not None and k > len(known_scores):
+            raise Exception("NDCG@k cannot be computed for k greater than the number of known scores")
+        self.k = len(known_scores) if k is None else k
+
+    def best_direction(self):
+        return 1
+
+    @staticmethod
+    def _quotient(dcg, idcg, evaluated, k):
+        if evaluated == 0 or k < 1:
+            raise ZeroDivisionError("division by zero")      # the reference divides the integer 0 by the integer 0 here
+        return _ieee_div(dcg, idcg)
+
+    def _of_entry(self, handle, plan, width, vector):
+        k = int(self.k)
+        if plan.num_kept == 0 or k < 1:
+            self._quotient(0, 0, 0, k)
+        dcg, idcg = (C.c_double * width)(), C.c_double()
+        status = L.rank_entry("pgh_ndcg_vec" if vector else "pgh_ndcg")(handle, plan._h, k, L.RANK_AUTO, dcg, C.byref(idcg))
+        if status == L.RANK_DECLINED:
+            return None
+        L.check(status)
+        return [self._quotient(float(v), idcg.value, plan.num_kept, k) for v in dcg]
+
+    def _columns_value(self, known, scores):
+        import math
+        k = int(self.k)
+
+        def gain(order_of):
+            ordinals = order_of.ordinals()
+            return backend.sum(known * (ordinals <= k) / (backend.log(ordinals + 1) / math.log(2)))
+        if len(scores) == 0 or k < 1:
+            self._quotient(0, 0, 0, k)
+        return self._quotient(gain(scores), gain(known), len(scores), k)
+
+
+class SpearmanCorrelation(_Ranked):                          # supervised.py:274-279 (scipy.stats.spearmanr in the reference)
+    """Spearman's rho of the scores and the known scores over the evaluated nodes: Pearson's correlation of their mid-ranks, in the
+    centred form (sum of products of 2 rank - (n + 1), exact integers).  Constant scores or known scores give nan, as scipy does.
+
+    With include/pgh_rank.h a column costs one device radix sort.  The columns route is the fallback of a
+    library WITHOUT that entry: the two filtered vectors are downloaded and ranked on the host with numpy."""
+    _ENTRIES = ("pgh_spearman", "pgh_spearman_vec")
+
+    def best_direction(self):
+        return 1
+
+    def _of_entry(self, handle, plan, width, vector):
+        rho = (C.c_double * width)()
+        status = L.rank_entry("pgh_spearman_vec" if vector else "pgh_spearman")(handle, plan._h, rho)
+        if status == L.RANK_DECLINED:
+            return None
+        L.check(status)
+        return [float(v) for v in rho]
+
+    @staticmethod
+    def _centred_ranks(values):
+        """2 midrank - (n + 1) of every entry, exact integers held in f64."""
+        import numpy as np
+        _, inverse, counts = np.unique(values, return_inverse=True, return_counts=True)
+        upto = np.cumsum(counts)
+        return ((2 * upto - counts)[inverse.reshape(-1)] - len(values)).astype(np.float64)
+
+    def _columns_value(self, known, scores):
+        import numpy as np
+        known, scores = np.asarray(known, dtype=np.float64), np.asarray(scores, dtype=np.float64)
+        if np.isnan(scores).any() or np.isnan(known).any():
+            return float("nan")
+        dk, ds = self._centred_ranks(known), self._centred_ranks(scores)
+        return _ieee_div(float(np.dot(ds, dk)), _ieee_sqrt(float(np.dot(ds, ds)) * float(np.dot(dk, dk))))
+
+
 class Unsupervised(Measure):
     """unsupervised.py:8-49: a measure of the scores and the graph alone.  `graph` may be left out when graph signals are evaluated;
     without a preprocessor the graph is taken unnormalised (normalization="none") unless a normalization is named."""
@@ -840,3 +1014,6 @@ def split(groups, training_samples=0.8, seed=0):
     if values is None:
         return group[:cut], group[cut:]
     return tuple(to_signal(groups, {node: float(values[groups.node2id[node]]) for node in side}) for side in (group[:cut], group[cut:]))
+
+
+from pygrank_amd.combination import AM, GM, Disparity, MeasureCombination, Parity  # noqa: E402,F401 -- re-exported; it imports Measure from here
