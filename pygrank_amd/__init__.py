@@ -32,6 +32,7 @@ from pygrank_amd.postprocess import (LinearSweep, Normalize, Ordinals, Postproce
 from pygrank_amd.filters import (AbsorbingWalks, ClosedFormGraphFilter, GenericGraphFilter, GraphFilter, HeatKernel,
                                  ImpulseGraphFilter, LFPR, LowPassRecursiveGraphFilter, PageRank, PageRankClosed,
                                  RecursiveGraphFilter, SymmetricAbsorbingRandomWalks)
+from pygrank_amd.krylov import arnoldi_iteration, krylov2original, krylov_base, krylov_error_bound
 from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector
 from pygrank_amd.autotune import AlgorithmSelection, ParameterTuner, SelfClearDict, Tuner, optimize
 from pygrank_amd.comparables import create_demo_filters, create_many_filters, create_variations

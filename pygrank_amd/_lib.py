@@ -1,7 +1,8 @@
 """ctypes binding of the C-ABI declared in include/pgh.h (and the multi-seed loops of include/pgh_batch.h, the tuner's entries of
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
 include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h, the locally fair PageRank's entries of
-include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h, the rank-based measures' entries of include/pgh_rank.h).
+include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h, the rank-based measures' entries of include/pgh_rank.h,
+the Krylov-space filters' entries of include/pgh_krylov.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -297,6 +298,16 @@ RANK_MAX_RELEVANT = 8192  # include/pgh_rank.h PGH_RANK_MAX_RELEVANT
 RANK_LDS_BYTES = 61440    # include/pgh_rank.h PGH_RANK_LDS_BYTES
 RANK_AUTO, RANK_STREAMING, RANK_SORTED = 0, 1, 2                                    # include/pgh_rank.h PGH_RANK_*
 
+# name -> (restype, argtypes); every symbol include/pgh_krylov.h declares.  Bound apart like LFPR's entries (krylov_entry): on a library
+# without them the Krylov-space filters take the reference's route, one backend primitive at a time.
+KRYLOV_SIGNATURES = {
+    "pgh_lanczos_close": (C.c_int, [c_vec, c_vec, C.c_double, c_vec, C.c_double, c_vec, c_mat, C.c_int32, c_f64p]),
+    "pgh_krylov_residuals": (C.c_int, [c_mat, c_f64p, C.c_int32, C.c_int32, c_f64p, c_f64p]),
+}
+KRYLOV_DECLINED = 2       # include/pgh_krylov.h PGH_KRYLOV_DECLINED: nothing was written, the caller takes the backend-primitive route
+KRYLOV_MAX_DIMS = 64      # include/pgh_krylov.h PGH_KRYLOV_MAX_DIMS
+KRYLOV_MAX_PROBES = 64    # include/pgh_krylov.h PGH_KRYLOV_MAX_PROBES
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -371,6 +382,21 @@ def bind_oversample(cdll):
 def bind_rank(cdll):
     """Binds the include/pgh_rank.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, RANK_SIGNATURES)
+
+
+def bind_krylov(cdll):
+    """Binds the include/pgh_krylov.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, KRYLOV_SIGNATURES)
+
+
+def krylov_entry(name):
+    """The bound include/pgh_krylov.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_krylov_entries", None)
+    if cache is None:
+        cache = bind_krylov(cdll)
+        cdll._pgh_krylov_entries = cache
+    return cache[name]
 
 
 def rank_entry(name):

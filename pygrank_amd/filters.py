@@ -945,25 +945,64 @@ class _PowerSlab:
 
 
 class ClosedFormGraphFilter(GraphFilter):
-    """abstract_filters.py:152-270: sum_k c_k (M^T)^k p with Taylor or the reference's "chebyshev" recurrence."""
+    """abstract_filters.py:152-270: sum_k c_k (M^T)^k p with Taylor or the reference's "chebyshev" recurrence.
 
-    def __init__(self, krylov_dims=None, coefficient_type="taylor", optimization_dict=None, *args, **kwargs):
+    krylov_dims=k: the filter is evaluated in the k-dimensional Krylov space of the personalization (pygrank_amd/krylov.py; DESIGN.md
+    section 17): k products build the Lanczos basis V [n, k] and the k x k matrix H, the expansion then runs on k x k host matrices and
+    the ranks are V @ result[:, 0].  As in the reference the outcome is an APPROXIMATION of the filter on the L2-normalised
+    personalization, and a basis whose estimated relative error exceeds 0.01 raises.
+    fused=True (the default; an extension): the basis comes from the engine's Lanczos step (include/pgh_krylov.h) and, under a plain
+    ConvergenceManager with Mabs / L1 / MaxDifference, the residuals of up to 64 iterations come from ONE pgh_krylov_residuals pass
+    over the basis and the ranks from ONE pgh_mat_gemv (_krylov_loop).  fused=False, and a library without the entries: the same
+    recurrence and the same loop in backend primitives (one gemv and two reductions per iteration).  Any other convergence manager,
+    overridden hooks, extra arguments, graph_dropout and a warm start step one iteration at a time through the hooks (one gemv and one
+    has_converged each)."""
+
+    def __init__(self, krylov_dims=None, coefficient_type="taylor", optimization_dict=None, *args, fused=True, **kwargs):
         super().__init__(*args, **kwargs)
-        if krylov_dims is not None:
-            raise NotImplementedError("the Krylov-space approximation (krylov_space.py) is outside the propagation "
-                                      "hot path of this build (SURVEY.md 2 row 16)")
-        self.krylov_dims = None
+        self.krylov_dims = krylov_dims
         self.coefficient_type = coefficient_type.lower()
         self.optimization_dict = optimization_dict
+        self.fused = fused
         self._active_dict = None
 
     _FORMS = ("taylor", "chebyshev")
 
+    def _krylov_basis(self, M, personalization):
+        """(basis, products it cost this run) for krylov_dims, with the error bound checked (abstract_filters.py:207-210).  With an
+        optimisation dict the basis, H and the bound are kept in the active dict, keyed by krylov_dims, while the graph object stays the
+        same (as _PowerSlab checks): a second run on the same personalization costs no product."""
+        from pygrank_amd import krylov
+        k = int(self.krylov_dims)
+        g = _device_graph(M)
+        store = self._active_dict.setdefault("krylov", {}) if self._active_dict is not None else None
+        kept = store.get(k) if store is not None else None
+        if kept is not None and g is not None and kept["graph"] is g:
+            basis, bound, spmv = kept["basis"], kept["bound"], 0
+        else:
+            basis = krylov.lanczos(M, personalization.np, k, fused=self.fused)
+            bound, spmv = basis.error_bound(), basis.spmv
+            if store is not None:
+                store[k] = dict(graph=g, basis=basis, bound=bound, powers={})
+        self._krylov_powers = store[k]["powers"] if store is not None else None
+        if bound > krylov.TOO_ROUGH:
+            raise Exception("Krylov approximation with estimated relative error " + str(bound)
+                            + " > 0.01 is too rough to be meaningful (try on lager graphs)")
+        return basis, spmv
+
     def _start(self, M, personalization, ranks, *args, **kwargs):
-        """abstract_filters.py:196-213: the sum starts empty, the running term is the personalization itself."""
-        self.coefficient, self.ranks_power = None, personalization.np
+        """abstract_filters.py:196-213: the sum starts empty, the running term is the personalization itself (in the Krylov space:
+        the k x k identity; the ranks keep their start value until the first step, as in the reference)."""
+        self.coefficient = None
         if self.coefficient_type == "chebyshev":
             self.prev_term = 0
+        if self.krylov_dims is not None:
+            self.krylov_base, self._krylov_spmv = self._krylov_basis(M, personalization)
+            self.krylov_H = self.krylov_base.H
+            self.krylov_result = self.krylov_H * 0
+            self.Mpower = np.eye(int(self.krylov_dims))
+            return
+        self.ranks_power = personalization.np
         ranks.np = backend.repeat(0.0, backend.length(ranks.np))
 
     def _recursion(self, result, next_term, next_coefficient):
@@ -988,6 +1027,8 @@ class ClosedFormGraphFilter(GraphFilter):
         refs = super().references()
         if self.coefficient_type == "chebyshev":
             refs.append("Chebyshev recurrence of the terms")
+        if self.krylov_dims is not None:                                          # abstract_filters.py:190-191, as written
+            refs.append("Lanczos acceleration \\cite{susnjara2015accelerated} in the" + str(self.krylov_dims) + "-dimensional Krylov space")
         if self.optimization_dict is not None:
             refs.append("stored powers of the personalization (optimization dictionary)")
         return refs
@@ -1002,6 +1043,14 @@ class ClosedFormGraphFilter(GraphFilter):
             self._active_dict = None
 
     def _retrieve_power(self, ranks_power, M):                                    # abstract_filters.py:241-246
+        if self.krylov_dims is not None:
+            # the k x k powers of H, kept per iteration beside the basis they belong to (the reference keys them by the iteration alone)
+            powers = getattr(self, "_krylov_powers", None)
+            if powers is None:
+                return ranks_power @ M
+            if self.convergence.iteration not in powers:
+                powers[self.convergence.iteration] = ranks_power @ M
+            return powers[self.convergence.iteration]
         if self._active_dict is not None:
             if self.convergence.iteration not in self._active_dict:
                 self._active_dict[self.convergence.iteration] = backend.conv(ranks_power, M)
@@ -1011,15 +1060,30 @@ class ClosedFormGraphFilter(GraphFilter):
     def _step(self, M, personalization, ranks, *args, **kwargs):
         """abstract_filters.py:248-256: draw the next coefficient, add the running term with it, propagate the term once more."""
         weight = self.coefficient = self._coefficient(self.coefficient)
+        if self.krylov_dims is not None:
+            self.krylov_result, term = self._recursion(self.krylov_result, self.Mpower, weight)
+            ranks.np = self.krylov_base.project(self.krylov_result[:, 0])
+            self.Mpower = self._retrieve_power(term, self.krylov_H)
+            return
         total, term = self._recursion(ranks.np, self.ranks_power, weight)
         ranks.np = total
         self.ranks_power = self._retrieve_power(term, M)
 
+    _KRYLOV_PER_RUN = ("krylov_base", "krylov_H", "krylov_result", "Mpower", "_krylov_spmv", "_krylov_powers")
+
     def _end(self, M, personalization, ranks, *args, **kwargs):
         """abstract_filters.py:258-267: the per-run attributes of the expansion go away."""
-        per_run = ["ranks_power", "coefficient"] + (["prev_term"] if self.coefficient_type == "chebyshev" else [])
+        if self.krylov_dims is not None:
+            cm = self.convergence
+            self.last_loop = dict(iterations=cm.iteration, converged=cm.iteration < cm.max_iters, spmv=self._krylov_spmv,
+                                  last_error=float("nan"), dims=int(self.krylov_dims), residual_passes=0)
+            per_run = list(self._KRYLOV_PER_RUN)
+        else:
+            per_run = ["ranks_power"]
+        per_run += ["coefficient"] + (["prev_term"] if self.coefficient_type == "chebyshev" else [])
         for name in per_run:
-            delattr(self, name)
+            if hasattr(self, name):
+                delattr(self, name)
         self._active_dict = None
 
     def _coefficient(self, previous_coefficient):
@@ -1124,6 +1188,9 @@ class ClosedFormGraphFilter(GraphFilter):
             raise Exception("rank_many evaluates stored powers: construct the filter with optimization_dict={}")
         if len(variants) < 1 or len(variants) > 64:
             raise Exception("rank_many takes 1 to 64 variants")
+        if self.krylov_dims is not None or any(getattr(v, "krylov_dims", None) is not None for v in variants):
+            raise Exception("rank_many evaluates stored powers of the personalization: filters with krylov_dims have none "
+                            "(rank them one by one)")
         personalization = to_signal(graph, personalization)
         self._prepare(personalization)
         personalization = self.personalization_transform(personalization)
@@ -1157,6 +1224,8 @@ class ClosedFormGraphFilter(GraphFilter):
         return slab, C_, iterations
 
     def _fused_loop(self, M, personalization, ranks, out_scale, *args, **kwargs):
+        if self.krylov_dims is not None:
+            return self._krylov_loop(M, personalization, ranks, out_scale, args, kwargs)
         if args or kwargs or type(self)._step is not ClosedFormGraphFilter._step \
                 or type(self)._recursion is not ClosedFormGraphFilter._recursion:
             return False
@@ -1187,6 +1256,75 @@ class ClosedFormGraphFilter(GraphFilter):
         self.convergence.finish_device_loop(res.iterations, res.converged)
         return True
 
+    def _krylov_forget(self):
+        per_run = self._KRYLOV_PER_RUN + ("coefficient", "prev_term")
+        for name in per_run:
+            if hasattr(self, name):
+                delattr(self, name)
+        self._active_dict = None
+
+    def _krylov_loop(self, M, personalization, ranks, out_scale, args, kwargs):
+        """The loop of a run with krylov_dims under a plain ConvergenceManager with Mabs / L1 / MaxDifference (DESIGN.md section 17);
+        False where the hooks must run it one iteration at a time with has_converged.
+        The k x k recursion runs on the host with the filter's own _coefficient and _recursion.  The change of iteration t is V d_t with
+        d_t = (result_t - result_{t-1})[:, 0], so its residual sum_i |V d_t| or max_i |V d_t| is taken from d_t directly and not from
+        two rounded f32 iterates: it resolves tolerances below fp32 eps, and the tolerance is clamped at fp64 eps as on the f64 routes
+        (_f64_cfg), not at fp32 eps.  fused: the recursion runs AHEAD, up to 64 iterations at a time, and ONE pgh_krylov_residuals pass
+        over the basis gives all their residuals; otherwise (fused=False, a library without the entry, a declined pass) every iteration
+        costs one pgh_mat_gemv and two reductions.  ConvergenceManager's rule (convergence.py:77-101: the call before step t + 1
+        compares the outcome of step t with the one before it, on multiples of end_modulo, and gives up at max_iters) then picks the
+        stopping iteration exactly as _expansion does, a second chunk follows if the first does not stop, and the ranks are ONE
+        pgh_mat_gemv.  As in the reference the first comparison is against the ranks' start value, the L1-normalised personalization
+        -- in the Krylov space |p|_2 e_0."""
+        own, cm, k = ClosedFormGraphFilter, self.convergence, int(self.krylov_dims)
+        hooks = ("_start", "_step", "_end", "_recursion", "_retrieve_power")
+        if args or kwargs or any(getattr(type(self), hook) is not getattr(own, hook) for hook in hooks) \
+                or type(cm) is not ConvergenceManager or cm.device_error_kind() not in (L.ERR_MABS, L.ERR_L1, L.ERR_LINF) \
+                or self.coefficient_type not in self._FORMS \
+                or getattr(self, "_raw_input", None) is None:          # (a warm start: the first comparison is against another vector)
+            return False
+        kind, n = cm.device_error_kind(), max(len(personalization.np), 1)
+        tol = 0.0 if cm.tol is None else max(float(cm.tol), float(np.finfo(np.float64).eps))
+        try:
+            self._start(M, personalization, ranks)
+            basis = self.krylov_base
+            ahead = L.KRYLOV_MAX_PROBES if basis.residual_entry(self.fused) is not None else 1
+            before = np.zeros(k)
+            before[0] = basis.p_norm
+            done, passes, err, converged, it, stop_at = 0, 0, float("nan"), False, 1, None
+            while stop_at is None:
+                steps = range(done + 1, min(done + ahead, int(cm.max_iters) - 1) + 1)
+                cols = []
+                for s in steps:
+                    cm.iteration = s                        # _coefficient and _recursion read convergence.iteration
+                    weight = self.coefficient = self._coefficient(self.coefficient)
+                    self.krylov_result, term = self._recursion(self.krylov_result, self.Mpower, weight)
+                    self.Mpower = self._retrieve_power(term, self.krylov_H)
+                    cols.append(np.array(np.asarray(self.krylov_result)[:, 0], dtype=np.float64))
+                if not cols:                                # max_iters <= 1: the first has_converged call ends the run
+                    it = done + 1
+                    break
+                deltas = np.stack([now - was for now, was in zip(cols, [before] + cols[:-1])], axis=1)
+                sums, tops, fused_pass = basis.residuals(deltas, self.fused)
+                passes += fused_pass
+                errors = tops if kind == L.ERR_LINF else (sums / n if kind == L.ERR_MABS else sums)
+                for index, s in enumerate(steps):
+                    it, err = s + 1, float(errors[index])   # the has_converged call that follows step s
+                    if it >= cm.max_iters or (it % cm.end_modulo == 0 and err <= tol):
+                        converged, stop_at = it < cm.max_iters, cols[index]
+                        break
+                done, before = steps[-1], cols[-1]
+            if stop_at is not None:
+                ranks.np = basis.project(stop_at, out_scale)
+            elif out_scale != 1.0:
+                ranks.np = ranks.np * out_scale
+            self.last_loop = dict(iterations=it, converged=converged, spmv=self._krylov_spmv, last_error=err, dims=k,
+                                  residual_passes=passes)
+        finally:
+            self._krylov_forget()
+        cm.finish_device_loop(it, converged)
+        return True
+
     def propagate(self, graph, features, *args, **kwargs):
         """signals.py:225-226 (one rank() per feature column) as multi-seed batches of up to 64 columns through pgh_poly_run_batch
         (include/pgh_batch.h) wherever a single rank() would run the f32 taylor loop of pgh_poly_run: the adjacency is streamed once
@@ -1194,7 +1332,7 @@ class ClosedFormGraphFilter(GraphFilter):
         an optimisation dict, overridden hooks, f64 iterates ...)."""
         own = ClosedFormGraphFilter
         g = None
-        if self.coefficient_type == "taylor" and self.optimization_dict is None and type(self)._step is own._step \
+        if self.coefficient_type == "taylor" and self.optimization_dict is None and self.krylov_dims is None and type(self)._step is own._step \
                 and type(self)._recursion is own._recursion and type(self)._start is own._start \
                 and type(self)._retrieve_power is own._retrieve_power and type(self)._prepare is own._prepare:
             g = self._batch_graph(graph, args, kwargs)
