@@ -24,7 +24,7 @@ from pygrank_amd.preprocessing import (Adjacency, AdjacencyWrapper, MethodHasher
 from pygrank_amd.utils import call, ensure_used_args, remove_used_args
 from pygrank_amd.measures import (AM, AUC, GM, L1, L2, MSQ, MSQRT, NDCG, Accuracy, BinaryCrossEntropy, Conductance, Cos, CrossEntropy,
                                   Density, Disparity, Dot, Euclidean, KLDivergence, L2Disparity, Mabs, MannWhitneyParity,
-                                  MaxDifference, MeasureCombination, MKLDivergence, Parity, PearsonCorrelation, PPV, RMabs,
+                                  MaxDifference, MeasureCombination, MKLDivergence, Modularity, Parity, PearsonCorrelation, PPV, RMabs,
                                   SpearmanCorrelation, Supervised, TNR, TPR, Unsupervised, pRule, split)
 from pygrank_amd.convergence import ConvergenceManager
 from pygrank_amd.postprocess import (LinearSweep, Normalize, Ordinals, Postprocessor, Sweep, Tautology, Threshold, Top,
@@ -38,5 +38,6 @@ from pygrank_amd.autotune import AlgorithmSelection, ParameterTuner, SelfClearDi
 from pygrank_amd.comparables import create_demo_filters, create_many_filters, create_variations
 from pygrank_amd.fairness import AdHocFairness, FairPersonalizer
 from pygrank_amd.oversampling import BoostedSeedOversampling, SeedOversampling
+from pygrank_amd.multigroup import ClusteringCoefficient, LinkAssessment, MultiSupervised, MultiUnsupervised
 
 __version__ = "0.1.0"

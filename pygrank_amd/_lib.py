@@ -2,7 +2,7 @@
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
 include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h, the locally fair PageRank's entries of
 include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h, the rank-based measures' entries of include/pgh_rank.h,
-the Krylov-space filters' entries of include/pgh_krylov.h).
+the Krylov-space filters' entries of include/pgh_krylov.h, the multi-group measures' entries of include/pgh_link.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -308,6 +308,21 @@ KRYLOV_DECLINED = 2       # include/pgh_krylov.h PGH_KRYLOV_DECLINED: nothing wa
 KRYLOV_MAX_DIMS = 64      # include/pgh_krylov.h PGH_KRYLOV_MAX_DIMS
 KRYLOV_MAX_PROBES = 64    # include/pgh_krylov.h PGH_KRYLOV_MAX_PROBES
 
+# name -> (restype, argtypes); every symbol include/pgh_link.h declares.  Bound apart like the Krylov entries (link_entry): on a library
+# without them LinkAssessment and ClusteringCoefficient score the downloaded slab with numpy.
+c_link_plan = C.c_void_p
+LINK_SIGNATURES = {
+    "pgh_link_plan_create": (C.c_int, [C.c_int64, C.c_int64, c_i32p, c_i32p, C.POINTER(C.c_uint8), C.POINTER(c_link_plan)]),
+    "pgh_link_plan_info": (C.c_int, [c_link_plan, c_i64p, c_i64p, c_i64p]),
+    "pgh_link_plan_destroy": (C.c_int, [c_link_plan]),
+    "pgh_link_auc": (C.c_int, [c_mat, c_link_plan, C.c_int32, c_f64p, c_i64p, c_i64p]),
+    "pgh_link_predictions": (C.c_int, [c_mat, c_link_plan, C.c_int32, C.c_int64, C.c_int64, c_f64p]),
+    "pgh_link_factors": (C.c_int, [c_mat, C.c_int32, c_vec]),
+}
+LINK_DECLINED = 2         # include/pgh_link.h PGH_LINK_DECLINED: nothing was written, the caller scores the downloaded slab on the host
+LINK_MAX_PAIRS = 1 << 27  # include/pgh_link.h PGH_LINK_MAX_PAIRS
+LINK_COS, LINK_DOT = 0, 1                                                           # include/pgh_link.h PGH_LINK_*
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -387,6 +402,21 @@ def bind_rank(cdll):
 def bind_krylov(cdll):
     """Binds the include/pgh_krylov.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, KRYLOV_SIGNATURES)
+
+
+def bind_link(cdll):
+    """Binds the include/pgh_link.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, LINK_SIGNATURES)
+
+
+def link_entry(name):
+    """The bound include/pgh_link.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_link_entries", None)
+    if cache is None:
+        cache = bind_link(cdll)
+        cdll._pgh_link_entries = cache
+    return cache[name]
 
 
 def krylov_entry(name):

@@ -16,11 +16,12 @@ AUC and MannWhitneyParity score a slab through the tuner's pgh_probe_auc (includ
 NDCG (supervised.py:68-90) and SpearmanCorrelation (:274-279) score a slab through include/pgh_rank.h: the DCG
 of 64 columns in one streaming pass, Spearman's rho with one device sort per column, both through a plan shared by every call.  The
 combinations of measures/combination.py (AM, GM, Disparity, Parity) live in pygrank_amd/combination.py and are re-exported here.
-Mistreatment and measures/multigroup.py stay out of scope.
+measures/multigroup.py lives in pygrank_amd/multigroup.py; Mistreatment stays out of scope.
 
 The unsupervised measures Conductance and Density (pygrank/measures/unsupervised.py:8-145) score a ranking without ground truth.  They are
 the reference's only measures that run `conv` themselves: two passes over the adjacency per score column.  Here the columns of a batch
 travel as one slab (include/pgh_measure.h: pgh_mat_col_stats + pgh_cut_forms): 64 columns cost two passes.
+Modularity (unsupervised.py:148-201) is a closed form over the same entries in place of the reference's loop over has_edge.
 """
 import collections.abc
 import ctypes as C
@@ -981,6 +982,132 @@ class Density(Unsupervised):
         internal_edges = backend.dot(backend.conv(scores, adjacency), scores)
         expected_edges = backend.sum(scores) ** 2 - backend.sum(scores ** 2)
         return backend.safe_div(internal_edges, expected_edges)
+
+
+class Modularity(Unsupervised):
+    """unsupervised.py:148-201: modularity of the fuzzy subgraph the scores describe, over a sample of the nodes.  With c_v the
+    multiplicity of v in the sample (all ones while the graph has at most max_positive_samples nodes; else the sample is
+    ``RandomState(seed).choice(n, max_positive_samples)``, a private generator where the reference reseeds numpy's global one) and
+    w = c * scores / max_rank,
+
+        Q = (w^T P w - (sum_v w_v d_v)^2 / 2m) / 2m
+
+    P the 0/1 pattern of the adjacency (``has_edge``), d = ``graph.degree`` and m = ``number_of_edges()`` with networkx's conventions
+    (in + out degree on a directed graph; on an undirected one a self-loop counts twice in the degree and once in m); m = 0 gives 0.
+    This closed form REPLACES the reference's O(samples^2) loop over ``has_edge``: the same sum, regrouped.  w^T P w is pgh_cut_forms
+    (PGH_CUT_INTERNAL) on the graph diag(c) P diag(c), sum w d the <known, scores> slot of pgh_pair_forms against c * d: up to 64
+    columns share both passes (``evaluate_many``).  fused=False, a library without the entries or a decline evaluates the same closed
+    form column by column with backend primitives (conv and dot)."""
+
+    def __init__(self, graph=None, max_rank=1, max_positive_samples=2000, seed=0, progress=lambda x: x, fused=True):
+        self.graph = graph
+        self.max_positive_samples = max_positive_samples
+        self.max_rank = max_rank
+        self.seed = seed
+        self.progress = progress                             # kept for the reference's signature: there is no loop to wrap
+        self.fused = fused
+        self.last_route = None
+        self._prepared = None
+
+    def _prepare(self, graph):
+        """Per graph: 2m, the device graph diag(c) P diag(c) and the vector c * d."""
+        import numpy as np
+        import scipy.sparse as sp
+        from pygrank_amd import multigroup
+        cached = self._prepared
+        if cached is not None and cached["of"] is graph and self.seed is not None:
+            return cached
+        taken, P = multigroup.pattern(graph)
+        n = P.shape[0]
+        out_degree = np.diff(P.indptr).astype(np.int64)
+        if taken.is_directed():
+            degree = out_degree + np.bincount(P.indices, minlength=n).astype(np.int64)
+            edges = int(P.nnz)
+        else:
+            loops = P.diagonal().astype(np.int64)
+            degree = out_degree + loops
+            edges = (int(P.nnz) + int(loops.sum())) // 2
+        prepared = dict(of=graph, edges=edges, graph=None, weighted_degree=None)
+        if edges != 0:
+            candidates, _ = multigroup.sample(n, self.max_positive_samples, self.seed)
+            counts = np.bincount(candidates, minlength=n).astype(np.float64)
+            scale = sp.dia_array((counts[None, :], [0]), shape=(n, n))
+            M = sp.csr_array(scale @ P.astype(np.float64) @ scale)
+            M.eliminate_zeros()
+            prepared["graph"] = backend.scipy_sparse_to_backend(M)
+            prepared["weighted_degree"] = backend.to_array(counts * degree)
+        self._prepared = prepared
+        return prepared
+
+    def _value(self, prepared, internal, weighted):
+        m = prepared["edges"]
+        return (internal - weighted * weighted / 2 / m) / 2 / m
+
+    def _slab(self, prepared, matrix):
+        import numpy as np
+        forms_fn, pair_fn = L.measure_entry("pgh_cut_forms"), L.supervised_entry("pgh_pair_forms")
+        out = []
+        for first in range(0, matrix.b, 64):
+            part = matrix if matrix.b <= 64 else matrix.get_cols(first, min(64, matrix.b - first))
+            factors = np.full(part.b, 1.0 / self.max_rank, dtype=np.float64)
+            forms = np.empty((part.b, 4), dtype=np.float64)
+            status = forms_fn(prepared["graph"]._h, part._h, factors.ctypes.data_as(C.c_void_p), 1.0, L.CUT_INTERNAL,
+                              forms.ctypes.data_as(C.c_void_p))
+            if status == L.MEASURE_DECLINED:
+                return None
+            L.check(status)
+            slots = np.empty((part.b, L.PAIR_SLOTS), dtype=np.float64)
+            status = pair_fn(part._h, prepared["weighted_degree"]._h, None, None, None, None, backend.epsilon(), L.PAIR_MOMENTS,
+                             slots.ctypes.data_as(C.c_void_p))
+            if status == L.PAIR_DECLINED:
+                return None
+            L.check(status)
+            out.extend(self._value(prepared, float(forms[j][0]), float(slots[j][5]) / self.max_rank) for j in range(part.b))
+        return out
+
+    def _one(self, prepared, scores):
+        w = scores / self.max_rank if self.max_rank != 1 else scores
+        return self._value(prepared, backend.dot(backend.conv(w, prepared["graph"]), w), backend.dot(w, prepared["weighted_degree"]))
+
+    def _route(self, graph, columns):
+        prepared = self._prepare(graph)
+        count = columns.b if isinstance(columns, DeviceMatrix) else len(columns)
+        if prepared["edges"] == 0:
+            return [0] * count
+        if self.fused and not _FORCE_PER_COLUMN and isinstance(prepared["graph"], DeviceGraph) \
+                and L.measure_entry("pgh_cut_forms") is not None and L.supervised_entry("pgh_pair_forms") is not None:
+            matrix = columns if isinstance(columns, DeviceMatrix) else DeviceMatrix.from_columns(columns)
+            out = self._slab(prepared, matrix)
+            if out is not None:
+                self.last_route = "slab"
+                return out
+        self.last_route = "columns"
+        vectors = columns.columns() if isinstance(columns, DeviceMatrix) else columns
+        for vector in vectors:
+            vector._h                       # noqa: B018 -- an unevaluated expression (device.LazyVector) is evaluated first
+        return [self._one(prepared, vector) for vector in vectors]
+
+    def evaluate(self, scores):
+        scores = to_signal(self.graph, scores)
+        return self._route(scores.graph, [scores.np])[0]
+
+    def evaluate_many(self, columns):
+        """What evaluate returns for every column, as a list: `columns` is a DeviceMatrix over the measure's graph, or a list of graph
+        signals / score vectors of one graph.  On the slab route up to 64 columns share the two passes."""
+        if isinstance(columns, DeviceMatrix):
+            if self.graph is None:
+                raise Exception("a slab of score columns can only be evaluated by a measure that was given its graph")
+            graph = self.graph.graph if isinstance(self.graph, GraphSignal) else self.graph
+            if columns.n != len(graph):
+                raise Exception(f"a slab of {columns.n} rows cannot hold scores of {len(graph)} nodes")
+            return self._route(graph, columns)
+        signals = [to_signal(self.graph, column) for column in columns]
+        if not signals:
+            return []
+        graph = signals[0].graph
+        if any(signal.graph is not graph for signal in signals):
+            raise Exception("the score columns belong to different graphs")
+        return self._route(graph, [signal.np for signal in signals])
 
 
 def split(groups, training_samples=0.8, seed=0):
