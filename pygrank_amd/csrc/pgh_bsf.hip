@@ -48,24 +48,6 @@ inline int blocks_for(int64_t n, int cap_mult = 16) {
     return (int)b;
 }
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)pooled_free(p);
-    }
-    int alloc(size_t count, bool zero = false) {
-        PGH_HIP(pooled_malloc(&p, sizeof(T) * (count > 0 ? count : 1)));
-        if (zero) PGH_HIP(hipMemsetAsync(p, 0, sizeof(T) * (count > 0 ? count : 1), rt().stream));
-        return 0;
-    }
-    T* release() {
-        T* q = p;
-        p = nullptr;
-        return q;
-    }
-};
-
 // ------------------------------------------------------------------------------------------------- builder kernels
 // reference count of every source (weights count as multiplicities when the format is value-free)
 __global__ void k_source_counts(const int32_t* __restrict__ col, const int32_t* __restrict__ mult, int64_t nnz,

@@ -101,6 +101,55 @@ inline hipError_t pooled_free(void* p) {
     pool_free(p);
     return hipSuccess;
 }
+namespace {     // (no exported symbols)
+// Pool blocks that go back when their frame ends, so that an early return frees them.  PoolBuf: bytes, viewed through as<T>();
+// DevBuf<T>: `count` elements (zero: cleared on the engine's stream), release() hands the block to a longer-lived owner.
+struct PoolBuf {
+    void* p = nullptr;
+    ~PoolBuf() {
+        if (p) pool_free(p);
+    }
+    int alloc(size_t bytes) { return pool_alloc(bytes > 0 ? bytes : 1, &p); }
+    template <typename T>
+    T* as() { return static_cast<T*>(p); }
+    template <typename T>
+    T* release() {
+        T* q = as<T>();
+        p = nullptr;
+        return q;
+    }
+};
+// Declared in front of the first enqueue that reads host memory of the caller (or of this frame): every way out of the frame, an
+// error's included, waits for the engine's stream first, so the memory may go away afterwards.  The way out that waits itself says so
+// (wait(), or passed = true behind a callee that waited) and is not made to wait twice.  Buffers declared before it are freed later.
+struct StreamFence {
+    bool passed = false;
+    ~StreamFence() {
+        if (!passed) (void)hipStreamSynchronize(rt().stream);
+    }
+    hipError_t wait() {
+        passed = true;
+        return hipStreamSynchronize(rt().stream);
+    }
+};
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)pooled_free(p);
+    }
+    int alloc(size_t count, bool zero = false) {
+        PGH_HIP(pooled_malloc(&p, sizeof(T) * (count > 0 ? count : 1)));
+        if (zero) PGH_HIP(hipMemsetAsync(p, 0, sizeof(T) * (count > 0 ? count : 1), rt().stream));
+        return 0;
+    }
+    T* release() {
+        T* q = p;
+        p = nullptr;
+        return q;
+    }
+};
+}  // namespace
 
 // merge items (rows + nnz) per thread of a 256-thread workgroup; the tile table is built for 256 * PGH_IPT
 #ifndef PGH_IPT

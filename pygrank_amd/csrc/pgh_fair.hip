@@ -12,7 +12,7 @@
 //                  per lane, not per element.
 //   exp(-b d) is the reciprocal of exp(b d) while |b d| < 700 (both finite and normal there: one rounding more, far below the f32
 //   store's half ulp); outside it is evaluated on its own.
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_fair.h"
 
 #include <cmath>
@@ -21,21 +21,19 @@
 using namespace pgh;
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 2048;   // 256 CUs x 8 workgroups, grid-stride beyond
 constexpr int kMaxParams = PGH_FAIR_MAX_PROBES * (4 * PGH_FAIR_MAX_BUCKETS + 1);
 
-__global__ __launch_bounds__(kBlock) void k_prior_edit(const float* __restrict__ pers, const float* __restrict__ sens,
-                                                        const float* __restrict__ ranks, double rank_max,
-                                                        const double* __restrict__ params /* [probes][np]: (a1 - a0, a0, b1 - b0, b0) x buckets, residual */,
-                                                        int buckets, int probes, int skew, int64_t n, float* __restrict__ out) {
+__global__ __launch_bounds__(kSlabBlock) void k_prior_edit(const float* __restrict__ pers, const float* __restrict__ sens,
+                                                            const float* __restrict__ ranks, double rank_max,
+                                                            const double* __restrict__ params /* [probes][np]: (a1 - a0, a0, b1 - b0, b0) x buckets, residual */,
+                                                            int buckets, int probes, int skew, int64_t n, float* __restrict__ out) {
     __shared__ double s_p[kMaxParams];
     const int np = 4 * buckets + 1;
-    for (int j = threadIdx.x; j < probes * np; j += kBlock) s_p[j] = params[j];
+    for (int j = threadIdx.x; j < probes * np; j += kSlabBlock) s_p[j] = params[j];
     __syncthreads();
     const int64_t total = n * probes;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * kSlabBlock;
+    int64_t e = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x;
     if (e >= total) return;
     int64_t row = e / probes;
     int col = (int)(e - row * probes);
@@ -66,10 +64,7 @@ __global__ __launch_bounds__(kBlock) void k_prior_edit(const float* __restrict__
     }
 }
 
-int decline(const std::string& why) {
-    set_error("pgh_prior_edit declined: " + why);
-    return PGH_FAIR_DECLINED;
-}
+const char* const kEdit = "pgh_prior_edit";
 }  // namespace
 
 PGH_WARM_KERNEL(k_prior_edit)
@@ -78,18 +73,18 @@ extern "C" int pgh_prior_edit(pgh_vec_t personalization, pgh_vec_t sensitive, pg
                               const double* params_host, int32_t buckets, int32_t probes, int32_t skew, pgh_mat_t out) {
     PGH_CHECK(personalization && sensitive && ranks && params_host && out, "pgh_prior_edit: null argument");
     PGH_CHECK(probes >= 1 && buckets >= 0, "pgh_prior_edit: probes >= 1 and buckets >= 0 expected");
-    if (probes > PGH_FAIR_MAX_PROBES) return decline("more than 64 probes");
-    if (buckets > PGH_FAIR_MAX_BUCKETS) return decline("more than 4 parameter buckets");
+    if (probes > PGH_FAIR_MAX_PROBES) return declined(PGH_FAIR_DECLINED, kEdit, "more than 64 probes");
+    if (buckets > PGH_FAIR_MAX_BUCKETS) return declined(PGH_FAIR_DECLINED, kEdit, "more than 4 parameter buckets");
     const int64_t n = personalization->n;
     PGH_CHECK(sensitive->n == n && ranks->n == n && out->n == n, "pgh_prior_edit: the three vectors and out differ in length");
     PGH_CHECK(out->b == probes, "pgh_prior_edit: out must have one column per probe");
-    if (rank_max == 0.0 || !std::isfinite(rank_max)) return decline("rank_max is zero or not finite");
+    if (rank_max == 0.0 || !std::isfinite(rank_max)) return declined(PGH_FAIR_DECLINED, kEdit, "rank_max is zero or not finite");
     const int np = 4 * buckets + 1;
     std::vector<double> staged((size_t)probes * np);
     for (int q = 0; q < probes; ++q) {
         const double* P = params_host + (size_t)q * np;
         for (int j = 0; j < np; ++j)
-            if (!std::isfinite(P[j])) return decline("non-finite parameter");
+            if (!std::isfinite(P[j])) return declined(PGH_FAIR_DECLINED, kEdit, "non-finite parameter");
         double* S = staged.data() + (size_t)q * np;
         for (int t = 0; t < buckets; ++t) {
             S[4 * t] = P[4 * t] - P[4 * t + 1];
@@ -103,19 +98,13 @@ extern "C" int pgh_prior_edit(pgh_vec_t personalization, pgh_vec_t sensitive, pg
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const size_t bytes = sizeof(double) * staged.size();
-    double* d_p = nullptr;
-    PGH_TRY(pool_alloc(bytes, (void**)&d_p));
-    hipError_t e = hipMemcpyAsync(d_p, staged.data(), bytes, hipMemcpyHostToDevice, r.stream);
-    if (e == hipSuccess) {
-        const int64_t total = n * probes;
-        int64_t grid = (total + kBlock - 1) / kBlock;
-        if (grid > kMaxGrid) grid = kMaxGrid;
-        k_prior_edit<<<(int)grid, kBlock, 0, r.stream>>>(personalization->data, sensitive->data, ranks->data, rank_max, d_p, buckets, probes,
-                                                         skew != 0 ? 1 : 0, n, out->data);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(r.stream);   // the staged parameters go away
-    pool_free(d_p);
-    if (e != hipSuccess) return fail(std::string("pgh_prior_edit: ") + hipGetErrorString(e));
+    PoolBuf d_p;
+    PGH_TRY(d_p.alloc(bytes));
+    StreamFence fence;                                       // the staged parameters go away
+    PGH_HIP(hipMemcpyAsync(d_p.p, staged.data(), bytes, hipMemcpyHostToDevice, r.stream));
+    k_prior_edit<<<grid_capped(n * probes, kSlabBlock), kSlabBlock, 0, r.stream>>>(personalization->data, sensitive->data, ranks->data, rank_max,
+                                                                          d_p.as<double>(), buckets, probes, skew != 0 ? 1 : 0, n, out->data);
+    PGH_HIP(hipGetLastError());
+    PGH_HIP(fence.wait());
     return 0;
 }

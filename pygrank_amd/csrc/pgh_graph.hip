@@ -140,23 +140,6 @@ __global__ void k_flags_from_exclude(const float* __restrict__ ex, int64_t n, ch
         flags[i] = ex[i] == 0.f ? 1 : 0;
 }
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)pooled_free(p);
-    }
-    int alloc(size_t count) {
-        PGH_HIP(pooled_malloc(&p, sizeof(T) * (count > 0 ? count : 1)));
-        return 0;
-    }
-    T* release() {
-        T* q = p;
-        p = nullptr;
-        return q;
-    }
-};
-
 }  // namespace
 
 namespace pgh {

@@ -10,7 +10,7 @@
 //   k_lanczos_close<U, BASIS>  lane <-> four consecutive elements (16-byte loads and stores), grid-stride; the elements behind the last
 //                              whole quad -- or all of them when an operand is not 16-byte aligned -- go one per lane.  The slab column
 //                              is written with four 4-byte stores per lane (stride b).  HBM-streaming.
-//   k_krylov_fold              one workgroup folds the block partials of both sums in their order.
+//   k_fold_regions             one workgroup folds the block partials of both sums in their order (pgh_slab.h).
 //   k_krylov_residuals<LPR>    the lane mapping of k_mat_gemm (pgh_runtime.hip): LPR lanes share a row (same address: one request) and
 //                              hold four probes each, the coefficients sit in LDS as doubles; instead of storing the [n, probes] product
 //                              every lane keeps sum |.| and max |.| of its four probes over its rows, the workgroup folds its rows
@@ -19,7 +19,7 @@
 // Every grid is a function of the shape alone and no kernel uses atomics, so two calls on the same input return the same bits.
 // The stored value (w - a v) - b u is formed from individually rounded f64 operations in that order: this file is compiled with
 // contraction into fused multiply-adds switched off (as pgh_lfpr.hip; a difference that cancels comes out as in a plain f64 evaluation).
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_krylov.h"
 
 #include <cmath>
@@ -30,17 +30,9 @@ using namespace pgh;
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 2048;       // 256 CUs x 8 workgroups, grid-stride beyond
 constexpr int kMaxResGrid = 1024;    // residual pass: 256 CUs x 4 workgroups (48 KB of LDS each)
-static_assert(kMaxGrid <= kMaxPartials && kPartialRegions >= 2, "one region of block partials per sum");
+static_assert(kPartialRegions >= 2, "one region of block partials per sum");
 static_assert(PGH_KRYLOV_MAX_DIMS == 64 && PGH_KRYLOV_MAX_PROBES == 64, "the coefficient tile of k_krylov_residuals is 64 x 64 doubles");
-
-// Behind the loads of an iteration: every load is in flight before the first use ("Waits")
-__device__ __forceinline__ void loads_issued() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 template <bool HAS_U>
 __device__ __forceinline__ float close_one(float w, float v, float u, double a, double b, double& sq, double& ov) {
@@ -53,15 +45,14 @@ __device__ __forceinline__ float close_one(float w, float v, float u, double a, 
     return stored;
 }
 
-// No operand carries __restrict__ (pgh_lfpr.hip: with it the optimiser sinks the loads past loads_issued() to their uses); out is
-// distinct from every input, checked by the caller
+// No operand carries __restrict__ (loads_issued(), pgh_slab.h); out is distinct from every input, checked by the caller
 template <bool HAS_U, bool HAS_BASIS>
-__global__ __launch_bounds__(kBlock) void k_lanczos_close(const float* w, const float* v, double a, const float* u, double b, int64_t n,
-                                                           int64_t nvec, float* out, float* basis, int ld, int col,
-                                                           double* __restrict__ partials) {
+__global__ __launch_bounds__(kSlabBlock) void k_lanczos_close(const float* w, const float* v, double a, const float* u, double b, int64_t n,
+                                                               int64_t nvec, float* out, float* basis, int ld, int col,
+                                                               double* __restrict__ partials) {
     __shared__ double s_red[4];
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    const int64_t gtid = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * kSlabBlock;
+    const int64_t gtid = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x;
     double sq = 0.0, ov = 0.0;
     for (int64_t q = gtid; q < nvec; q += stride) {
         const float4 w4 = reinterpret_cast<const float4*>(w)[q];
@@ -96,29 +87,17 @@ __global__ __launch_bounds__(kBlock) void k_lanczos_close(const float* w, const 
     }
 }
 
-// out[k] = sum of region k's `count` block partials, k < 2: thread t takes partials t, t + 256, ... in order, then the block reduction
-__global__ __launch_bounds__(kBlock) void k_krylov_fold(const double* __restrict__ partials, int count, double* __restrict__ out) {
-    __shared__ double s_red[4];
-    for (int k = 0; k < 2; ++k) {
-        const double* __restrict__ part = partials + (size_t)k * kMaxPartials;
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < count; i += kBlock) acc += part[i];
-        acc = block_reduce_256<0>(acc, s_red);
-        if (threadIdx.x == 0) out[k] = acc;
-    }
-}
-
 // part[block][0 .. probes) = sum |r[i, t]|, part[block][probes .. 2 probes) = max |r[i, t]| over the rows of this workgroup
 template <int LPR>
-__global__ __launch_bounds__(kBlock) void k_krylov_residuals(const float* __restrict__ m, int64_t n, int b, const double* __restrict__ deltas,
-                                                              int count, int probes, double* __restrict__ part) {
+__global__ __launch_bounds__(kSlabBlock) void k_krylov_residuals(const float* __restrict__ m, int64_t n, int b, const double* __restrict__ deltas,
+                                                                  int count, int probes, double* __restrict__ part) {
 #pragma clang fp contract(fast)      // (one rounding per multiply-add: half the f64 instructions, and nothing here cancels)
     __shared__ double s_c[PGH_KRYLOV_MAX_DIMS * PGH_KRYLOV_MAX_PROBES];
-    __shared__ double s_sum[kBlock * 4];
-    __shared__ double s_max[kBlock * 4];
-    for (int j = threadIdx.x; j < count * probes; j += kBlock) s_c[j] = deltas[j];
+    __shared__ double s_sum[kSlabBlock * 4];
+    __shared__ double s_max[kSlabBlock * 4];
+    for (int j = threadIdx.x; j < count * probes; j += kSlabBlock) s_c[j] = deltas[j];
     __syncthreads();
-    constexpr int ROWS = kBlock / LPR;
+    constexpr int ROWS = kSlabBlock / LPR;
     const int q0 = (threadIdx.x % LPR) * 4, r_in = threadIdx.x / LPR;
     double sum[4] = {0.0, 0.0, 0.0, 0.0}, top[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t i = blockIdx.x * (int64_t)ROWS + r_in; i < n; i += (int64_t)gridDim.x * ROWS) {
@@ -168,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void k_krylov_residuals(const float* __rest
 
 // out[t] = sum over the blocks, out[probes + t] = max over the blocks: wavefront w takes probes w, w + 4, ..., its lanes the blocks
 // l, l + 64, ... in order, then the wavefront reduction
-__global__ __launch_bounds__(kBlock) void k_krylov_fold_probes(const double* __restrict__ part, int blocks, int probes, double* __restrict__ out) {
+__global__ __launch_bounds__(kSlabBlock) void k_krylov_fold_probes(const double* __restrict__ part, int blocks, int probes, double* __restrict__ out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int t = wave; t < probes; t += 4) {
         double s = 0.0, top = 0.0;
@@ -184,16 +163,9 @@ __global__ __launch_bounds__(kBlock) void k_krylov_fold_probes(const double* __r
         }
     }
 }
-
-int decline(const char* who, const std::string& why) {
-    set_error(std::string(who) + " declined: " + why);
-    return PGH_KRYLOV_DECLINED;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 }  // namespace
 
-PGH_WARM_KERNEL(k_krylov_fold)
+PGH_WARM_KERNEL(k_krylov_fold_probes)
 
 extern "C" int pgh_lanczos_close(pgh_vec_t w, pgh_vec_t v, double a, pgh_vec_t u, double b, pgh_vec_t out, pgh_mat_t basis, int32_t col,
                                  double* sums_host) {
@@ -205,7 +177,7 @@ extern "C" int pgh_lanczos_close(pgh_vec_t w, pgh_vec_t v, double a, pgh_vec_t u
     if (n > 0)
         PGH_CHECK(out->data != w->data && out->data != v->data && (u == nullptr || out->data != u->data),
                   "pgh_lanczos_close: out shares its memory with an input");
-    if (!(std::isfinite(a) && std::isfinite(b))) return decline("pgh_lanczos_close", "a coefficient is not finite");
+    if (!(std::isfinite(a) && std::isfinite(b))) return declined(PGH_KRYLOV_DECLINED, "pgh_lanczos_close", "a coefficient is not finite");
     if (n == 0) {
         sums_host[0] = sums_host[1] = 0.0;
         return 0;
@@ -215,26 +187,19 @@ extern "C" int pgh_lanczos_close(pgh_vec_t w, pgh_vec_t v, double a, pgh_vec_t u
     const bool ok16 = aligned16(w->data) && aligned16(v->data) && aligned16(out->data) && (u == nullptr || aligned16(u->data));
     const int64_t nvec = ok16 ? n / 4 : 0;
     const int64_t lanes = nvec + (n - 4 * nvec);
-    int64_t g = (lanes + kBlock - 1) / kBlock;
-    if (g > kMaxGrid) g = kMaxGrid;
-    const int grid = (int)g;
+    const int grid = grid_capped(lanes, kSlabBlock);
     const float* up = u ? u->data : v->data;
     float* bp = basis ? basis->data : nullptr;
     const int ld = basis ? basis->b : 0;
 #define PGH_CLOSE(U, B) \
-    k_lanczos_close<U, B><<<grid, kBlock, 0, r.stream>>>(w->data, v->data, a, up, b, n, nvec, out->data, bp, ld, col, r.d_partials)
+    k_lanczos_close<U, B><<<grid, kSlabBlock, 0, r.stream>>>(w->data, v->data, a, up, b, n, nvec, out->data, bp, ld, col, r.d_partials)
     if (u != nullptr && basis != nullptr) PGH_CLOSE(true, true);
     else if (u != nullptr) PGH_CLOSE(true, false);
     else if (basis != nullptr) PGH_CLOSE(false, true);
     else PGH_CLOSE(false, false);
 #undef PGH_CLOSE
     PGH_HIP(hipGetLastError());
-    k_krylov_fold<<<1, kBlock, 0, r.stream>>>(r.d_partials, grid, r.d_scalars);
-    PGH_HIP(hipGetLastError());
-    PGH_TRY(scalars_to_host(0, 2));
-    sums_host[0] = r.h_scalars[0];
-    sums_host[1] = r.h_scalars[1];
-    return 0;
+    return fold_regions_to_host(grid, 2, -1, sums_host);
 }
 
 extern "C" int pgh_krylov_residuals(pgh_mat_t basis, const double* deltas_host, int32_t count, int32_t probes, double* abssum_host,
@@ -244,7 +209,7 @@ extern "C" int pgh_krylov_residuals(pgh_mat_t basis, const double* deltas_host, 
               "pgh_krylov_residuals: 1 <= count <= basis.b <= 64");
     PGH_CHECK(probes >= 1 && probes <= PGH_KRYLOV_MAX_PROBES, "pgh_krylov_residuals: 1 <= probes <= 64");
     for (int64_t k = 0; k < (int64_t)count * probes; ++k)
-        if (!std::isfinite(deltas_host[k])) return decline("pgh_krylov_residuals", "a coefficient is not finite");
+        if (!std::isfinite(deltas_host[k])) return declined(PGH_KRYLOV_DECLINED, "pgh_krylov_residuals", "a coefficient is not finite");
     const int64_t n = basis->n;
     if (n == 0) {
         for (int t = 0; t < probes; ++t) abssum_host[t] = absmax_host[t] = 0.0;
@@ -252,8 +217,8 @@ extern "C" int pgh_krylov_residuals(pgh_mat_t basis, const double* deltas_host, 
     }
     PGH_TRY(ensure_init());
     Runtime& r = rt();
-    const int lpr = probes > 32 ? 16 : (probes > 16 ? 8 : (probes > 8 ? 4 : (probes > 4 ? 2 : 1)));
-    const int rows = kBlock / lpr;
+    const int lpr = lpr_for(probes);
+    const int rows = kSlabBlock / lpr;
     int64_t g = (n + rows - 1) / rows;
     if (g > kMaxResGrid) g = kMaxResGrid;
     const int grid = (int)g;
@@ -266,7 +231,7 @@ extern "C" int pgh_krylov_residuals(pgh_mat_t basis, const double* deltas_host, 
     hipError_t e = hipMemcpyAsync(d, deltas_host, sizeof(double) * coeffs, hipMemcpyHostToDevice, r.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r.stream);           // the caller's array may go away
     if (e == hipSuccess) {
-#define PGH_RES(LPR) k_krylov_residuals<LPR><<<grid, kBlock, 0, r.stream>>>(basis->data, n, basis->b, d, count, probes, part)
+#define PGH_RES(LPR) k_krylov_residuals<LPR><<<grid, kSlabBlock, 0, r.stream>>>(basis->data, n, basis->b, d, count, probes, part)
         switch (lpr) {
             case 16: PGH_RES(16); break;
             case 8: PGH_RES(8); break;
@@ -275,7 +240,7 @@ extern "C" int pgh_krylov_residuals(pgh_mat_t basis, const double* deltas_host, 
             default: PGH_RES(1); break;
         }
 #undef PGH_RES
-        k_krylov_fold_probes<<<1, kBlock, 0, r.stream>>>(part, grid, probes, folded);
+        k_krylov_fold_probes<<<1, kSlabBlock, 0, r.stream>>>(part, grid, probes, folded);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), folded, sizeof(double) * 2 * probes, hipMemcpyDeviceToHost, r.stream);

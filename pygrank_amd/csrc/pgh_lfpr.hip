@@ -10,7 +10,7 @@
 //                        quad -- or all of them when an operand is not 16-byte aligned -- go one per lane.  Every operand load is
 //                        unconditional, the three cases are selects; the nullable `original` is the template parameter.
 //   k_lfpr_close<LINF>   the same shape: seven operand quads in, two out, five sums.
-//   k_lfpr_fold          one workgroup folds the block partials of every sum in their order.
+//   k_fold_regions       one workgroup folds the block partials of every sum in their order (pgh_slab.h).
 // Sums: f64 per lane -> wavefront shuffles -> LDS -> one partial per workgroup in rt().d_partials (one region per sum) -> the fold.  The
 // grid is a function of the length alone, so two calls on the same input return the same bits.
 // Every stored value, the residual term y * y_scale - x * x_scale and the case test R < phi * (R + B) are formed from individually rounded
@@ -19,7 +19,7 @@
 // any other product and sum: measured -- a row on the edge came out as 2^-54 instead of 0 with them), so that a sign, a maximum,
 // a row exactly on the edge between two cases and a difference that cancels (dR and dB next to that edge) come out as in a plain f64
 // evaluation.  The kernels are bound by HBM, not by these operations.
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_lfpr.h"
 
 #include <cmath>
@@ -29,16 +29,9 @@ using namespace pgh;
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 2048;   // 256 CUs x 8 workgroups, grid-stride beyond
-static_assert(kMaxGrid <= kMaxPartials && kPartialRegions >= 5, "one region of block partials per sum");
-
-// Behind the loads of an iteration: neither the optimiser nor the scheduler moves a load below this point, so every load is in flight
-// before the first use ("Waits"; without it the compiler sinks each load to its use and waits for them in turn)
-__device__ __forceinline__ void loads_issued() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
+static_assert(kPartialRegions >= 5, "one region of block partials per sum");
+const char* const kSetup = "pgh_lfpr_setup";
+const char* const kClose = "pgh_lfpr_close";
 
 __device__ __forceinline__ double safe_inv(double v) { return v != 0.0 ? 1.0 / v : 0.0; }
 
@@ -61,14 +54,14 @@ __device__ __forceinline__ SetupOut setup_one(float s_, float r_, float b_, floa
 }
 
 template <bool ORIG>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_lfpr_setup(const float* __restrict__ sens, const float* __restrict__ out_r,
-                                                       const float* __restrict__ out_b, const float* __restrict__ orig, double phi, int64_t n,
-                                                       int64_t nvec, float* __restrict__ d, float* __restrict__ dr, float* __restrict__ db,
-                                                       float* __restrict__ xr, float* __restrict__ xb, double* __restrict__ partials) {
+__global__ __launch_bounds__(kSlabBlock) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_lfpr_setup(const float* __restrict__ sens, const float* __restrict__ out_r,
+                                                           const float* __restrict__ out_b, const float* __restrict__ orig, double phi, int64_t n,
+                                                           int64_t nvec, float* __restrict__ d, float* __restrict__ dr, float* __restrict__ db,
+                                                           float* __restrict__ xr, float* __restrict__ xb, double* __restrict__ partials) {
     __shared__ double s_red[4];
     const double omp = 1.0 - phi;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    const int64_t gtid = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * kSlabBlock;
+    const int64_t gtid = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x;
     double sum_r = 0.0, sum_b = 0.0;
     for (int64_t v = gtid; v < nvec; v += stride) {
         const float4 s4 = reinterpret_cast<const float4*>(sens)[v];
@@ -131,17 +124,16 @@ __device__ __forceinline__ CloseOut close_one(float y0, float x, float xr, float
     return out;
 }
 
-// y may be y0 (every element is read, then written, by the one lane that owns it).  No operand carries __restrict__: with it the
-// optimiser moves the loads of d, dR, dB past loads_issued() to their uses (measured in the assembly: 4 + 3 loads with a drained wait
-// between them); every load of an iteration precedes its stores anyway
+// y may be y0 (every element is read, then written, by the one lane that owns it).  No operand carries __restrict__ (loads_issued(),
+// pgh_slab.h); every load of an iteration precedes its stores anyway
 template <bool LINF>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_lfpr_close(const float* y0, const float* x, double x_scale, const float* xr,
-                                                       const float* xb, const float* d, const float* dr, const float* db, double cR,
-                                                       double cB, double y_scale, int64_t n, int64_t nvec, float* y, float* u,
-                                                       double* __restrict__ partials) {
+__global__ __launch_bounds__(kSlabBlock) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_lfpr_close(const float* y0, const float* x, double x_scale, const float* xr,
+                                                           const float* xb, const float* d, const float* dr, const float* db, double cR,
+                                                           double cB, double y_scale, int64_t n, int64_t nvec, float* y, float* u,
+                                                           double* __restrict__ partials) {
     __shared__ double s_red[4];
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    const int64_t gtid = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * kSlabBlock;
+    const int64_t gtid = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x;
     CloseAcc acc;
     for (int64_t v = gtid; v < nvec; v += stride) {
         const float4 a4 = reinterpret_cast<const float4*>(y0)[v];
@@ -178,54 +170,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 4))) 
     }
 }
 
-// out[k] = fold of region k's `count` block partials, k < regions: thread t takes partials t, t + 256, ... in order, then the block
-// reduction; region `max_at` (-1: none) is a maximum of non-negative values, the others are sums
-__global__ __launch_bounds__(kBlock) void k_lfpr_fold(const double* __restrict__ partials, int count, int regions, int max_at,
-                                                      double* __restrict__ out) {
-    __shared__ double s_red[4];
-    for (int k = 0; k < regions; ++k) {
-        const double* __restrict__ part = partials + (size_t)k * kMaxPartials;
-        double acc = 0.0;
-        if (k == max_at) {
-            for (int i = threadIdx.x; i < count; i += kBlock) acc = fmax(acc, part[i]);
-            acc = block_reduce_256<1>(acc, s_red);
-        } else {
-            for (int i = threadIdx.x; i < count; i += kBlock) acc += part[i];
-            acc = block_reduce_256<0>(acc, s_red);
-        }
-        if (threadIdx.x == 0) out[k] = acc;
-    }
-}
-
-int decline(const char* who, const std::string& why) {
-    set_error(std::string(who) + " declined: " + why);
-    return PGH_LFPR_DECLINED;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // quads the kernels take as 16-byte words, and the grid for them plus the elements that go one per lane
 void shape_for(int64_t n, bool all_aligned, int64_t* nvec, int* grid) {
     *nvec = all_aligned ? n / 4 : 0;
     const int64_t lanes = *nvec + (n - 4 * *nvec);
-    int64_t g = (lanes + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    if (g > kMaxGrid) g = kMaxGrid;
-    *grid = (int)g;
-}
-
-// sums_host[0 .. count) <- the folds of the first `count` regions of block partials
-int fold_to_host(int grid, int count, int max_at, double* sums_host) {
-    Runtime& r = rt();
-    k_lfpr_fold<<<1, kBlock, 0, r.stream>>>(r.d_partials, grid, count, max_at, r.d_scalars);
-    PGH_HIP(hipGetLastError());
-    PGH_TRY(scalars_to_host(0, count));
-    for (int k = 0; k < count; ++k) sums_host[k] = r.h_scalars[k];
-    return 0;
+    *grid = grid_capped(lanes, kSlabBlock);
 }
 }  // namespace
 
-PGH_WARM_KERNEL(k_lfpr_fold)
+PGH_WARM_KERNEL(k_lfpr_setup<false>)
 
 extern "C" int pgh_lfpr_setup(pgh_vec_t sensitive, pgh_vec_t out_r, pgh_vec_t out_b, pgh_vec_t original, double phi, pgh_vec_t d,
                               pgh_vec_t dR, pgh_vec_t dB, pgh_vec_t xR, pgh_vec_t xB, double* sums_host) {
@@ -242,7 +195,7 @@ extern "C" int pgh_lfpr_setup(pgh_vec_t sensitive, pgh_vec_t out_r, pgh_vec_t ou
             for (int b = 0; b < 4; ++b) PGH_CHECK(outs[a] != ins[b], "pgh_lfpr_setup: an output shares its memory with an input");
         }
     }
-    if (!std::isfinite(phi)) return decline("pgh_lfpr_setup", "phi is not finite");
+    if (!std::isfinite(phi)) return declined(PGH_LFPR_DECLINED, kSetup, "phi is not finite");
     if (n == 0) {
         sums_host[0] = sums_host[1] = 0.0;
         return 0;
@@ -256,13 +209,13 @@ extern "C" int pgh_lfpr_setup(pgh_vec_t sensitive, pgh_vec_t out_r, pgh_vec_t ou
     int grid = 1;
     shape_for(n, ok16, &nvec, &grid);
     if (original != nullptr)
-        k_lfpr_setup<true><<<grid, kBlock, 0, r.stream>>>(ins[0], ins[1], ins[2], ins[3], phi, n, nvec, outs[0], outs[1], outs[2], outs[3],
+        k_lfpr_setup<true><<<grid, kSlabBlock, 0, r.stream>>>(ins[0], ins[1], ins[2], ins[3], phi, n, nvec, outs[0], outs[1], outs[2], outs[3],
                                                           outs[4], r.d_partials);
     else
-        k_lfpr_setup<false><<<grid, kBlock, 0, r.stream>>>(ins[0], ins[1], ins[2], ins[0], phi, n, nvec, outs[0], outs[1], outs[2], outs[3],
+        k_lfpr_setup<false><<<grid, kSlabBlock, 0, r.stream>>>(ins[0], ins[1], ins[2], ins[0], phi, n, nvec, outs[0], outs[1], outs[2], outs[3],
                                                            outs[4], r.d_partials);
     PGH_HIP(hipGetLastError());
-    return fold_to_host(grid, 2, -1, sums_host);
+    return fold_regions_to_host(grid, 2, -1, sums_host);
 }
 
 extern "C" int pgh_lfpr_close(pgh_vec_t y0, pgh_vec_t x, double x_scale, pgh_vec_t xR, pgh_vec_t xB, pgh_vec_t d, pgh_vec_t dR,
@@ -281,9 +234,9 @@ extern "C" int pgh_lfpr_close(pgh_vec_t y0, pgh_vec_t x, double x_scale, pgh_vec
         }
     }
     if (!(std::isfinite(cR) && std::isfinite(cB) && std::isfinite(x_scale) && std::isfinite(y_scale)))
-        return decline("pgh_lfpr_close", "a coefficient or a scale is not finite");
+        return declined(PGH_LFPR_DECLINED, kClose, "a coefficient or a scale is not finite");
     if (err_kind != PGH_ERR_MABS && err_kind != PGH_ERR_L1 && err_kind != PGH_ERR_LINF)
-        return decline("pgh_lfpr_close", "the residual is sum |.| (PGH_ERR_MABS, PGH_ERR_L1) or max |.| (PGH_ERR_LINF)");
+        return declined(PGH_LFPR_DECLINED, kClose, "the residual is sum |.| (PGH_ERR_MABS, PGH_ERR_L1) or max |.| (PGH_ERR_LINF)");
     if (n == 0) {
         for (int k = 0; k < 5; ++k) sums_host[k] = 0.0;
         return 0;
@@ -297,11 +250,11 @@ extern "C" int pgh_lfpr_close(pgh_vec_t y0, pgh_vec_t x, double x_scale, pgh_vec
     shape_for(n, ok16, &nvec, &grid);
     const bool linf = err_kind == PGH_ERR_LINF;
     if (linf)
-        k_lfpr_close<true><<<grid, kBlock, 0, r.stream>>>(ins[0], ins[1], x_scale, ins[2], ins[3], ins[4], ins[5], ins[6], cR, cB, y_scale, n,
+        k_lfpr_close<true><<<grid, kSlabBlock, 0, r.stream>>>(ins[0], ins[1], x_scale, ins[2], ins[3], ins[4], ins[5], ins[6], cR, cB, y_scale, n,
                                                           nvec, y->data, u->data, r.d_partials);
     else
-        k_lfpr_close<false><<<grid, kBlock, 0, r.stream>>>(ins[0], ins[1], x_scale, ins[2], ins[3], ins[4], ins[5], ins[6], cR, cB, y_scale, n,
+        k_lfpr_close<false><<<grid, kSlabBlock, 0, r.stream>>>(ins[0], ins[1], x_scale, ins[2], ins[3], ins[4], ins[5], ins[6], cR, cB, y_scale, n,
                                                            nvec, y->data, u->data, r.d_partials);
     PGH_HIP(hipGetLastError());
-    return fold_to_host(grid, 5, linf ? 3 : -1, sums_host);
+    return fold_regions_to_host(grid, 5, linf ? 3 : -1, sums_host);
 }

@@ -18,7 +18,7 @@
 //                         2 * negatives_below + negatives_in_group from the prefix counts; 64-bit integer sums, one integer atomic per
 //                         wavefront (integer addition is associative: the result does not depend on the order of arrival).
 // No grid shape enters a result: a row is summed by one lane alone, a pair is a function of its two rows, the counts are integers.
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_link.h"
 
 #include <hipcub/hipcub.hpp>
@@ -49,32 +49,24 @@ struct pgh_link_plan_s {
 };
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 2048;
 constexpr int kChunk = 32;           // columns of a row tile in LDS at a time
 constexpr int kStrideMax = kChunk + 1;
 
-inline int grid_for(int64_t items, int per_block) {
-    int64_t g = (items + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    return (int)(g > kMaxGrid ? kMaxGrid : g);
-}
-
 // FACTORS = false: l2[i] = sum_j (double)S[i, j]^2 in ascending j.  FACTORS = true: out[i] = (float)(S[i, b-1] / sqrt(l2[i])), 0 for l2 = 0.
 template <bool FACTORS>
-__global__ __launch_bounds__(kBlock) void k_link_rows(const float* __restrict__ S, int64_t n, int b, double* __restrict__ l2, float* __restrict__ out) {
-    __shared__ float s_tile[kBlock * kStrideMax];
-    const int64_t tiles = (n + kBlock - 1) / kBlock;
+__global__ __launch_bounds__(kSlabBlock) void k_link_rows(const float* __restrict__ S, int64_t n, int b, double* __restrict__ l2, float* __restrict__ out) {
+    __shared__ float s_tile[kSlabBlock * kStrideMax];
+    const int64_t tiles = (n + kSlabBlock - 1) / kSlabBlock;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int64_t r0 = tile * kBlock;
-        const int rows = (int)((n - r0) < kBlock ? (n - r0) : kBlock);
+        const int64_t r0 = tile * kSlabBlock;
+        const int rows = (int)((n - r0) < kSlabBlock ? (n - r0) : kSlabBlock);
         double acc = 0.0;
         float last = 0.f;
         for (int c0 = 0; c0 < b; c0 += kChunk) {
             const int w = (b - c0) < kChunk ? (b - c0) : kChunk;
             const int stride = w | 1;
             __syncthreads();                                   // the previous chunk has been read
-            for (int t = threadIdx.x; t < rows * w; t += kBlock) {
+            for (int t = threadIdx.x; t < rows * w; t += kSlabBlock) {
                 const int r = t / w, c = t - r * w;
                 s_tile[r * stride + c] = S[(r0 + r) * (int64_t)b + c0 + c];
             }
@@ -99,8 +91,8 @@ __global__ __launch_bounds__(kBlock) void k_link_rows(const float* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_link_last_column(const float* __restrict__ S, int64_t n, int b, float* __restrict__ out) {
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) out[i] = S[i * b + (b - 1)];
+__global__ __launch_bounds__(kSlabBlock) void k_link_last_column(const float* __restrict__ S, int64_t n, int b, float* __restrict__ out) {
+    for (int64_t i = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kSlabBlock) out[i] = S[i * b + (b - 1)];
 }
 
 // ascending unsigned order of the keys = ascending order of the doubles; both zeros share a key
@@ -112,12 +104,12 @@ __device__ __forceinline__ unsigned long long order_key(double x) {
 
 // pair k = first_pair + i, i < count: keys[i] (when given) and preds[i] (when given)
 template <bool COS>
-__global__ __launch_bounds__(kBlock) void k_link_pairs(const float* __restrict__ S, int b, const double* __restrict__ l2, const int32_t* __restrict__ first,
-                                                        const int32_t* __restrict__ second, int64_t first_pair, int64_t count,
-                                                        unsigned long long* __restrict__ keys, double* __restrict__ preds,
-                                                        unsigned long long* __restrict__ nan_flag) {
+__global__ __launch_bounds__(kSlabBlock) void k_link_pairs(const float* __restrict__ S, int b, const double* __restrict__ l2, const int32_t* __restrict__ first,
+                                                            const int32_t* __restrict__ second, int64_t first_pair, int64_t count,
+                                                            unsigned long long* __restrict__ keys, double* __restrict__ preds,
+                                                            unsigned long long* __restrict__ nan_flag) {
     bool nan = false;
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kBlock) {
+    for (int64_t i = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kSlabBlock) {
         const int64_t v = first[first_pair + i], u = second[first_pair + i];
         const double sv = (double)S[v * b + (b - 1)], su = (double)S[u * b + (b - 1)];
         double pred = su * sv;
@@ -137,10 +129,10 @@ struct IsNegative {
 };
 
 // result[0] += sum over the positives at sorted positions i of 2 * negatives below key[i] + negatives at key[i]
-__global__ __launch_bounds__(kBlock) void k_link_count(const unsigned long long* __restrict__ keys, const uint8_t* __restrict__ labels,
-                                                        const uint32_t* __restrict__ neg_before, int64_t count, unsigned long long* __restrict__ result) {
+__global__ __launch_bounds__(kSlabBlock) void k_link_count(const unsigned long long* __restrict__ keys, const uint8_t* __restrict__ labels,
+                                                            const uint32_t* __restrict__ neg_before, int64_t count, unsigned long long* __restrict__ result) {
     unsigned long long wins = 0;
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kBlock) {
+    for (int64_t i = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kSlabBlock) {
         if (labels[i] == 0) continue;
         const unsigned long long key = keys[i];
         int64_t lo = 0, hi = i;                   // first position whose key is not below `key`
@@ -157,13 +149,8 @@ __global__ __launch_bounds__(kBlock) void k_link_count(const unsigned long long*
         const unsigned long long below = neg_before[begin], tied = neg_before[lo] - neg_before[begin];
         wins += 2ull * below + tied;
     }
-    for (int off = 32; off >= 1; off >>= 1) wins += __shfl_down(wins, off, 64);
+    wins = wave_sum_u64(wins, 1);
     if ((threadIdx.x & 63) == 0 && wins) atomicAdd(&result[0], wins);
-}
-
-int decline(const char* who, const std::string& why) {
-    set_error(std::string(who) + " declined: " + why);
-    return PGH_LINK_DECLINED;
 }
 
 // pool_alloc that turns a failure into a decline
@@ -171,7 +158,7 @@ int scratch(const char* who, size_t bytes, void** p) {
     if (*p != nullptr) return 0;
     if (pool_alloc(bytes > 0 ? bytes : 1, p) != 0) {
         *p = nullptr;
-        return decline(who, "the plan's scratch does not fit in device memory");
+        return declined(PGH_LINK_DECLINED, who, "the plan's scratch does not fit in device memory");
     }
     return 0;
 }
@@ -186,7 +173,7 @@ int check_call(const char* who, pgh_mat_t scores, pgh_link_plan_t plan, int32_t 
 
 int row_sums(const char* who, pgh_mat_t scores, pgh_link_plan_t plan) {
     PGH_TRY(scratch(who, sizeof(double) * (size_t)plan->n, (void**)&plan->l2));
-    k_link_rows<false><<<grid_for(plan->n, kBlock), kBlock, 0, rt().stream>>>(scores->data, plan->n, scores->b, plan->l2, nullptr);
+    k_link_rows<false><<<grid_capped(plan->n, kSlabBlock), kSlabBlock, 0, rt().stream>>>(scores->data, plan->n, scores->b, plan->l2, nullptr);
     PGH_HIP(hipGetLastError());
     return 0;
 }
@@ -287,19 +274,19 @@ extern "C" int pgh_link_auc(pgh_mat_t scores, pgh_link_plan_t plan, int32_t simi
     if (cos) PGH_TRY(row_sums(who, scores, plan));
     PGH_HIP(hipMemsetAsync(plan->result, 0, sizeof(unsigned long long) * 2, r.stream));
     PGH_HIP(hipMemsetAsync(plan->neg_before, 0, sizeof(uint32_t), r.stream));
-    const int grid = grid_for(count, kBlock);
+    const int grid = grid_capped(count, kSlabBlock);
     if (cos)
-        k_link_pairs<true><<<grid, kBlock, 0, r.stream>>>(scores->data, scores->b, plan->l2, plan->first, plan->second, 0, count, plan->key_in, nullptr,
+        k_link_pairs<true><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, scores->b, plan->l2, plan->first, plan->second, 0, count, plan->key_in, nullptr,
                                                           plan->result + 1);
     else
-        k_link_pairs<false><<<grid, kBlock, 0, r.stream>>>(scores->data, scores->b, nullptr, plan->first, plan->second, 0, count, plan->key_in, nullptr,
+        k_link_pairs<false><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, scores->b, nullptr, plan->first, plan->second, 0, count, plan->key_in, nullptr,
                                                            plan->result + 1);
     PGH_HIP(hipGetLastError());
     size_t bytes = plan->temp_bytes;
     PGH_HIP(hipcub::DeviceRadixSort::SortPairs(plan->temp, bytes, plan->key_in, plan->key_out, plan->label, plan->label_out, (int)count, 0, 64, r.stream));
     bytes = plan->temp_bytes;
     PGH_HIP(hipcub::DeviceScan::InclusiveSum(plan->temp, bytes, negatives, plan->neg_before + 1, (int)count, r.stream));
-    k_link_count<<<grid, kBlock, 0, r.stream>>>(plan->key_out, plan->label_out, plan->neg_before, count, plan->result);
+    k_link_count<<<grid, kSlabBlock, 0, r.stream>>>(plan->key_out, plan->label_out, plan->neg_before, count, plan->result);
     PGH_HIP(hipGetLastError());
     unsigned long long host[2] = {0, 0};
     PGH_HIP(hipMemcpyAsync(host, plan->result, sizeof(host), hipMemcpyDeviceToHost, r.stream));
@@ -319,25 +306,19 @@ extern "C" int pgh_link_predictions(pgh_mat_t scores, pgh_link_plan_t plan, int3
     Runtime& r = rt();
     const bool cos = similarity == PGH_LINK_COS;
     if (cos) PGH_TRY(scratch(who, sizeof(double) * (size_t)plan->n, (void**)&plan->l2));
-    double* preds = nullptr;
-    if (pool_alloc(sizeof(double) * (size_t)count, (void**)&preds) != 0) return decline(who, "the predictions do not fit in device memory");
-    hipError_t e = hipSuccess;
-    int rc = cos ? row_sums(who, scores, plan) : 0;
-    if (rc == 0) {
-        const int grid = grid_for(count, kBlock);
-        if (cos)
-            k_link_pairs<true><<<grid, kBlock, 0, r.stream>>>(scores->data, scores->b, plan->l2, plan->first, plan->second, first, count, nullptr, preds, nullptr);
-        else
-            k_link_pairs<false><<<grid, kBlock, 0, r.stream>>>(scores->data, scores->b, nullptr, plan->first, plan->second, first, count, nullptr, preds,
-                                                               nullptr);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out_host, preds, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, r.stream);
-        const hipError_t s = hipStreamSynchronize(r.stream);
-        if (e == hipSuccess) e = s;
-    }
-    pool_free(preds);
-    PGH_TRY(rc);
-    PGH_HIP(e);
+    PoolBuf preds;
+    if (preds.alloc(sizeof(double) * (size_t)count) != 0) return declined(PGH_LINK_DECLINED, who, "the predictions do not fit in device memory");
+    if (cos) PGH_TRY(row_sums(who, scores, plan));
+    const int grid = grid_capped(count, kSlabBlock);
+    if (cos)
+        k_link_pairs<true><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, scores->b, plan->l2, plan->first, plan->second, first, count, nullptr,
+                                                          preds.as<double>(), nullptr);
+    else
+        k_link_pairs<false><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, scores->b, nullptr, plan->first, plan->second, first, count, nullptr,
+                                                           preds.as<double>(), nullptr);
+    PGH_HIP(hipGetLastError());
+    PGH_HIP(hipMemcpyAsync(out_host, preds.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, r.stream));
+    PGH_HIP(hipStreamSynchronize(r.stream));
     return 0;
 }
 
@@ -351,9 +332,9 @@ extern "C" int pgh_link_factors(pgh_mat_t scores, int32_t similarity, pgh_vec_t 
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     if (similarity == PGH_LINK_COS)
-        k_link_rows<true><<<grid_for(n, kBlock), kBlock, 0, r.stream>>>(scores->data, n, scores->b, nullptr, out->data);
+        k_link_rows<true><<<grid_capped(n, kSlabBlock), kSlabBlock, 0, r.stream>>>(scores->data, n, scores->b, nullptr, out->data);
     else
-        k_link_last_column<<<grid_for(n, kBlock), kBlock, 0, r.stream>>>(scores->data, n, scores->b, out->data);
+        k_link_last_column<<<grid_capped(n, kSlabBlock), kSlabBlock, 0, r.stream>>>(scores->data, n, scores->b, out->data);
     PGH_HIP(hipGetLastError());
     return 0;
 }

@@ -10,14 +10,14 @@
 //   pgh_spmm       Y = M^T X, the multi-seed pass as it stands
 //   k_cut_forms    every row of X and Y once: the lanes of a row hold four score columns each (the mapping of k_mat_gemm, pgh_runtime.hip)
 //                  and add y_s x_s, y_s x_c, y_c x_s, y_c x_c into f64 registers
-//   k_fold_parts   the partial sums of the kParts row parts, added in index order
-// A row belongs to part (row / rows per workgroup) % kParts whatever the launch: the grid only decides which workgroup walks which
+//   k_fold_fields  the partial sums of the kSlabParts row parts, added in index order (pgh_slab.h)
+// A row belongs to part (row / rows per workgroup) % kSlabParts whatever the launch: the grid only decides which workgroup walks which
 // parts.  Lanes -> wavefront (shuffles) -> workgroup (LDS, wavefront order) -> parts (index order) are all fixed orders, so the forms
 // are the same bits on every call and for every grid.  No atomics.
 //
 // C = M^T c is computed, not derived as max_rank * (M^T 1) - N: that difference cancels in f32 exactly where Conductance looks, the
 // complement's internal weight <C, c> of a community that nearly fills the graph.
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_measure.h"
 
 #include <cmath>
@@ -25,40 +25,20 @@
 using namespace pgh;
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kParts = 1024;         // row parts of a slab: 256 CUs x 4 workgroups take one each
-constexpr int kMaxCols = 64;
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) pool_free(p);
-    }
-    int alloc(size_t bytes) { return pool_alloc(bytes > 0 ? bytes : 1, &p); }
-    template <typename T>
-    T* as() { return static_cast<T*>(p); }
-};
-
-// the grid comes from the device, not from the rows: every workgroup walks kParts / grid parts
-int parts_grid() {
-    const int g = rt().num_cus * 4;
-    return g < 1 ? 1 : (g > kParts ? kParts : g);
-}
-
 struct ColFactors {
-    float f[kMaxCols];
+    float f[kSlabMaxCols];
 };
 
-// Every virtual thread v < stride of the kParts * kBlock keeps ONE column (the stride is a multiple of b) and walks the slab with it;
-// the threads of a part that share a column are folded through LDS in thread order.  partial: [kParts][b][4] = sum, sum of squares,
+// Every virtual thread v < stride of the kSlabParts * kSlabBlock keeps ONE column (the stride is a multiple of b) and walks the slab with it;
+// the threads of a part that share a column are folded through LDS in thread order.  partial: [kSlabParts][b][4] = sum, sum of squares,
 // max, min.
-__global__ __launch_bounds__(kBlock) void k_col_stats(const float* __restrict__ m, int64_t n, int b, double* __restrict__ partial) {
-    __shared__ double s_sum[kBlock], s_sq[kBlock];
-    __shared__ float s_max[kBlock], s_min[kBlock];
+__global__ __launch_bounds__(kSlabBlock) void k_col_stats(const float* __restrict__ m, int64_t n, int b, double* __restrict__ partial) {
+    __shared__ double s_sum[kSlabBlock], s_sq[kSlabBlock];
+    __shared__ float s_max[kSlabBlock], s_min[kSlabBlock];
     const int64_t total = n * b;
-    const int64_t stride = ((int64_t)kParts * kBlock) / b * b;
-    for (int part = blockIdx.x; part < kParts; part += gridDim.x) {
-        const int64_t first = (int64_t)part * kBlock;
+    const int64_t stride = ((int64_t)kSlabParts * kSlabBlock) / b * b;
+    for (int part = blockIdx.x; part < kSlabParts; part += gridDim.x) {
+        const int64_t first = (int64_t)part * kSlabBlock;
         double sum = 0.0, sq = 0.0;
         float mx = -INFINITY, mn = INFINITY;
         if (first + threadIdx.x < stride) {
@@ -86,11 +66,11 @@ __global__ __launch_bounds__(kBlock) void k_col_stats(const float* __restrict__ 
         s_max[threadIdx.x] = mx;
         s_min[threadIdx.x] = mn;
         __syncthreads();
-        for (int j = threadIdx.x; j < b; j += kBlock) {
+        for (int j = threadIdx.x; j < b; j += kSlabBlock) {
             const int start = (int)(((int64_t)j - first % b + b) % b);     // first thread of this part that owns column j
             double t = 0.0, q = 0.0;
             float hi = -INFINITY, lo = INFINITY;
-            for (int k = start; k < kBlock; k += b) {
+            for (int k = start; k < kSlabBlock; k += b) {
                 t += s_sum[k];
                 q += s_sq[k];
                 hi = fmaxf(hi, s_max[k]);
@@ -106,39 +86,15 @@ __global__ __launch_bounds__(kBlock) void k_col_stats(const float* __restrict__ 
     }
 }
 
-// out[4 j + f] = the parts' partial[.][j][f] in index order: workgroup j, thread (slice k, f) adds parts k, k + 64, ..., then the 64
-// slices are added in slice order.  STATS: f = 2 is a maximum, f = 3 a minimum.
-template <bool STATS>
-__global__ __launch_bounds__(kBlock) void k_fold_parts(const double* __restrict__ partial, int cols, double* __restrict__ out) {
-    __shared__ double s_v[kBlock];
-    const int j = blockIdx.x, f = threadIdx.x & 3, k = threadIdx.x >> 2;
-    const bool is_max = STATS && f == 2, is_min = STATS && f == 3;
-    double acc = is_max ? -INFINITY : (is_min ? INFINITY : 0.0);
-    for (int p = k; p < kParts; p += kBlock / 4) {
-        const double v = partial[((int64_t)p * cols + j) * 4 + f];
-        acc = is_max ? fmax(acc, v) : (is_min ? fmin(acc, v) : acc + v);
-    }
-    s_v[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double r = s_v[f];
-        for (int q = 1; q < kBlock / 4; ++q) {
-            const double v = s_v[q * 4 + f];
-            r = is_max ? fmax(r, v) : (is_min ? fmin(r, v) : r + v);
-        }
-        out[j * 4 + f] = r;
-    }
-}
-
 // X[i, q] = s, X[i, bp + q] = c (BOTH) for the score columns first .. first + bc of `scores` ([n, b], rows of b floats); a thread
 // writes one float4 of either half.  The products and differences are single f32 operations (no contraction into an fma: c is
 // max_rank minus the ROUNDED s, what two vector-scalar calls of the engine store).
 template <bool BOTH>
-__global__ __launch_bounds__(kBlock) void k_cut_pack(const float* __restrict__ scores, int64_t n, int b, int first, int bc, int bp, ColFactors factors,
-                                                      float max_rank, float* __restrict__ X) {
+__global__ __launch_bounds__(kSlabBlock) void k_cut_pack(const float* __restrict__ scores, int64_t n, int b, int first, int bc, int bp, ColFactors factors,
+                                                          float max_rank, float* __restrict__ X) {
     const int quads = bp >> 2, W = BOTH ? 2 * bp : bp;
     const int64_t total = n * quads;
-    for (int64_t w = blockIdx.x * (int64_t)kBlock + threadIdx.x; w < total; w += (int64_t)gridDim.x * kBlock) {
+    for (int64_t w = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; w < total; w += (int64_t)gridDim.x * kSlabBlock) {
         const int64_t i = w / quads;
         const int q0 = (int)(w - i * quads) * 4;
         const float* __restrict__ row = scores + i * b + first;
@@ -160,20 +116,20 @@ __global__ __launch_bounds__(kBlock) void k_cut_pack(const float* __restrict__ s
 // X = [s | c] and Y = M^T X, both [n, W] with W = 2 bp (ALL) or bp (only s, only <N, s>).  lpr lanes (a power of two >= bp / 4) share a row;
 // lane l of them holds the score columns 4 l .. 4 l + 3 and reads its float4 of either half of the row of X and of Y: every element of
 // both slabs is read once, by one lane, as part of a 16-byte word.  The columns bc .. bp - 1 are zeros in X, so is their product.
-// partial: [kParts][bp][4] = <N, s>, <N, c>, <C, s>, <C, c>.
+// partial: [kSlabParts][bp][4] = <N, s>, <N, c>, <C, s>, <C, c>.
 template <bool ALL>
-__global__ __launch_bounds__(kBlock) void k_cut_forms(const float* __restrict__ X, const float* __restrict__ Y, int64_t n, int bp, int lpr,
-                                                       double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_cut_forms(const float* __restrict__ X, const float* __restrict__ Y, int64_t n, int bp, int lpr,
+                                                           double* __restrict__ partial) {
     constexpr int F = ALL ? 4 : 1;
-    __shared__ double s_red[kBlock / 64][16][4 * F];
+    __shared__ double s_red[kSlabBlock / 64][16][4 * F];
     const int W = ALL ? 2 * bp : bp;
-    const int rows = kBlock / lpr;
+    const int rows = kSlabBlock / lpr;
     const int l = threadIdx.x & (lpr - 1), r_in = threadIdx.x / lpr;
     const int q0 = 4 * l;
     const bool live = q0 < bp;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t step = (int64_t)kParts * rows;
-    for (int part = blockIdx.x; part < kParts; part += gridDim.x) {
+    const int64_t step = (int64_t)kSlabParts * rows;
+    for (int part = blockIdx.x; part < kSlabParts; part += gridDim.x) {
         double a[4 * F];
 #pragma unroll
         for (int k = 0; k < 4 * F; ++k) a[k] = 0.0;
@@ -209,13 +165,13 @@ __global__ __launch_bounds__(kBlock) void k_cut_forms(const float* __restrict__ 
             if (lane < lpr) s_red[wave][lane][k] = v;
         }
         __syncthreads();
-        for (int o = threadIdx.x; o < bp * 4; o += kBlock) {
+        for (int o = threadIdx.x; o < bp * 4; o += kSlabBlock) {
             const int col = o >> 2, f = o & 3;
             double r = 0.0;
             if (ALL || f == 0) {
                 const int slot = ALL ? 4 * (col & 3) + f : (col & 3);
 #pragma unroll
-                for (int w = 0; w < kBlock / 64; ++w) r += s_red[w][col >> 2][slot];
+                for (int w = 0; w < kSlabBlock / 64; ++w) r += s_red[w][col >> 2][slot];
             }
             partial[((int64_t)part * bp + col) * 4 + f] = r;
         }
@@ -223,10 +179,7 @@ __global__ __launch_bounds__(kBlock) void k_cut_forms(const float* __restrict__ 
     }
 }
 
-int decline(const std::string& why) {
-    set_error("pgh_cut_forms declined: " + why);
-    return PGH_MEASURE_DECLINED;
-}
+const char* const kCut = "pgh_cut_forms";
 }  // namespace
 
 PGH_WARM_KERNEL(k_col_stats)
@@ -244,15 +197,11 @@ extern "C" int pgh_mat_col_stats(pgh_mat_t m, double* out_host) {
         return 0;
     }
     Runtime& r = rt();
-    DevBuf partial, folded;
-    PGH_TRY(partial.alloc(sizeof(double) * (size_t)kParts * b * 4));
-    PGH_TRY(folded.alloc(sizeof(double) * (size_t)b * 4));
-    k_col_stats<<<parts_grid(), kBlock, 0, r.stream>>>(m->data, m->n, b, partial.as<double>());
-    k_fold_parts<true><<<b, kBlock, 0, r.stream>>>(partial.as<double>(), b, folded.as<double>());
+    PoolBuf partial;
+    PGH_TRY(partial.alloc(sizeof(double) * (size_t)kSlabParts * b * 4));
+    k_col_stats<<<parts_grid(), kSlabBlock, 0, r.stream>>>(m->data, m->n, b, partial.as<double>());
     PGH_HIP(hipGetLastError());
-    PGH_HIP(hipMemcpyAsync(out_host, folded.p, sizeof(double) * (size_t)b * 4, hipMemcpyDeviceToHost, r.stream));
-    PGH_HIP(hipStreamSynchronize(r.stream));
-    return 0;
+    return fold_fields_to_host<fold_kinds(kFoldSum, kFoldSum, kFoldMax, kFoldMin)>(partial.as<double>(), kSlabParts, b, b, out_host);
 }
 
 extern "C" int pgh_cut_forms(pgh_graph_t g, pgh_mat_t scores, const double* factors_host, double max_rank, int32_t forms,
@@ -260,42 +209,40 @@ extern "C" int pgh_cut_forms(pgh_graph_t g, pgh_mat_t scores, const double* fact
     PGH_CHECK(g && scores && out_host, "pgh_cut_forms: null argument");
     PGH_CHECK(forms == PGH_CUT_ALL || forms == PGH_CUT_INTERNAL, "pgh_cut_forms: unknown forms");
     PGH_CHECK(scores->b >= 1, "pgh_cut_forms: at least one column expected");
-    if (scores->b > kMaxCols) return decline("more than 64 columns");
-    if (!std::isfinite((float)max_rank)) return decline("non-finite max_rank");
+    if (scores->b > kSlabMaxCols) return declined(PGH_MEASURE_DECLINED, kCut, "more than 64 columns");
+    if (!std::isfinite((float)max_rank)) return declined(PGH_MEASURE_DECLINED, kCut, "non-finite max_rank");
     const int b = scores->b;
     ColFactors factors;
-    for (int j = 0; j < kMaxCols; ++j) factors.f[j] = 1.f;
+    for (int j = 0; j < kSlabMaxCols; ++j) factors.f[j] = 1.f;
     if (factors_host != nullptr)
         for (int j = 0; j < b; ++j) {
             factors.f[j] = (float)factors_host[j];
-            if (!std::isfinite(factors.f[j])) return decline("non-finite factor");
+            if (!std::isfinite(factors.f[j])) return declined(PGH_MEASURE_DECLINED, kCut, "non-finite factor");
         }
-    if (g->n_rows != g->n_cols) return decline("the multi-seed pass needs a square matrix");
-    if (!g->bsf.enabled || g->part_perm != nullptr) return decline("the graph has no multi-seed layout");
+    if (g->n_rows != g->n_cols) return declined(PGH_MEASURE_DECLINED, kCut, "the multi-seed pass needs a square matrix");
+    if (!g->bsf.enabled || g->part_perm != nullptr) return declined(PGH_MEASURE_DECLINED, kCut, "the graph has no multi-seed layout");
     PGH_CHECK(scores->n == g->n_cols, "pgh_cut_forms: shape mismatch");
     const int64_t n = scores->n;
     const bool all = forms == PGH_CUT_ALL;
-    double result[4 * kMaxCols];
-    for (int k = 0; k < 4 * kMaxCols; ++k) result[k] = 0.0;
+    double result[4 * kSlabMaxCols];
+    for (int k = 0; k < 4 * kSlabMaxCols; ++k) result[k] = 0.0;
     if (n > 0 && g->nnz > 0) {
         Runtime& r = rt();
-        const int per = all ? kMaxCols / 2 : kMaxCols;       // score columns per slab of <= 64
+        const int per = all ? kSlabMaxCols / 2 : kSlabMaxCols;       // score columns per slab of <= 64
         const int bp0 = ((b < per ? b : per) + 3) & ~3;
         const size_t slab = sizeof(float) * (size_t)n * (size_t)(all ? 2 * bp0 : bp0);      // the first chunk is the widest
         // same-sized blocks come back from the runtime's pool on the next call: no allocation after the first
-        DevBuf X, Y, partial, folded;
+        PoolBuf X, Y, partial;
         PGH_TRY(X.alloc(slab));
         PGH_TRY(Y.alloc(slab));
-        PGH_TRY(partial.alloc(sizeof(double) * (size_t)kParts * bp0 * 4));
-        PGH_TRY(folded.alloc(sizeof(double) * (size_t)bp0 * 4));
+        PGH_TRY(partial.alloc(sizeof(double) * (size_t)kSlabParts * bp0 * 4));
         const int grid = parts_grid();
         for (int first = 0; first < b; first += per) {
             const int bc = b - first < per ? b - first : per;
             const int bp = (bc + 3) & ~3, W = all ? 2 * bp : bp;
-            int lpr = 1;
-            while (lpr * 4 < bp) lpr <<= 1;
-            if (all) k_cut_pack<true><<<grid, kBlock, 0, r.stream>>>(scores->data, n, b, first, bc, bp, factors, (float)max_rank, X.as<float>());
-            else k_cut_pack<false><<<grid, kBlock, 0, r.stream>>>(scores->data, n, b, first, bc, bp, factors, (float)max_rank, X.as<float>());
+            const int lpr = lpr_for(bp);
+            if (all) k_cut_pack<true><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, n, b, first, bc, bp, factors, (float)max_rank, X.as<float>());
+            else k_cut_pack<false><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, n, b, first, bc, bp, factors, (float)max_rank, X.as<float>());
             PGH_HIP(hipGetLastError());
             pgh_mat_s mx, my;
             mx.data = X.as<float>();
@@ -303,12 +250,10 @@ extern "C" int pgh_cut_forms(pgh_graph_t g, pgh_mat_t scores, const double* fact
             mx.n = my.n = n;
             mx.b = my.b = W;
             PGH_TRY(pgh_spmm(g, &mx, &my));
-            if (all) k_cut_forms<true><<<grid, kBlock, 0, r.stream>>>(X.as<float>(), Y.as<float>(), n, bp, lpr, partial.as<double>());
-            else k_cut_forms<false><<<grid, kBlock, 0, r.stream>>>(X.as<float>(), Y.as<float>(), n, bp, lpr, partial.as<double>());
-            k_fold_parts<false><<<bc, kBlock, 0, r.stream>>>(partial.as<double>(), bp, folded.as<double>());
+            if (all) k_cut_forms<true><<<grid, kSlabBlock, 0, r.stream>>>(X.as<float>(), Y.as<float>(), n, bp, lpr, partial.as<double>());
+            else k_cut_forms<false><<<grid, kSlabBlock, 0, r.stream>>>(X.as<float>(), Y.as<float>(), n, bp, lpr, partial.as<double>());
             PGH_HIP(hipGetLastError());
-            PGH_HIP(hipMemcpyAsync(result + 4 * first, folded.p, sizeof(double) * (size_t)bc * 4, hipMemcpyDeviceToHost, r.stream));
-            PGH_HIP(hipStreamSynchronize(r.stream));
+            PGH_TRY(fold_fields_to_host<kFoldSums>(partial.as<double>(), kSlabParts, bp, bc, result + 4 * first));
         }
     }
     for (int k = 0; k < 4 * b; ++k) out_host[k] = result[k];

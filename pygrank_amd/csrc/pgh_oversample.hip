@@ -9,19 +9,19 @@
 //   k_seed_resample  ranks (, keep) -> the 0 / 1 slab of the next seeds, per column: ones written
 //   k_boost_forms    seeds, fresh, total -> per column: S1, S2, S3
 //   k_boost_update   total += w[c] * fresh, then min / count of the new total over the mask's ones
-//   k_os_fold        the parts' partial results, in index order
+//   k_fold_fields    the parts' partial results, in index order (pgh_slab.h)
 // Work shape (the scheme of k_col_stats, pgh_measure.hip, on 16-byte words): the slab is a sequence of quads (four consecutive floats);
 // virtual lane v < stride_q takes the quads v, v + stride_q, ... and stride_q is a multiple of b, so slot u of a lane stays on column
-// (4 v + u) % b: four private accumulators per sum, no division in the loop.  A part is kBlock consecutive virtual lanes, whatever the
-// launch; the grid only decides which workgroup walks which parts.  Inside a part the 4 * kBlock slots are folded per column through
-// LDS -- G lanes per column take every G-th slot of that column in slot order, then a halving tree over the G -- and k_os_fold adds
+// (4 v + u) % b: four private accumulators per sum, no division in the loop.  A part is kSlabBlock consecutive virtual lanes, whatever the
+// launch; the grid only decides which workgroup walks which parts.  Inside a part the 4 * kSlabBlock slots are folded per column through
+// LDS -- G lanes per column take every G-th slot of that column in slot order, then a halving tree over the G -- and k_fold_fields adds
 // the parts in index order: every order is fixed by (n, b) alone, so two calls return the same bits for every grid.  No atomics.
 // The last quad of a slab whose n * b is not a multiple of four, and every quad of a slab that is not 16-byte aligned, go element by
 // element under a bounds test.
 // Per-column host arguments (floors, weights) reach the kernels through a pooled device buffer; a lane reads its four once.
 // This file is compiled without contraction into fused multiply-adds (the pragma below), so that total + w * fresh is a rounded
 // product and a rounded sum, as in a plain f64 evaluation.
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_oversample.h"
 
 #include <cmath>
@@ -32,25 +32,15 @@ using namespace pgh;
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kParts = 1024;               // slab parts: 256 CUs x 4 workgroups take one each
-constexpr int kSlots = 4 * kBlock;         // accumulator slots of a part
-constexpr int kMaxCols = PGH_OVERSAMPLE_MAX_COLS;
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) pool_free(p);
-    }
-    int alloc(size_t bytes) { return pool_alloc(bytes > 0 ? bytes : 1, &p); }
-    template <typename T>
-    T* as() { return static_cast<T*>(p); }
-};
+constexpr int kSlots = 4 * kSlabBlock;         // accumulator slots of a part
+static_assert(PGH_OVERSAMPLE_MAX_COLS == kSlabMaxCols, "the per-column host arrays hold kSlabMaxCols entries");
+// the fields of a part's partial result: a minimum or a sum, two sums, the 64-bit count
+constexpr int kMinFirst = fold_kinds(kFoldMin, kFoldSum, kFoldSum, kFoldCount), kSumFirst = fold_kinds(kFoldSum, kFoldSum, kFoldSum, kFoldCount);
 
 struct Shape {
     int64_t total;      // n * b elements
     int64_t quads;      // ceil(total / 4)
-    int64_t stride_q;   // virtual lanes that take quads: kParts * kBlock rounded down to a multiple of b
+    int64_t stride_q;   // virtual lanes that take quads: kSlabParts * kSlabBlock rounded down to a multiple of b
     int     parts;      // parts that hold at least one quad
     int     b;
     int     vec;        // every operand is 16-byte aligned: whole quads travel as one word
@@ -93,7 +83,7 @@ __device__ __forceinline__ void fold_part(const double (&a)[4][ND > 0 ? ND : 1],
     }
     __syncthreads();
     int G = 1;
-    while (2 * G * b <= kBlock) G *= 2;                      // b <= 64: G >= 4
+    while (2 * G * b <= kSlabBlock) G *= 2;                      // b <= 64: G >= 4
     const bool on = t < G * b;
     const int j = t % b, g = t / b;
     double r[ND > 0 ? ND : 1];
@@ -101,8 +91,8 @@ __device__ __forceinline__ void fold_part(const double (&a)[4][ND > 0 ? ND : 1],
     for (int f = 0; f < ND; ++f) r[f] = (MIN0 && f == 0) ? INFINITY : 0.0;
     long long rc = 0;
     if (on) {
-        // slot el of this part is element 4 * part * kBlock + el of the lanes' first quads: its column is (4 * part * kBlock + el) % b
-        const int shift = (int)(((int64_t)4 * part * kBlock) % b);
+        // slot el of this part is element 4 * part * kSlabBlock + el of the lanes' first quads: its column is (4 * part * kSlabBlock + el) % b
+        const int shift = (int)(((int64_t)4 * part * kSlabBlock) % b);
         const int start = ((j - shift) % b + b) % b;
         for (int el = start + g * b; el < kSlots; el += G * b) {
 #pragma unroll
@@ -137,14 +127,14 @@ __device__ __forceinline__ void fold_part(const double (&a)[4][ND > 0 ? ND : 1],
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kBlock) void k_seed_floor(const float* __restrict__ ranks, const float* __restrict__ seeds, Shape s,
-                                                        double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_seed_floor(const float* __restrict__ ranks, const float* __restrict__ seeds, Shape s,
+                                                            double* __restrict__ partial) {
     __shared__ double s_d[kSlots];
     __shared__ long long s_c[kSlots];
     for (int part = blockIdx.x; part < s.parts; part += gridDim.x) {
         double a[4][1] = {{INFINITY}, {INFINITY}, {INFINITY}, {INFINITY}};
         long long c[4] = {0, 0, 0, 0};
-        const int64_t v = (int64_t)part * kBlock + threadIdx.x;
+        const int64_t v = (int64_t)part * kSlabBlock + threadIdx.x;
         if (v < s.stride_q) {
             for (int64_t q = v; q < s.quads; q += s.stride_q) {
                 float r[4], m[4];
@@ -164,14 +154,14 @@ __global__ __launch_bounds__(kBlock) void k_seed_floor(const float* __restrict__
 
 // out may be keep: a quad is read, then written, by the one lane that owns it (no __restrict__ on either)
 template <bool KEEP>
-__global__ __launch_bounds__(kBlock) void k_seed_resample(const float* ranks, const float* __restrict__ floors /* [b] */, int strict,
-                                                           const float* keep, float* out, Shape s, double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_seed_resample(const float* ranks, const float* __restrict__ floors /* [b] */, int strict,
+                                                               const float* keep, float* out, Shape s, double* __restrict__ partial) {
     __shared__ double s_d[kSlots];
     __shared__ long long s_c[kSlots];
     for (int part = blockIdx.x; part < s.parts; part += gridDim.x) {
         double a[4][1] = {{0.0}, {0.0}, {0.0}, {0.0}};
         long long c[4] = {0, 0, 0, 0};
-        const int64_t v = (int64_t)part * kBlock + threadIdx.x;
+        const int64_t v = (int64_t)part * kSlabBlock + threadIdx.x;
         if (v < s.stride_q) {
             float fl[4];
 #pragma unroll
@@ -195,14 +185,14 @@ __global__ __launch_bounds__(kBlock) void k_seed_resample(const float* ranks, co
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_boost_forms(const float* __restrict__ seeds, const float* __restrict__ fresh,
-                                                         const float* __restrict__ total, Shape s, double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_boost_forms(const float* __restrict__ seeds, const float* __restrict__ fresh,
+                                                             const float* __restrict__ total, Shape s, double* __restrict__ partial) {
     __shared__ double s_d[3 * kSlots];
     __shared__ long long s_c[1];
     for (int part = blockIdx.x; part < s.parts; part += gridDim.x) {
         double a[4][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
         const long long c[4] = {0, 0, 0, 0};
-        const int64_t v = (int64_t)part * kBlock + threadIdx.x;
+        const int64_t v = (int64_t)part * kSlabBlock + threadIdx.x;
         if (v < s.stride_q) {
             for (int64_t q = v; q < s.quads; q += s.stride_q) {
                 float m[4], r[4], t[4];
@@ -223,15 +213,15 @@ __global__ __launch_bounds__(kBlock) void k_boost_forms(const float* __restrict_
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_boost_update(float* __restrict__ total, const float* __restrict__ fresh,
-                                                          const double* __restrict__ weights /* [b] */, const float* __restrict__ mask, Shape s,
-                                                          double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_boost_update(float* __restrict__ total, const float* __restrict__ fresh,
+                                                              const double* __restrict__ weights /* [b] */, const float* __restrict__ mask, Shape s,
+                                                              double* __restrict__ partial) {
     __shared__ double s_d[kSlots];
     __shared__ long long s_c[kSlots];
     for (int part = blockIdx.x; part < s.parts; part += gridDim.x) {
         double a[4][1] = {{INFINITY}, {INFINITY}, {INFINITY}, {INFINITY}};
         long long c[4] = {0, 0, 0, 0};
-        const int64_t v = (int64_t)part * kBlock + threadIdx.x;
+        const int64_t v = (int64_t)part * kSlabBlock + threadIdx.x;
         if (v < s.stride_q) {
             double w[4];
 #pragma unroll
@@ -255,68 +245,16 @@ __global__ __launch_bounds__(kBlock) void k_boost_update(float* __restrict__ tot
     }
 }
 
-// out[4 j + f] = the parts' partial[.][j][f] in index order: workgroup j, thread (slice k, f) folds the parts k, k + 64, ..., then the
-// 64 slices are folded in slice order.  Field 0 is a minimum when min0, field 3 a 64-bit integer sum, the others f64 sums.
-__global__ __launch_bounds__(kBlock) void k_os_fold(const double* __restrict__ partial, int parts, int cols, int min0, double* __restrict__ out) {
-    __shared__ double s_v[kBlock];
-    const int j = blockIdx.x, f = threadIdx.x & 3, k = threadIdx.x >> 2;
-    const bool is_min = min0 && f == 0, is_int = f == 3;
-    double acc = is_min ? INFINITY : 0.0;
-    long long cnt = 0;
-    for (int p = k; p < parts; p += kBlock / 4) {
-        const double x = partial[((int64_t)p * cols + j) * 4 + f];
-        if (is_int) cnt += __double_as_longlong(x);
-        else acc = is_min ? fmin(acc, x) : acc + x;
-    }
-    s_v[threadIdx.x] = is_int ? __longlong_as_double(cnt) : acc;
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double r = s_v[f];
-        long long rc = __double_as_longlong(s_v[f]);
-        for (int q = 1; q < kBlock / 4; ++q) {
-            const double x = s_v[q * 4 + f];
-            if (is_int) rc += __double_as_longlong(x);
-            else r = is_min ? fmin(r, x) : r + x;
-        }
-        out[j * 4 + f] = is_int ? __longlong_as_double(rc) : r;
-    }
-}
-
-int decline(const char* who, const std::string& why) {
-    set_error(std::string(who) + " declined: " + why);
-    return PGH_OVERSAMPLE_DECLINED;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 Shape shape_of(int64_t n, int b, bool vec) {
     Shape s;
     s.total = n * b;
     s.quads = (s.total + 3) / 4;
-    s.stride_q = ((int64_t)kParts * kBlock) / b * b;
+    s.stride_q = ((int64_t)kSlabParts * kSlabBlock) / b * b;
     const int64_t lanes = s.quads < s.stride_q ? s.quads : s.stride_q;
-    s.parts = (int)((lanes + kBlock - 1) / kBlock);
+    s.parts = (int)((lanes + kSlabBlock - 1) / kSlabBlock);
     s.b = b;
     s.vec = vec ? 1 : 0;
     return s;
-}
-
-int grid_for(const Shape& s) {
-    const int most = rt().num_cus * 4;
-    const int g = s.parts < most ? s.parts : most;
-    return g < 1 ? 1 : g;
-}
-
-// result[4 c + f] <- the fold of the parts' partial results of every column; waits for the stream
-int fold_to_host(const Shape& s, double* partial, bool min0, double* result /* [4 * b] */) {
-    Runtime& r = rt();
-    DevBuf folded;
-    PGH_TRY(folded.alloc(sizeof(double) * (size_t)s.b * 4));
-    k_os_fold<<<s.b, kBlock, 0, r.stream>>>(partial, s.parts, s.b, min0 ? 1 : 0, folded.as<double>());
-    PGH_HIP(hipGetLastError());
-    PGH_HIP(hipMemcpyAsync(result, folded.p, sizeof(double) * (size_t)s.b * 4, hipMemcpyDeviceToHost, r.stream));
-    PGH_HIP(hipStreamSynchronize(r.stream));
-    return 0;
 }
 
 int64_t count_of(double word) {
@@ -328,14 +266,14 @@ int64_t count_of(double word) {
 bool same_shape(pgh_mat_t a, pgh_mat_t b) { return a->n == b->n && a->b == b->b; }
 }  // namespace
 
-PGH_WARM_KERNEL(k_os_fold)
+PGH_WARM_KERNEL(k_seed_floor)
 
 extern "C" int pgh_seed_floor(pgh_mat_t ranks, pgh_mat_t seeds, double* floor_host, int64_t* count_host) {
     PGH_CHECK(ranks && seeds && floor_host && count_host, "pgh_seed_floor: null argument");
     PGH_CHECK(ranks->b >= 1 && ranks->n >= 0, "pgh_seed_floor: at least one column expected");
     PGH_CHECK(same_shape(ranks, seeds), "pgh_seed_floor: ranks and seeds differ in shape");
     const int b = ranks->b;
-    if (b > kMaxCols) return decline("pgh_seed_floor", "more than 64 columns");
+    if (b > kSlabMaxCols) return declined(PGH_OVERSAMPLE_DECLINED, "pgh_seed_floor", "more than 64 columns");
     if (ranks->n == 0) {
         for (int c = 0; c < b; ++c) {
             floor_host[c] = INFINITY;
@@ -346,12 +284,12 @@ extern "C" int pgh_seed_floor(pgh_mat_t ranks, pgh_mat_t seeds, double* floor_ho
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const Shape s = shape_of(ranks->n, b, aligned16(ranks->data) && aligned16(seeds->data));
-    DevBuf partial;
+    PoolBuf partial;
     PGH_TRY(partial.alloc(sizeof(double) * (size_t)s.parts * b * 4));
-    k_seed_floor<<<grid_for(s), kBlock, 0, r.stream>>>(ranks->data, seeds->data, s, partial.as<double>());
+    k_seed_floor<<<parts_grid(s.parts), kSlabBlock, 0, r.stream>>>(ranks->data, seeds->data, s, partial.as<double>());
     PGH_HIP(hipGetLastError());
-    double result[4 * kMaxCols];
-    PGH_TRY(fold_to_host(s, partial.as<double>(), true, result));
+    double result[4 * kSlabMaxCols];
+    PGH_TRY(fold_fields_to_host<kMinFirst>(partial.as<double>(), s.parts, s.b, s.b, result));
     for (int c = 0; c < b; ++c) {
         floor_host[c] = result[4 * c];
         count_host[c] = count_of(result[4 * c + 3]);
@@ -366,10 +304,10 @@ extern "C" int pgh_seed_resample(pgh_mat_t ranks, const double* floor_host, int3
     PGH_CHECK(same_shape(ranks, out) && (keep == nullptr || same_shape(ranks, keep)), "pgh_seed_resample: the slabs differ in shape");
     PGH_CHECK(ranks->n == 0 || out->data != ranks->data, "pgh_seed_resample: out shares its memory with ranks");
     const int b = ranks->b;
-    if (b > kMaxCols) return decline("pgh_seed_resample", "more than 64 columns");
-    float floors[kMaxCols];
+    if (b > kSlabMaxCols) return declined(PGH_OVERSAMPLE_DECLINED, "pgh_seed_resample", "more than 64 columns");
+    float floors[kSlabMaxCols];
     for (int c = 0; c < b; ++c) {
-        if (!std::isfinite(floor_host[c])) return decline("pgh_seed_resample", "a floor is not finite");
+        if (!std::isfinite(floor_host[c])) return declined(PGH_OVERSAMPLE_DECLINED, "pgh_seed_resample", "a floor is not finite");
         floors[c] = (float)floor_host[c];
     }
     if (ranks->n == 0) {
@@ -379,23 +317,20 @@ extern "C" int pgh_seed_resample(pgh_mat_t ranks, const double* floor_host, int3
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const Shape s = shape_of(ranks->n, b, aligned16(ranks->data) && aligned16(out->data) && (keep == nullptr || aligned16(keep->data)));
-    DevBuf partial, d_floors;
+    PoolBuf partial, d_floors;
     PGH_TRY(partial.alloc(sizeof(double) * (size_t)s.parts * b * 4));
     PGH_TRY(d_floors.alloc(sizeof(float) * (size_t)b));
+    StreamFence fence;                                       // the staged floors go away with this frame
     PGH_HIP(hipMemcpyAsync(d_floors.p, floors, sizeof(float) * (size_t)b, hipMemcpyHostToDevice, r.stream));
+    const int grid = parts_grid(s.parts), strictly = strict != 0 ? 1 : 0;
     if (keep != nullptr)
-        k_seed_resample<true><<<grid_for(s), kBlock, 0, r.stream>>>(ranks->data, d_floors.as<float>(), strict != 0 ? 1 : 0, keep->data, out->data, s,
-                                                                    partial.as<double>());
+        k_seed_resample<true><<<grid, kSlabBlock, 0, r.stream>>>(ranks->data, d_floors.as<float>(), strictly, keep->data, out->data, s, partial.as<double>());
     else
-        k_seed_resample<false><<<grid_for(s), kBlock, 0, r.stream>>>(ranks->data, d_floors.as<float>(), strict != 0 ? 1 : 0, ranks->data, out->data,
-                                                                     s, partial.as<double>());
-    hipError_t e = hipGetLastError();
-    double result[4 * kMaxCols];
-    int rc = 0;
-    if (e == hipSuccess) rc = fold_to_host(s, partial.as<double>(), false, result);   // waits: the staged floors go away with this frame
-    else (void)hipStreamSynchronize(r.stream);
-    if (e != hipSuccess) return fail(std::string("pgh_seed_resample: ") + hipGetErrorString(e));
-    PGH_TRY(rc);
+        k_seed_resample<false><<<grid, kSlabBlock, 0, r.stream>>>(ranks->data, d_floors.as<float>(), strictly, ranks->data, out->data, s, partial.as<double>());
+    PGH_HIP(hipGetLastError());
+    double result[4 * kSlabMaxCols];
+    PGH_TRY(fold_fields_to_host<kSumFirst>(partial.as<double>(), s.parts, s.b, s.b, result));
+    fence.passed = true;                                     // (the fold waited)
     for (int c = 0; c < b; ++c) count_host[c] = count_of(result[4 * c + 3]);
     return 0;
 }
@@ -405,7 +340,7 @@ extern "C" int pgh_boost_forms(pgh_mat_t seeds, pgh_mat_t fresh, pgh_mat_t total
     PGH_CHECK(seeds->b >= 1 && seeds->n >= 0, "pgh_boost_forms: at least one column expected");
     PGH_CHECK(same_shape(seeds, fresh) && same_shape(seeds, total), "pgh_boost_forms: the slabs differ in shape");
     const int b = seeds->b;
-    if (b > kMaxCols) return decline("pgh_boost_forms", "more than 64 columns");
+    if (b > kSlabMaxCols) return declined(PGH_OVERSAMPLE_DECLINED, "pgh_boost_forms", "more than 64 columns");
     if (seeds->n == 0) {
         for (int k = 0; k < 3 * b; ++k) forms_host[k] = 0.0;
         return 0;
@@ -413,12 +348,12 @@ extern "C" int pgh_boost_forms(pgh_mat_t seeds, pgh_mat_t fresh, pgh_mat_t total
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const Shape s = shape_of(seeds->n, b, aligned16(seeds->data) && aligned16(fresh->data) && aligned16(total->data));
-    DevBuf partial;
+    PoolBuf partial;
     PGH_TRY(partial.alloc(sizeof(double) * (size_t)s.parts * b * 4));
-    k_boost_forms<<<grid_for(s), kBlock, 0, r.stream>>>(seeds->data, fresh->data, total->data, s, partial.as<double>());
+    k_boost_forms<<<parts_grid(s.parts), kSlabBlock, 0, r.stream>>>(seeds->data, fresh->data, total->data, s, partial.as<double>());
     PGH_HIP(hipGetLastError());
-    double result[4 * kMaxCols];
-    PGH_TRY(fold_to_host(s, partial.as<double>(), false, result));
+    double result[4 * kSlabMaxCols];
+    PGH_TRY(fold_fields_to_host<kSumFirst>(partial.as<double>(), s.parts, s.b, s.b, result));
     for (int c = 0; c < b; ++c)
         for (int f = 0; f < 3; ++f) forms_host[3 * c + f] = result[4 * c + f];
     return 0;
@@ -432,9 +367,9 @@ extern "C" int pgh_boost_update(pgh_mat_t total, pgh_mat_t fresh, const double* 
     PGH_CHECK(total->n == 0 || (total->data != fresh->data && total->data != mask->data),
               "pgh_boost_update: total shares its memory with fresh or mask");
     const int b = total->b;
-    if (b > kMaxCols) return decline("pgh_boost_update", "more than 64 columns");
+    if (b > kSlabMaxCols) return declined(PGH_OVERSAMPLE_DECLINED, "pgh_boost_update", "more than 64 columns");
     for (int c = 0; c < b; ++c)
-        if (!std::isfinite(weights_host[c])) return decline("pgh_boost_update", "a weight is not finite");
+        if (!std::isfinite(weights_host[c])) return declined(PGH_OVERSAMPLE_DECLINED, "pgh_boost_update", "a weight is not finite");
     if (total->n == 0) {
         for (int c = 0; c < b; ++c) {
             floor_host[c] = INFINITY;
@@ -445,18 +380,16 @@ extern "C" int pgh_boost_update(pgh_mat_t total, pgh_mat_t fresh, const double* 
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const Shape s = shape_of(total->n, b, aligned16(total->data) && aligned16(fresh->data) && aligned16(mask->data));
-    DevBuf partial, d_weights;
+    PoolBuf partial, d_weights;
     PGH_TRY(partial.alloc(sizeof(double) * (size_t)s.parts * b * 4));
     PGH_TRY(d_weights.alloc(sizeof(double) * (size_t)b));
+    StreamFence fence;                                       // the caller's weights may go away
     PGH_HIP(hipMemcpyAsync(d_weights.p, weights_host, sizeof(double) * (size_t)b, hipMemcpyHostToDevice, r.stream));
-    k_boost_update<<<grid_for(s), kBlock, 0, r.stream>>>(total->data, fresh->data, d_weights.as<double>(), mask->data, s, partial.as<double>());
-    hipError_t e = hipGetLastError();
-    double result[4 * kMaxCols];
-    int rc = 0;
-    if (e == hipSuccess) rc = fold_to_host(s, partial.as<double>(), true, result);    // waits: the caller's weights were read by then
-    else (void)hipStreamSynchronize(r.stream);
-    if (e != hipSuccess) return fail(std::string("pgh_boost_update: ") + hipGetErrorString(e));
-    PGH_TRY(rc);
+    k_boost_update<<<parts_grid(s.parts), kSlabBlock, 0, r.stream>>>(total->data, fresh->data, d_weights.as<double>(), mask->data, s, partial.as<double>());
+    PGH_HIP(hipGetLastError());
+    double result[4 * kSlabMaxCols];
+    PGH_TRY(fold_fields_to_host<kMinFirst>(partial.as<double>(), s.parts, s.b, s.b, result));
+    fence.passed = true;                                     // (the fold waited)
     for (int c = 0; c < b; ++c) {
         floor_host[c] = result[4 * c];
         count_host[c] = count_of(result[4 * c + 3]);

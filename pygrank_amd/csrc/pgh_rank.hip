@@ -4,7 +4,7 @@
 // (SpearmanCorrelation: scipy.stats.spearmanr on the host).
 //
 // The plan (pgh_rank_plan_create), once per (known scores, exclude) pair:
-//   k_rank_classify     a class byte per row (0 excluded, 1 kept, 2 kept and relevant), the two counts, the negative flag
+//   k_classify_labels   a class byte per row (0 excluded, 1 kept, 2 kept and relevant), the two counts, the negative flag (pgh_slab.h)
 //   hipcub select       the kept rows and the relevant rows in ascending row order; k_rank_gather takes their known scores
 //   lazily              the kept known scores in descending order (hipcub), d_known by two binary searches per kept row, sum d_known^2
 // pgh_ndcg, streaming route, all on the engine's stream:
@@ -17,15 +17,16 @@
 //   k_ndcg_finish       one workgroup per column: thread t owns a fixed run of entries, a scan over the runs' sums gives every
 //                       pos_v = inclusive prefix of the bins, and the terms are summed in f64 in that fixed order
 // Sorted route and Spearman, per column: k_rank_keys (canonical keys of the kept rows from the strided column), hipcub radix sort of
-// (key, kept position) pairs, k_dcg_parts / k_rho_parts (kParts workgroups whatever the device, element i always with the same lane)
-// and k_fold_parts.
-#include "pgh_common.h"
+// (key, kept position) pairs, k_dcg_parts / k_rho_parts (kRankParts workgroups whatever the device, element i always with the same lane)
+// and k_rank_fold.
+#include "pgh_slab.h"
 #include "pgh_rank.h"
 
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
 #include <cstdint>
+#include <memory>
 
 using namespace pgh;
 
@@ -43,27 +44,8 @@ struct pgh_rank_plan_s {
 };
 
 namespace {
-constexpr int kBlock = 256;
 constexpr int kStreamBlock = 512;
-constexpr int kParts = 256;          // fixed row parts of the f64 sums: the grid of k_dcg_parts / k_rho_parts whatever the device
-constexpr int kMaxCols = 64;
-constexpr int kMaxGrid = 2048;
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) pool_free(p);
-    }
-    int alloc(size_t bytes) { return pool_alloc(bytes > 0 ? bytes : 1, &p); }
-    template <typename T>
-    T* as() { return static_cast<T*>(p); }
-};
-
-inline int grid_for(int64_t items, int per_block) {
-    int64_t g = (items + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    return (int)(g > kMaxGrid ? kMaxGrid : g);
-}
+constexpr int kRankParts = 256;          // fixed row parts of the f64 sums: the grid of k_dcg_parts / k_rho_parts whatever the device
 
 // -0.0 and +0.0 are one score: a radix key would tell them apart
 __device__ __forceinline__ float canonical(float s) { return s == 0.f ? 0.f : s; }
@@ -71,49 +53,25 @@ __device__ __forceinline__ float canonical(float s) { return s == 0.f ? 0.f : s;
 // (a_s, a_r) comes before (b_s, b_r) in a column's order: score descending, row ascending
 __device__ __forceinline__ bool before(float a_s, int32_t a_r, float b_s, int32_t b_r) { return a_s > b_s || (a_s == b_s && a_r < b_r); }
 
-__global__ __launch_bounds__(kBlock) void k_rank_classify(const float* __restrict__ known, const float* __restrict__ exclude, int64_t n,
-                                                           uint8_t* __restrict__ cls, unsigned long long* __restrict__ counts /* kept, relevant, negative */) {
-    unsigned long long kept = 0, rel = 0, neg = 0;
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const bool out = exclude != nullptr && exclude[i] != 0.f;
-        const float k = known[i];
-        const uint8_t c = out ? 0 : (k != 0.f ? 2 : 1);
-        cls[i] = c;
-        kept += c != 0;
-        rel += c == 2;
-        neg += c != 0 && k < 0.f;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        kept += __shfl_down(kept, off, 64);
-        rel += __shfl_down(rel, off, 64);
-        neg += __shfl_down(neg, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (kept) atomicAdd(&counts[0], kept);
-        if (rel) atomicAdd(&counts[1], rel);
-        if (neg) atomicAdd(&counts[2], neg);
-    }
-}
-
 struct ClassAtLeast {
     const uint8_t* cls;
     uint8_t least;
     __host__ __device__ bool operator()(const int32_t& i) const { return cls[i] >= least; }
 };
 
-__global__ __launch_bounds__(kBlock) void k_rank_gather(const float* __restrict__ src, const int32_t* __restrict__ rows, int64_t count, float* __restrict__ out) {
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kBlock) out[i] = canonical(src[rows[i]]);
+__global__ __launch_bounds__(kSlabBlock) void k_rank_gather(const float* __restrict__ src, const int32_t* __restrict__ rows, int64_t count, float* __restrict__ out) {
+    for (int64_t i = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kSlabBlock) out[i] = canonical(src[rows[i]]);
 }
 
-__global__ __launch_bounds__(kBlock) void k_rank_iota(int32_t* __restrict__ p, int64_t count) {
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kBlock) p[i] = (int32_t)i;
+__global__ __launch_bounds__(kSlabBlock) void k_rank_iota(int32_t* __restrict__ p, int64_t count) {
+    for (int64_t i = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kSlabBlock) p[i] = (int32_t)i;
 }
 
 // keys[p] = the canonical score of kept row p in column `col`; a NaN raises the column's flag
-__global__ __launch_bounds__(kBlock) void k_rank_keys(const float* __restrict__ S, int b, int col, const int32_t* __restrict__ kept_row, int64_t count,
-                                                       float* __restrict__ keys, int* __restrict__ nan_flag) {
+__global__ __launch_bounds__(kSlabBlock) void k_rank_keys(const float* __restrict__ S, int b, int col, const int32_t* __restrict__ kept_row, int64_t count,
+                                                           float* __restrict__ keys, int* __restrict__ nan_flag) {
     bool nan = false;
-    for (int64_t p = blockIdx.x * (int64_t)kBlock + threadIdx.x; p < count; p += (int64_t)gridDim.x * kBlock) {
+    for (int64_t p = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; p < count; p += (int64_t)gridDim.x * kSlabBlock) {
         const float s = S[(int64_t)kept_row[p] * b + col];
         nan |= s != s;
         keys[p] = canonical(s);
@@ -134,40 +92,28 @@ __device__ __forceinline__ int64_t count_above(const float* __restrict__ K, int6
 }
 
 // d[p] = lo + hi - count for the value vals[p] among the descending run K (K is a permutation of vals)
-__global__ __launch_bounds__(kBlock) void k_rank_dknown(const float* __restrict__ vals, const float* __restrict__ K, int64_t count, int32_t* __restrict__ d) {
-    for (int64_t p = blockIdx.x * (int64_t)kBlock + threadIdx.x; p < count; p += (int64_t)gridDim.x * kBlock) {
+__global__ __launch_bounds__(kSlabBlock) void k_rank_dknown(const float* __restrict__ vals, const float* __restrict__ K, int64_t count, int32_t* __restrict__ d) {
+    for (int64_t p = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; p < count; p += (int64_t)gridDim.x * kSlabBlock) {
         const float v = vals[p];
         d[p] = (int32_t)(count_above<true>(K, count, v) + count_above<false>(K, count, v) - count);
     }
 }
 
-// ---- f64 sums over fixed parts: element i belongs to lane (i % (kParts * kBlock)) of the kParts workgroups, whatever the device
-__device__ __forceinline__ void part_store(double a, double c, double* __restrict__ partial /* [kParts][2] */) {
-    __shared__ double s_w[kBlock / 64][2];
-    for (int off = 32; off >= 1; off >>= 1) {
-        a += __shfl_down(a, off, 64);
-        c += __shfl_down(c, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_w[threadIdx.x >> 6][0] = a;
-        s_w[threadIdx.x >> 6][1] = c;
-    }
-    __syncthreads();
+// ---- f64 sums over fixed parts: element i belongs to lane (i % (kRankParts * kSlabBlock)) of the kRankParts workgroups, whatever the device
+__device__ __forceinline__ void part_store(double a, double c, double* __restrict__ partial /* [kRankParts][2] */) {
+    __shared__ double s_red[4];
+    a = block_reduce_256<0>(a, s_red);
+    c = block_reduce_256<0>(c, s_red);
     if (threadIdx.x == 0) {
-        double ra = s_w[0][0], rc = s_w[0][1];
-        for (int w = 1; w < kBlock / 64; ++w) {
-            ra += s_w[w][0];
-            rc += s_w[w][1];
-        }
-        partial[2 * blockIdx.x] = ra;
-        partial[2 * blockIdx.x + 1] = rc;
+        partial[2 * blockIdx.x] = a;
+        partial[2 * blockIdx.x + 1] = c;
     }
 }
 
 // sum over i < count of vals[order ? order[i] : i] / log2(i + 2)
-__global__ __launch_bounds__(kBlock) void k_dcg_parts(const float* __restrict__ vals, const int32_t* __restrict__ order, int64_t count, double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_dcg_parts(const float* __restrict__ vals, const int32_t* __restrict__ order, int64_t count, double* __restrict__ partial) {
     double acc = 0.0;
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < count; i += (int64_t)kParts * kBlock) {
+    for (int64_t i = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; i < count; i += (int64_t)kRankParts * kSlabBlock) {
         const float v = vals[order != nullptr ? order[i] : i];
         acc += (double)v / log2((double)i + 2.0);
     }
@@ -175,10 +121,10 @@ __global__ __launch_bounds__(kBlock) void k_dcg_parts(const float* __restrict__ 
 }
 
 // K: a column's keys in descending order, payload: their kept positions; sums d_s d_k and d_s^2.  payload == nullptr: sums d^2 of `dk` alone
-__global__ __launch_bounds__(kBlock) void k_rho_parts(const float* __restrict__ K, const int32_t* __restrict__ payload, const int32_t* __restrict__ dk, int64_t count,
-                                                       double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_rho_parts(const float* __restrict__ K, const int32_t* __restrict__ payload, const int32_t* __restrict__ dk, int64_t count,
+                                                           double* __restrict__ partial) {
     double sk = 0.0, ss = 0.0;
-    for (int64_t p = blockIdx.x * (int64_t)kBlock + threadIdx.x; p < count; p += (int64_t)kParts * kBlock) {
+    for (int64_t p = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; p < count; p += (int64_t)kRankParts * kSlabBlock) {
         if (payload == nullptr) {
             const double d = (double)dk[p];
             ss += d * d;
@@ -192,61 +138,40 @@ __global__ __launch_bounds__(kBlock) void k_rho_parts(const float* __restrict__ 
     part_store(sk, ss, partial);
 }
 
-// out[0], out[1] = the parts' two sums, in part order (one workgroup of kParts threads)
-__global__ __launch_bounds__(kParts) void k_fold_parts(const double* __restrict__ partial, double* __restrict__ out) {
-    __shared__ double s_w[kParts / 64][2];
-    double a = partial[2 * threadIdx.x], c = partial[2 * threadIdx.x + 1];
-    for (int off = 32; off >= 1; off >>= 1) {
-        a += __shfl_down(a, off, 64);
-        c += __shfl_down(c, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_w[threadIdx.x >> 6][0] = a;
-        s_w[threadIdx.x >> 6][1] = c;
-    }
-    __syncthreads();
+// out[0], out[1] = the parts' two sums, in part order (one workgroup, thread t holds part t)
+static_assert(kRankParts == 256, "k_rank_fold is one block_reduce_256");
+__global__ __launch_bounds__(kRankParts) void k_rank_fold(const double* __restrict__ partial, double* __restrict__ out) {
+    __shared__ double s_red[4];
+    const double a = block_reduce_256<0>(partial[2 * threadIdx.x], s_red);
+    const double c = block_reduce_256<0>(partial[2 * threadIdx.x + 1], s_red);
     if (threadIdx.x == 0) {
-        double ra = s_w[0][0], rc = s_w[0][1];
-        for (int w = 1; w < kParts / 64; ++w) {
-            ra += s_w[w][0];
-            rc += s_w[w][1];
-        }
-        out[0] = ra;
-        out[1] = rc;
+        out[0] = a;
+        out[1] = c;
     }
 }
 
 // ---- the streaming route
 // Column j = blockIdx.x: the m relevant rows' (canonical score, relevant index) pairs sorted into the column's order; written as
 // skey / srow / sknown [j][0 .. m).  m <= PGH_RANK_MAX_RELEVANT, padded = a power of two >= m; the pads sort last.
-__global__ __launch_bounds__(kBlock) void k_ndcg_relevant(const float* __restrict__ S, int b, const int32_t* __restrict__ rel_row, const float* __restrict__ rel_known,
-                                                           int m, int padded, float* __restrict__ skey, int32_t* __restrict__ srow, float* __restrict__ sknown) {
+__global__ __launch_bounds__(kSlabBlock) void k_ndcg_relevant(const float* __restrict__ S, int b, const int32_t* __restrict__ rel_row, const float* __restrict__ rel_known,
+                                                               int m, int padded, float* __restrict__ skey, int32_t* __restrict__ srow, float* __restrict__ sknown) {
     __shared__ float s_v[PGH_RANK_MAX_RELEVANT];
     __shared__ int32_t s_r[PGH_RANK_MAX_RELEVANT];
     const int j = blockIdx.x;
-    for (int e = threadIdx.x; e < padded; e += kBlock) {
+    for (int e = threadIdx.x; e < padded; e += kSlabBlock) {
         s_v[e] = e < m ? canonical(S[(int64_t)rel_row[e] * b + j]) : -INFINITY;
         s_r[e] = e < m ? e : 0x7fffffff;
     }
     __syncthreads();
-    for (int size = 2; size <= padded; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < padded; t += kBlock) {
-                const int other = t ^ stride;
-                if (other > t) {
-                    const float a = s_v[t], c = s_v[other];
-                    const int32_t ar = s_r[t], cr = s_r[other];
-                    const bool forward = (t & size) == 0;
-                    if (before(c, cr, a, ar) == forward) {
-                        s_v[t] = c, s_v[other] = a;
-                        s_r[t] = cr, s_r[other] = ar;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int e = threadIdx.x; e < m; e += kBlock) {
+    bitonic_sort_lds<kSlabBlock>(
+        padded, [&](int i, int k) { return before(s_v[i], s_r[i], s_v[k], s_r[k]); },
+        [&](int i, int k) {
+            const float v = s_v[i];
+            const int32_t r = s_r[i];
+            s_v[i] = s_v[k], s_r[i] = s_r[k];
+            s_v[k] = v, s_r[k] = r;
+        });
+    for (int e = threadIdx.x; e < m; e += kSlabBlock) {
         const int32_t r = s_r[e];
         const bool real = r >= 0 && r < m;               // a NaN score leaves the network's output unordered, never out of range
         skey[(int64_t)j * m + e] = s_v[e];
@@ -314,12 +239,12 @@ __global__ __launch_bounds__(kStreamBlock) void k_ndcg_stream(const float* __res
 
 // Column j = blockIdx.x: pos of entry e = bins[j][0] + .. + bins[j][e]; dcg[j] = sum over the entries with pos < k of known / log2(pos + 2).
 // Thread t owns the entries [t * run, t * run + run): a fixed order whatever the launch.
-__global__ __launch_bounds__(kBlock) void k_ndcg_finish(const unsigned int* __restrict__ bins, const float* __restrict__ sknown, int m, int64_t k,
-                                                         double* __restrict__ dcg) {
-    __shared__ unsigned long long s_sum[kBlock];
-    __shared__ double s_w[kBlock / 64];
+__global__ __launch_bounds__(kSlabBlock) void k_ndcg_finish(const unsigned int* __restrict__ bins, const float* __restrict__ sknown, int m, int64_t k,
+                                                             double* __restrict__ dcg) {
+    __shared__ unsigned long long s_sum[kSlabBlock];
+    __shared__ double s_w[kSlabBlock / 64];
     const int j = blockIdx.x;
-    const int run = (m + kBlock - 1) / kBlock;
+    const int run = (m + kSlabBlock - 1) / kSlabBlock;
     const int first = threadIdx.x * run;
     const int stop = first + run < m ? first + run : m;
     const unsigned int* __restrict__ cnt = bins + (int64_t)j * m;
@@ -329,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void k_ndcg_finish(const unsigned int* __re
     __syncthreads();
     if (threadIdx.x == 0) {                                              // exclusive scan of 256 sums
         unsigned long long run_sum = 0;
-        for (int t = 0; t < kBlock; ++t) {
+        for (int t = 0; t < kSlabBlock; ++t) {
             const unsigned long long x = s_sum[t];
             s_sum[t] = run_sum;
             run_sum += x;
@@ -342,19 +267,8 @@ __global__ __launch_bounds__(kBlock) void k_ndcg_finish(const unsigned int* __re
         pos += cnt[e];
         if ((long long)pos < k) acc += (double)sknown[(int64_t)j * m + e] / log2((double)pos + 2.0);
     }
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = s_w[0];
-        for (int w = 1; w < kBlock / 64; ++w) r += s_w[w];
-        dcg[j] = r;
-    }
-}
-
-int decline(const char* entry, const std::string& why) {
-    set_error(std::string(entry) + " declined: " + why);
-    return PGH_RANK_DECLINED;
+    acc = block_reduce_256<0>(acc, s_w);
+    if (threadIdx.x == 0) dcg[j] = acc;
 }
 
 // keys_in -> (keys_out, order) descending and stable: equal keys keep their kept positions ascending
@@ -362,7 +276,7 @@ int sort_pairs_desc(const float* keys_in, float* keys_out, const int32_t* iota, 
     Runtime& r = rt();
     size_t temp_bytes = 0;
     PGH_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, temp_bytes, keys_in, keys_out, iota, order, (int)count, 0, 32, r.stream));
-    DevBuf temp;
+    PoolBuf temp;
     PGH_TRY(temp.alloc(temp_bytes));
     PGH_HIP(hipcub::DeviceRadixSort::SortPairsDescending(temp.p, temp_bytes, keys_in, keys_out, iota, order, (int)count, 0, 32, r.stream));
     return 0;
@@ -372,26 +286,20 @@ int sort_pairs_desc(const float* keys_in, float* keys_out, const int32_t* iota, 
 int ensure_known_desc(pgh_rank_plan_s* plan) {
     if (plan->known_desc != nullptr || plan->n_kept == 0) return 0;
     Runtime& r = rt();
-    float* out = nullptr;
-    PGH_TRY(pool_alloc(sizeof(float) * (size_t)plan->n_kept, (void**)&out));
+    PoolBuf out, temp;
+    PGH_TRY(out.alloc(sizeof(float) * (size_t)plan->n_kept));
     size_t temp_bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortKeysDescending(nullptr, temp_bytes, plan->kept_known, out, (int)plan->n_kept, 0, 32, r.stream);
-    DevBuf temp;
-    int rc = e == hipSuccess ? temp.alloc(temp_bytes) : 0;
-    if (e == hipSuccess && rc == 0)
-        e = hipcub::DeviceRadixSort::SortKeysDescending(temp.p, temp_bytes, plan->kept_known, out, (int)plan->n_kept, 0, 32, r.stream);
-    if (e != hipSuccess || rc != 0) {
-        pool_free(out);
-        return rc != 0 ? rc : fail(std::string("pgh_rank: sorting the known scores: ") + hipGetErrorString(e));
-    }
-    plan->known_desc = out;
+    PGH_HIP(hipcub::DeviceRadixSort::SortKeysDescending(nullptr, temp_bytes, plan->kept_known, out.as<float>(), (int)plan->n_kept, 0, 32, r.stream));
+    PGH_TRY(temp.alloc(temp_bytes));
+    PGH_HIP(hipcub::DeviceRadixSort::SortKeysDescending(temp.p, temp_bytes, plan->kept_known, out.as<float>(), (int)plan->n_kept, 0, 32, r.stream));
+    plan->known_desc = out.release<float>();
     return 0;
 }
 
-// partial (kParts x 2 doubles) folded into two host doubles
+// partial (kRankParts x 2 doubles) folded into two host doubles
 int fold_to_host(double* partial, double* folded, double* host2) {
     Runtime& r = rt();
-    k_fold_parts<<<1, kParts, 0, r.stream>>>(partial, folded);
+    k_rank_fold<<<1, kRankParts, 0, r.stream>>>(partial, folded);
     PGH_HIP(hipGetLastError());
     PGH_HIP(hipMemcpyAsync(host2, folded, sizeof(double) * 2, hipMemcpyDeviceToHost, r.stream));
     PGH_HIP(hipStreamSynchronize(r.stream));
@@ -403,22 +311,15 @@ int ensure_d_known(pgh_rank_plan_s* plan) {
     PGH_TRY(ensure_known_desc(plan));
     Runtime& r = rt();
     const int64_t count = plan->n_kept;
-    int32_t* d = nullptr;
-    PGH_TRY(pool_alloc(sizeof(int32_t) * (size_t)count, (void**)&d));
-    DevBuf partial, folded;
-    int rc = partial.alloc(sizeof(double) * 2 * kParts);
-    if (rc == 0) rc = folded.alloc(sizeof(double) * 2);
+    PoolBuf d, partial, folded;
+    PGH_TRY(d.alloc(sizeof(int32_t) * (size_t)count));
+    PGH_TRY(partial.alloc(sizeof(double) * 2 * kRankParts));
+    PGH_TRY(folded.alloc(sizeof(double) * 2));
     double host2[2] = {0.0, 0.0};
-    if (rc == 0) {
-        k_rank_dknown<<<grid_for(count, kBlock), kBlock, 0, r.stream>>>(plan->kept_known, plan->known_desc, count, d);
-        k_rho_parts<<<kParts, kBlock, 0, r.stream>>>(nullptr, nullptr, d, count, partial.as<double>());
-        rc = fold_to_host(partial.as<double>(), folded.as<double>(), host2);
-    }
-    if (rc != 0) {
-        pool_free(d);
-        return rc;
-    }
-    plan->d_known = d;
+    k_rank_dknown<<<grid_capped(count, kSlabBlock), kSlabBlock, 0, r.stream>>>(plan->kept_known, plan->known_desc, count, d.as<int32_t>());
+    k_rho_parts<<<kRankParts, kSlabBlock, 0, r.stream>>>(nullptr, nullptr, d.as<int32_t>(), count, partial.as<double>());
+    PGH_TRY(fold_to_host(partial.as<double>(), folded.as<double>(), host2));
+    plan->d_known = d.release<int32_t>();
     plan->sum_dk2 = host2[1];
     return 0;
 }
@@ -437,20 +338,20 @@ int ndcg_streaming(pgh_mat_t scores, pgh_rank_plan_s* plan, int64_t k, double* d
     int padded = 1;
     while (padded < m) padded <<= 1;
     const size_t cells = (size_t)b * m;
-    DevBuf skey, srow, sknown, bins, flags, dcg;
+    PoolBuf skey, srow, sknown, bins, flags, dcg;
     PGH_TRY(skey.alloc(sizeof(float) * cells));
     PGH_TRY(srow.alloc(sizeof(int32_t) * cells));
     PGH_TRY(sknown.alloc(sizeof(float) * cells));
     PGH_TRY(bins.alloc(sizeof(unsigned int) * cells));
-    PGH_TRY(flags.alloc(sizeof(int) * kMaxCols));
-    PGH_TRY(dcg.alloc(sizeof(double) * kMaxCols));
+    PGH_TRY(flags.alloc(sizeof(int) * kSlabMaxCols));
+    PGH_TRY(dcg.alloc(sizeof(double) * kSlabMaxCols));
     PGH_HIP(hipMemsetAsync(bins.p, 0, sizeof(unsigned int) * cells, r.stream));
-    PGH_HIP(hipMemsetAsync(flags.p, 0, sizeof(int) * kMaxCols, r.stream));
-    k_ndcg_relevant<<<b, kBlock, 0, r.stream>>>(scores->data, b, plan->rel_row, plan->rel_known, m, padded, skey.as<float>(), srow.as<int32_t>(),
+    PGH_HIP(hipMemsetAsync(flags.p, 0, sizeof(int) * kSlabMaxCols, r.stream));
+    k_ndcg_relevant<<<b, kSlabBlock, 0, r.stream>>>(scores->data, b, plan->rel_row, plan->rel_known, m, padded, skey.as<float>(), srow.as<int32_t>(),
                                                  sknown.as<float>());
     const size_t lds_all = 8 * cells;
     const bool in_lds = lds_all <= PGH_RANK_LDS_BYTES;
-    int grid = grid_for(n * b, kStreamBlock);
+    int grid = grid_capped(n * b, kStreamBlock);
     const int cap = r.num_cus * (in_lds ? 2 : 4);
     if (grid > cap) grid = cap;
     if (in_lds)
@@ -459,10 +360,10 @@ int ndcg_streaming(pgh_mat_t scores, pgh_rank_plan_s* plan, int64_t k, double* d
     else
         k_ndcg_stream<false><<<grid, kStreamBlock, 0, r.stream>>>(scores->data, n, b, plan->cls, skey.as<float>(), srow.as<int32_t>(), m,
                                                                    bins.as<unsigned int>(), flags.as<int>());
-    k_ndcg_finish<<<b, kBlock, 0, r.stream>>>(bins.as<unsigned int>(), sknown.as<float>(), m, k, dcg.as<double>());
+    k_ndcg_finish<<<b, kSlabBlock, 0, r.stream>>>(bins.as<unsigned int>(), sknown.as<float>(), m, k, dcg.as<double>());
     PGH_HIP(hipGetLastError());
-    int host_flags[kMaxCols];
-    double host_dcg[kMaxCols];
+    int host_flags[kSlabMaxCols];
+    double host_dcg[kSlabMaxCols];
     PGH_HIP(hipMemcpyAsync(host_flags, flags.p, sizeof(int) * b, hipMemcpyDeviceToHost, r.stream));
     PGH_HIP(hipMemcpyAsync(host_dcg, dcg.p, sizeof(double) * b, hipMemcpyDeviceToHost, r.stream));
     PGH_HIP(hipStreamSynchronize(r.stream));
@@ -472,7 +373,7 @@ int ndcg_streaming(pgh_mat_t scores, pgh_rank_plan_s* plan, int64_t k, double* d
 
 // what the sorted route and Spearman share: per column the canonical keys of the kept rows, sorted descending with their kept positions
 struct ColumnSorter {
-    DevBuf keys, sorted, iota, order, partial, folded, flag;
+    PoolBuf keys, sorted, iota, order, partial, folded, flag;
     int64_t count = 0;
     int prepare(int64_t kept) {
         count = kept;
@@ -480,17 +381,17 @@ struct ColumnSorter {
         PGH_TRY(sorted.alloc(sizeof(float) * (size_t)kept));
         PGH_TRY(iota.alloc(sizeof(int32_t) * (size_t)kept));
         PGH_TRY(order.alloc(sizeof(int32_t) * (size_t)kept));
-        PGH_TRY(partial.alloc(sizeof(double) * 2 * kParts));
+        PGH_TRY(partial.alloc(sizeof(double) * 2 * kRankParts));
         PGH_TRY(folded.alloc(sizeof(double) * 2));
         PGH_TRY(flag.alloc(sizeof(int)));
-        k_rank_iota<<<grid_for(kept, kBlock), kBlock, 0, rt().stream>>>(iota.as<int32_t>(), kept);
+        k_rank_iota<<<grid_capped(kept, kSlabBlock), kSlabBlock, 0, rt().stream>>>(iota.as<int32_t>(), kept);
         PGH_HIP(hipGetLastError());
         return 0;
     }
     int sort_column(pgh_mat_t scores, const pgh_rank_plan_s* plan, int col) {
         Runtime& r = rt();
         PGH_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), r.stream));
-        k_rank_keys<<<grid_for(count, kBlock), kBlock, 0, r.stream>>>(scores->data, scores->b, col, plan->kept_row, count, keys.as<float>(), flag.as<int>());
+        k_rank_keys<<<grid_capped(count, kSlabBlock), kSlabBlock, 0, r.stream>>>(scores->data, scores->b, col, plan->kept_row, count, keys.as<float>(), flag.as<int>());
         PGH_HIP(hipGetLastError());
         return sort_pairs_desc(keys.as<float>(), sorted.as<float>(), iota.as<int32_t>(), order.as<int32_t>(), count);
     }
@@ -509,7 +410,7 @@ int ndcg_sorted(pgh_mat_t scores, pgh_rank_plan_s* plan, int64_t k, double* dcg_
     PGH_TRY(sorter.prepare(plan->n_kept));
     for (int j = 0; j < scores->b; ++j) {
         PGH_TRY(sorter.sort_column(scores, plan, j));
-        k_dcg_parts<<<kParts, kBlock, 0, r.stream>>>(plan->kept_known, sorter.order.as<int32_t>(), top, sorter.partial.as<double>());
+        k_dcg_parts<<<kRankParts, kSlabBlock, 0, r.stream>>>(plan->kept_known, sorter.order.as<int32_t>(), top, sorter.partial.as<double>());
         double host2[2];
         int nan = 0;
         PGH_TRY(sorter.finish(host2, &nan));
@@ -523,27 +424,27 @@ int ndcg_impl(pgh_mat_t scores, pgh_rank_plan_t plan, int64_t k, int32_t route, 
     PGH_CHECK(dcg_host && idcg_host, "pgh_ndcg: null argument");
     PGH_CHECK(k >= 1, "pgh_ndcg: k >= 1 expected");
     PGH_CHECK(route == PGH_RANK_AUTO || route == PGH_RANK_STREAMING || route == PGH_RANK_SORTED, "pgh_ndcg: unknown route");
-    if (scores->b > kMaxCols) return decline("pgh_ndcg", "more than 64 columns");
+    if (scores->b > kSlabMaxCols) return declined(PGH_RANK_DECLINED, "pgh_ndcg", "more than 64 columns");
     const bool too_many = plan->n_rel > PGH_RANK_MAX_RELEVANT;
     bool streaming = route != PGH_RANK_SORTED;
     if (streaming && (too_many || plan->has_negative)) {
         if (route == PGH_RANK_STREAMING)
-            return decline("pgh_ndcg", too_many ? "more relevant rows than the per-column sort holds" : "a negative known score");
+            return declined(PGH_RANK_DECLINED, "pgh_ndcg", too_many ? "more relevant rows than the per-column sort holds" : "a negative known score");
         streaming = false;
     }
     PGH_TRY(ensure_init());
-    double dcg[kMaxCols];
+    double dcg[kSlabMaxCols];
     double idcg = 0.0;
     if (plan->n_rel == 0) {
         for (int j = 0; j < scores->b; ++j) dcg[j] = 0.0;
     } else {
         PGH_TRY(ensure_known_desc(plan));
         Runtime& r = rt();
-        DevBuf partial, folded;
-        PGH_TRY(partial.alloc(sizeof(double) * 2 * kParts));
+        PoolBuf partial, folded;
+        PGH_TRY(partial.alloc(sizeof(double) * 2 * kRankParts));
         PGH_TRY(folded.alloc(sizeof(double) * 2));
         const int64_t top = k < plan->n_kept ? k : plan->n_kept;
-        k_dcg_parts<<<kParts, kBlock, 0, r.stream>>>(plan->known_desc, nullptr, top, partial.as<double>());
+        k_dcg_parts<<<kRankParts, kSlabBlock, 0, r.stream>>>(plan->known_desc, nullptr, top, partial.as<double>());
         double host2[2];
         PGH_TRY(fold_to_host(partial.as<double>(), folded.as<double>(), host2));
         idcg = host2[0];
@@ -557,9 +458,9 @@ int ndcg_impl(pgh_mat_t scores, pgh_rank_plan_t plan, int64_t k, int32_t route, 
 int spearman_impl(pgh_mat_t scores, pgh_rank_plan_t plan, double* rho_host) {
     PGH_TRY(check_slab("pgh_spearman", scores, plan));
     PGH_CHECK(rho_host, "pgh_spearman: null argument");
-    if (scores->b > kMaxCols) return decline("pgh_spearman", "more than 64 columns");
+    if (scores->b > kSlabMaxCols) return declined(PGH_RANK_DECLINED, "pgh_spearman", "more than 64 columns");
     PGH_TRY(ensure_init());
-    double rho[kMaxCols];
+    double rho[kSlabMaxCols];
     if (plan->n_kept == 0) {
         for (int j = 0; j < scores->b; ++j) rho[j] = (double)NAN;
     } else {
@@ -569,7 +470,7 @@ int spearman_impl(pgh_mat_t scores, pgh_rank_plan_t plan, double* rho_host) {
         PGH_TRY(sorter.prepare(plan->n_kept));
         for (int j = 0; j < scores->b; ++j) {
             PGH_TRY(sorter.sort_column(scores, plan, j));
-            k_rho_parts<<<kParts, kBlock, 0, r.stream>>>(sorter.sorted.as<float>(), sorter.order.as<int32_t>(), plan->d_known, plan->n_kept,
+            k_rho_parts<<<kRankParts, kSlabBlock, 0, r.stream>>>(sorter.sorted.as<float>(), sorter.order.as<int32_t>(), plan->d_known, plan->n_kept,
                                                           sorter.partial.as<double>());
             double host2[2];
             int nan = 0;
@@ -582,7 +483,7 @@ int spearman_impl(pgh_mat_t scores, pgh_rank_plan_t plan, double* rho_host) {
 }
 }  // namespace
 
-PGH_WARM_KERNEL(k_rank_classify)
+PGH_WARM_KERNEL(k_rank_fold)
 
 extern "C" int pgh_rank_plan_destroy(pgh_rank_plan_t plan) {
     if (!plan) return 0;
@@ -600,57 +501,40 @@ extern "C" int pgh_rank_plan_create(pgh_vec_t known, pgh_vec_t exclude, pgh_rank
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const int64_t n = known->n;
-    pgh_rank_plan_s* plan = new pgh_rank_plan_s();
+    std::unique_ptr<pgh_rank_plan_s, int (*)(pgh_rank_plan_t)> plan(new pgh_rank_plan_s(), pgh_rank_plan_destroy);
     plan->n = n;
     if (n == 0) {
-        *out = plan;
+        *out = plan.release();
         return 0;
     }
-    DevBuf counts, selected;
-    int rc = counts.alloc(sizeof(unsigned long long) * 3);
-    if (rc == 0) rc = selected.alloc(sizeof(int));
-    if (rc == 0) rc = pool_alloc((size_t)n, (void**)&plan->cls);
-    unsigned long long host[3] = {0, 0, 0};
-    hipError_t e = hipSuccess;
-    if (rc == 0) {
-        e = hipMemsetAsync(counts.p, 0, sizeof(unsigned long long) * 3, r.stream);
-        if (e == hipSuccess) {
-            k_rank_classify<<<grid_for(n, kBlock * 8), kBlock, 0, r.stream>>>(known->data, exclude ? exclude->data : nullptr, n, plan->cls,
-                                                                               counts.as<unsigned long long>());
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(host, counts.p, sizeof(host), hipMemcpyDeviceToHost, r.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(r.stream);
-    }
-    if (rc == 0 && e == hipSuccess) {
-        plan->n_kept = (int64_t)host[0];
-        plan->n_rel = (int64_t)host[1];
-        plan->has_negative = host[2] != 0 ? 1 : 0;
-        // the rows of class >= least in ascending row order, and their known scores
-        auto list_rows = [&](uint8_t least, int64_t count, int32_t** rows, float** values) -> int {
-            if (count == 0) return 0;
-            PGH_TRY(pool_alloc(sizeof(int32_t) * (size_t)count, (void**)rows));
-            PGH_TRY(pool_alloc(sizeof(float) * (size_t)count, (void**)values));
-            hipcub::CountingInputIterator<int32_t> ids(0);
-            const ClassAtLeast keep{plan->cls, least};
-            size_t temp_bytes = 0;
-            PGH_HIP(hipcub::DeviceSelect::If(nullptr, temp_bytes, ids, *rows, selected.as<int>(), (int)n, keep, r.stream));
-            DevBuf temp;
-            PGH_TRY(temp.alloc(temp_bytes));
-            PGH_HIP(hipcub::DeviceSelect::If(temp.p, temp_bytes, ids, *rows, selected.as<int>(), (int)n, keep, r.stream));
-            k_rank_gather<<<grid_for(count, kBlock), kBlock, 0, r.stream>>>(known->data, *rows, count, *values);
-            PGH_HIP(hipGetLastError());
-            PGH_HIP(hipStreamSynchronize(r.stream));
-            return 0;
-        };
-        rc = list_rows(1, plan->n_kept, &plan->kept_row, &plan->kept_known);
-        if (rc == 0) rc = list_rows(2, plan->n_rel, &plan->rel_row, &plan->rel_known);
-    }
-    if (rc != 0 || e != hipSuccess) {
-        pgh_rank_plan_destroy(plan);
-        return e != hipSuccess ? fail(std::string("pgh_rank_plan_create: ") + hipGetErrorString(e)) : rc;
-    }
-    *out = plan;
+    PoolBuf selected;
+    PGH_TRY(selected.alloc(sizeof(int)));
+    PGH_TRY(pool_alloc((size_t)n, (void**)&plan->cls));
+    unsigned long long counts[4];
+    PGH_TRY(classify_labels(known, exclude, plan->cls, counts));
+    plan->n_kept = (int64_t)counts[0];
+    plan->n_rel = (int64_t)counts[1];
+    plan->has_negative = counts[3] != 0 ? 1 : 0;
+    // the rows of class >= least in ascending row order, and their known scores
+    auto list_rows = [&](uint8_t least, int64_t count, int32_t** rows, float** values) -> int {
+        if (count == 0) return 0;
+        PGH_TRY(pool_alloc(sizeof(int32_t) * (size_t)count, (void**)rows));
+        PGH_TRY(pool_alloc(sizeof(float) * (size_t)count, (void**)values));
+        hipcub::CountingInputIterator<int32_t> ids(0);
+        const ClassAtLeast keep{plan->cls, least};
+        size_t temp_bytes = 0;
+        PGH_HIP(hipcub::DeviceSelect::If(nullptr, temp_bytes, ids, *rows, selected.as<int>(), (int)n, keep, r.stream));
+        PoolBuf temp;
+        PGH_TRY(temp.alloc(temp_bytes));
+        PGH_HIP(hipcub::DeviceSelect::If(temp.p, temp_bytes, ids, *rows, selected.as<int>(), (int)n, keep, r.stream));
+        k_rank_gather<<<grid_capped(count, kSlabBlock), kSlabBlock, 0, r.stream>>>(known->data, *rows, count, *values);
+        PGH_HIP(hipGetLastError());
+        PGH_HIP(hipStreamSynchronize(r.stream));
+        return 0;
+    };
+    PGH_TRY(list_rows(1, plan->n_kept, &plan->kept_row, &plan->kept_known));
+    PGH_TRY(list_rows(2, plan->n_rel, &plan->rel_row, &plan->rel_known));
+    *out = plan.release();
     return 0;
 }
 

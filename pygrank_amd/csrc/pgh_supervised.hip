@@ -7,7 +7,7 @@
 //   k_pair_rows    b a multiple of 4: the lanes of a row hold four score columns each (the mapping of k_mat_gemm, pgh_runtime.hip, and
 //                  k_cut_forms, pgh_measure.hip) and read them as one 16-byte word; every element of the slab is read once
 //   k_pair_cols    every other b: a thread keeps ONE column and walks the slab with it (the mapping of k_col_stats, pgh_measure.hip)
-//   k_pair_fold    the partial slots of the kParts row parts, folded in a fixed order
+//   k_pair_fold    the partial slots of the kSlabParts row parts, folded in a fixed order
 // Known scores and exclude values are addressed through a (row stride, column stride) pair -- (1, 0) for a vector shared by the
 // columns, (b, 1) for a matrix -- so one kernel body serves a vector, a matrix or (exclude) nothing.  A shared vector is read once
 // per row: by the one lane group (k_pair_rows) or by the b threads (k_pair_cols, one 4-byte word of a line they all hit) that hold
@@ -18,7 +18,7 @@
 // A row belongs to a part whatever the launch: the grid only decides which workgroup walks which parts.  Lanes -> wavefront
 // (shuffles) -> workgroup (LDS, wavefront order) -> parts (k_pair_fold) are all fixed orders, so the slots are the same bits on every
 // call and for every grid.  No atomics.
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_supervised.h"
 
 #include <cmath>
@@ -27,29 +27,10 @@
 using namespace pgh;
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kParts = 1024;         // row parts of a slab: 256 CUs x 4 workgroups take one each
-constexpr int kMaxCols = 64;
 constexpr int kMoments = 12, kAll = 17;     // slots the two instantiations accumulate
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) pool_free(p);
-    }
-    int alloc(size_t bytes) { return pool_alloc(bytes > 0 ? bytes : 1, &p); }
-    template <typename T>
-    T* as() { return static_cast<T*>(p); }
-};
-
-// the grid comes from the device, not from the rows: every workgroup walks kParts / grid parts
-int parts_grid() {
-    const int g = rt().num_cus * 4;
-    return g < 1 ? 1 : (g > kParts ? kParts : g);
-}
-
 struct PairFactors {
-    double f[kMaxCols];
+    double f[kSlabMaxCols];
 };
 
 // known or exclude: element (i, j) is at data[i * rs + j * cs]; data == nullptr (exclude only): nothing is excluded
@@ -110,22 +91,22 @@ __device__ __forceinline__ void slots_add(double (&a)[NS], double s, double k, d
 }
 
 // lpr lanes (a power of two >= b / 4, at most 16) share a row; lane l of them holds the score columns 4 l .. 4 l + 3.  Part p owns the
-// rows i with (i / rows per workgroup) % kParts == p.  partial: [kParts][b][NS].
+// rows i with (i / rows per workgroup) % kSlabParts == p.  partial: [kSlabParts][b][NS].
 template <bool LOGS>
-__global__ __launch_bounds__(kBlock) void k_pair_rows(const float* __restrict__ S, int64_t n, int b, int lpr, Operand known, Operand exclude,
-                                                       PairFactors factors, double eps, double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_pair_rows(const float* __restrict__ S, int64_t n, int b, int lpr, Operand known, Operand exclude,
+                                                           PairFactors factors, double eps, double* __restrict__ partial) {
     constexpr int NS = LOGS ? kAll : kMoments;
-    __shared__ double s_red[kBlock / 64][16][4 * NS];
-    const int rows = kBlock / lpr;
+    __shared__ double s_red[kSlabBlock / 64][16][4 * NS];
+    const int rows = kSlabBlock / lpr;
     const int l = threadIdx.x & (lpr - 1), r_in = threadIdx.x / lpr;
     const int q0 = 4 * l;
     const bool live = q0 < b;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t step = (int64_t)kParts * rows;
+    const int64_t step = (int64_t)kSlabParts * rows;
     double fac[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) fac[u] = live ? factors.f[q0 + u] : 1.0;
-    for (int part = blockIdx.x; part < kParts; part += gridDim.x) {
+    for (int part = blockIdx.x; part < kSlabParts; part += gridDim.x) {
         double a[4][NS];
 #pragma unroll
         for (int u = 0; u < 4; ++u) slots_clear(a[u]);
@@ -171,29 +152,29 @@ __global__ __launch_bounds__(kBlock) void k_pair_rows(const float* __restrict__ 
             }
         }
         __syncthreads();
-        for (int o = threadIdx.x; o < b * NS; o += kBlock) {
+        for (int o = threadIdx.x; o < b * NS; o += kSlabBlock) {
             const int col = o / NS, f = o - col * NS;
             double r = s_red[0][col >> 2][(col & 3) * NS + f];
 #pragma unroll
-            for (int w = 1; w < kBlock / 64; ++w) r = slot_join(f, r, s_red[w][col >> 2][(col & 3) * NS + f]);
+            for (int w = 1; w < kSlabBlock / 64; ++w) r = slot_join(f, r, s_red[w][col >> 2][(col & 3) * NS + f]);
             partial[((int64_t)part * b + col) * NS + f] = r;
         }
         __syncthreads();
     }
 }
 
-// Every virtual thread v < stride of the kParts * kBlock keeps ONE column (the stride is a multiple of b) and walks the slab with it;
-// the threads of a part that share a column are folded through LDS in thread order, one slot at a time.  partial: [kParts][b][NS].
+// Every virtual thread v < stride of the kSlabParts * kSlabBlock keeps ONE column (the stride is a multiple of b) and walks the slab with it;
+// the threads of a part that share a column are folded through LDS in thread order, one slot at a time.  partial: [kSlabParts][b][NS].
 template <bool LOGS>
-__global__ __launch_bounds__(kBlock) void k_pair_cols(const float* __restrict__ S, int64_t n, int b, Operand known, Operand exclude,
-                                                       PairFactors factors, double eps, double* __restrict__ partial) {
+__global__ __launch_bounds__(kSlabBlock) void k_pair_cols(const float* __restrict__ S, int64_t n, int b, Operand known, Operand exclude,
+                                                           PairFactors factors, double eps, double* __restrict__ partial) {
     constexpr int NS = LOGS ? kAll : kMoments;
-    __shared__ double s_v[kBlock];
+    __shared__ double s_v[kSlabBlock];
     const int64_t total = n * b;
-    const int64_t stride = ((int64_t)kParts * kBlock) / b * b;
+    const int64_t stride = ((int64_t)kSlabParts * kSlabBlock) / b * b;
     const int64_t row_step = stride / b;
-    for (int part = blockIdx.x; part < kParts; part += gridDim.x) {
-        const int64_t first = (int64_t)part * kBlock;
+    for (int part = blockIdx.x; part < kSlabParts; part += gridDim.x) {
+        const int64_t first = (int64_t)part * kSlabBlock;
         const int64_t v = first + threadIdx.x;
         double a[NS];
         slots_clear(a);
@@ -222,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_cols(const float* __restrict__ 
             __syncthreads();
             if (threadIdx.x < b) {
                 double r = s_v[start];
-                for (int k = start + b; k < kBlock; k += b) r = slot_join(f, r, s_v[k]);
+                for (int k = start + b; k < kSlabBlock; k += b) r = slot_join(f, r, s_v[k]);
                 partial[((int64_t)part * b + threadIdx.x) * NS + f] = r;
             }
             __syncthreads();
@@ -232,18 +213,18 @@ __global__ __launch_bounds__(kBlock) void k_pair_cols(const float* __restrict__ 
 
 // out[PGH_PAIR_SLOTS j + f] = the parts' partial[.][j][f]: workgroup j; per slot, thread t joins the parts t, t + 256, ... in index
 // order, a wavefront joins its lanes with shuffles, and the wavefronts are joined in wavefront order.  The slots ns .. 19 are zeros.
-__global__ __launch_bounds__(kBlock) void k_pair_fold(const double* __restrict__ partial, int cols, int ns, double* __restrict__ out) {
-    __shared__ double s_w[kBlock / 64];
+__global__ __launch_bounds__(kSlabBlock) void k_pair_fold(const double* __restrict__ partial, int cols, int ns, double* __restrict__ out) {
+    __shared__ double s_w[kSlabBlock / 64];
     const int j = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int f = 0; f < ns; ++f) {
         double acc = partial[((int64_t)threadIdx.x * cols + j) * ns + f];
-        for (int p = threadIdx.x + kBlock; p < kParts; p += kBlock) acc = slot_join(f, acc, partial[((int64_t)p * cols + j) * ns + f]);
+        for (int p = threadIdx.x + kSlabBlock; p < kSlabParts; p += kSlabBlock) acc = slot_join(f, acc, partial[((int64_t)p * cols + j) * ns + f]);
         for (int off = 32; off >= 1; off >>= 1) acc = slot_join(f, acc, __shfl_down(acc, off, 64));
         if (lane == 0) s_w[wave] = acc;
         __syncthreads();
         if (threadIdx.x == 0) {
             double r = s_w[0];
-            for (int w = 1; w < kBlock / 64; ++w) r = slot_join(f, r, s_w[w]);
+            for (int w = 1; w < kSlabBlock / 64; ++w) r = slot_join(f, r, s_w[w]);
             out[j * PGH_PAIR_SLOTS + f] = r;
         }
         __syncthreads();
@@ -251,12 +232,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(const double* __restrict__
     if (threadIdx.x >= ns && threadIdx.x < PGH_PAIR_SLOTS) out[j * PGH_PAIR_SLOTS + threadIdx.x] = 0.0;
 }
 
-int decline(const std::string& why) {
-    set_error("pgh_pair_forms declined: " + why);
-    return PGH_PAIR_DECLINED;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+const char* const kPair = "pgh_pair_forms";
 }  // namespace
 
 extern "C" int pgh_pair_forms(pgh_mat_t scores, pgh_vec_t known_vec, pgh_mat_t known_mat, pgh_vec_t exclude_vec, pgh_mat_t exclude_mat,
@@ -266,24 +242,24 @@ extern "C" int pgh_pair_forms(pgh_mat_t scores, pgh_vec_t known_vec, pgh_mat_t k
     PGH_CHECK((known_vec != nullptr) != (known_mat != nullptr), "pgh_pair_forms: exactly one of known_vec and known_mat expected");
     PGH_CHECK(!(exclude_vec && exclude_mat), "pgh_pair_forms: at most one of exclude_vec and exclude_mat expected");
     PGH_CHECK(scores->b >= 1 && scores->n >= 0, "pgh_pair_forms: at least one column expected");
-    if (scores->b > kMaxCols) return decline("more than 64 columns");
+    if (scores->b > kSlabMaxCols) return declined(PGH_PAIR_DECLINED, kPair, "more than 64 columns");
     const int b = scores->b;
     const int64_t n = scores->n;
     PGH_CHECK(known_vec == nullptr || known_vec->n == n, "pgh_pair_forms: shape mismatch (known_vec)");
     PGH_CHECK(known_mat == nullptr || (known_mat->n == n && known_mat->b == b), "pgh_pair_forms: shape mismatch (known_mat)");
     PGH_CHECK(exclude_vec == nullptr || exclude_vec->n == n, "pgh_pair_forms: shape mismatch (exclude_vec)");
     PGH_CHECK(exclude_mat == nullptr || (exclude_mat->n == n && exclude_mat->b == b), "pgh_pair_forms: shape mismatch (exclude_mat)");
-    if (!std::isfinite(eps)) return decline("non-finite eps");
+    if (!std::isfinite(eps)) return declined(PGH_PAIR_DECLINED, kPair, "non-finite eps");
     PairFactors factors;
-    for (int j = 0; j < kMaxCols; ++j) factors.f[j] = 1.0;
+    for (int j = 0; j < kSlabMaxCols; ++j) factors.f[j] = 1.0;
     if (factors_host != nullptr)
         for (int j = 0; j < b; ++j) {
             factors.f[j] = factors_host[j];
-            if (!std::isfinite(factors.f[j])) return decline("non-finite factor");
+            if (!std::isfinite(factors.f[j])) return declined(PGH_PAIR_DECLINED, kPair, "non-finite factor");
         }
     const bool logs = groups == PGH_PAIR_LOGS;
     const int ns = logs ? kAll : kMoments;
-    double result[PGH_PAIR_SLOTS * kMaxCols];
+    double result[PGH_PAIR_SLOTS * kSlabMaxCols];
     for (int j = 0; j < b; ++j)
         for (int f = 0; f < PGH_PAIR_SLOTS; ++f) result[PGH_PAIR_SLOTS * j + f] = slot_is_max(f) ? -INFINITY : 0.0;
     if (n > 0) {
@@ -296,22 +272,21 @@ extern "C" int pgh_pair_forms(pgh_mat_t scores, pgh_vec_t known_vec, pgh_mat_t k
         exclude.rs = exclude_mat ? b : 1;
         exclude.cs = exclude_mat ? 1 : 0;
         // same-sized blocks come back from the runtime's pool on the next call: no allocation after the first
-        DevBuf partial, folded;
-        PGH_TRY(partial.alloc(sizeof(double) * (size_t)kParts * b * ns));
+        PoolBuf partial, folded;
+        PGH_TRY(partial.alloc(sizeof(double) * (size_t)kSlabParts * b * ns));
         PGH_TRY(folded.alloc(sizeof(double) * (size_t)b * PGH_PAIR_SLOTS));
         const int grid = parts_grid();
         const bool words = b % 4 == 0 && aligned16(scores->data) && (known_mat == nullptr || aligned16(known.data)) &&
                            (exclude_mat == nullptr || aligned16(exclude.data));
         if (words) {
-            int lpr = 1;
-            while (lpr * 4 < b) lpr <<= 1;
-            if (logs) k_pair_rows<true><<<grid, kBlock, 0, r.stream>>>(scores->data, n, b, lpr, known, exclude, factors, eps, partial.as<double>());
-            else k_pair_rows<false><<<grid, kBlock, 0, r.stream>>>(scores->data, n, b, lpr, known, exclude, factors, eps, partial.as<double>());
+            const int lpr = lpr_for(b);
+            if (logs) k_pair_rows<true><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, n, b, lpr, known, exclude, factors, eps, partial.as<double>());
+            else k_pair_rows<false><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, n, b, lpr, known, exclude, factors, eps, partial.as<double>());
         } else {
-            if (logs) k_pair_cols<true><<<grid, kBlock, 0, r.stream>>>(scores->data, n, b, known, exclude, factors, eps, partial.as<double>());
-            else k_pair_cols<false><<<grid, kBlock, 0, r.stream>>>(scores->data, n, b, known, exclude, factors, eps, partial.as<double>());
+            if (logs) k_pair_cols<true><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, n, b, known, exclude, factors, eps, partial.as<double>());
+            else k_pair_cols<false><<<grid, kSlabBlock, 0, r.stream>>>(scores->data, n, b, known, exclude, factors, eps, partial.as<double>());
         }
-        k_pair_fold<<<b, kBlock, 0, r.stream>>>(partial.as<double>(), b, ns, folded.as<double>());
+        k_pair_fold<<<b, kSlabBlock, 0, r.stream>>>(partial.as<double>(), b, ns, folded.as<double>());
         PGH_HIP(hipGetLastError());
         PGH_HIP(hipMemcpyAsync(result, folded.p, sizeof(double) * (size_t)b * PGH_PAIR_SLOTS, hipMemcpyDeviceToHost, r.stream));
         PGH_HIP(hipStreamSynchronize(r.stream));

@@ -12,10 +12,11 @@
 //                      Lanes add ub + lb into 64-bit integers; wavefronts (shuffles), workgroups (LDS) and the device (one integer
 //                      atomic per workgroup and probe) sum integers, so nothing depends on the grid or on arrival order.
 //   the host forms     auc[q] = (2 m n_neg - T_q) / (2 m n_neg)
-#include "pgh_common.h"
+#include "pgh_slab.h"
 #include "pgh_tune.h"
 
 #include <cmath>
+#include <memory>
 
 using namespace pgh;
 
@@ -26,48 +27,10 @@ struct pgh_probe_plan_s {
 };
 
 namespace {
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 2048;   // 256 CUs x 8 workgroups, grid-stride beyond
-
-inline int grid_rows(int64_t rows, int rows_per_block) {
-    int64_t g = (rows + rows_per_block - 1) / rows_per_block;
-    if (g < 1) g = 1;
-    return (int)(g > kMaxGrid ? kMaxGrid : g);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v, int stop) {
-    for (int off = 32; off >= stop; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// class byte of every node + the two class counts (counts[0] positives, counts[1] negatives)
-__global__ __launch_bounds__(kBlock) void k_plan_classify(const float* __restrict__ known, const float* __restrict__ exclude, int64_t n,
-                                                           uint8_t* __restrict__ cls, unsigned long long* __restrict__ counts) {
-    __shared__ unsigned long long s_cnt[2];
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    unsigned long long pos = 0, neg = 0;
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const bool out = exclude != nullptr && exclude[i] != 0.f;
-        const uint8_t c = out ? 0 : (known[i] != 0.f ? 2 : 1);
-        cls[i] = c;
-        pos += c == 2;
-        neg += c == 1;
-    }
-    pos = wave_sum_u64(pos, 1);
-    neg = wave_sum_u64(neg, 1);
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&s_cnt[0], pos);
-        atomicAdd(&s_cnt[1], neg);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x] != 0) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-}
-
 // rows of the positives, appended in arrival order (the slot counter never passes n_pos: the same predicate counted them)
-__global__ __launch_bounds__(kBlock) void k_plan_positives(const uint8_t* __restrict__ cls, int64_t n, int64_t n_pos, int32_t* __restrict__ pos_idx,
-                                                            unsigned long long* __restrict__ cursor) {
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+__global__ __launch_bounds__(kSlabBlock) void k_plan_positives(const uint8_t* __restrict__ cls, int64_t n, int64_t n_pos, int32_t* __restrict__ pos_idx,
+                                                                unsigned long long* __restrict__ cursor) {
+    for (int64_t i = blockIdx.x * (int64_t)kSlabBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kSlabBlock) {
         if (cls[i] != 2) continue;
         const unsigned long long slot = atomicAdd(cursor, 1ull);
         if (slot < (unsigned long long)n_pos) pos_idx[slot] = (int32_t)i;
@@ -75,12 +38,12 @@ __global__ __launch_bounds__(kBlock) void k_plan_positives(const uint8_t* __rest
 }
 
 // sorted[q][0 .. m): the scores of the positives under probe q, ascending.  m <= PGH_TUNE_MAX_POSITIVES.
-__global__ __launch_bounds__(kBlock) void k_probe_positives(const float* __restrict__ slab, int b, const double* __restrict__ coeffs, int terms, int probes,
-                                                             const int32_t* __restrict__ pos_idx, int m, int padded /* power of two >= m */,
-                                                             float* __restrict__ sorted) {
+__global__ __launch_bounds__(kSlabBlock) void k_probe_positives(const float* __restrict__ slab, int b, const double* __restrict__ coeffs, int terms, int probes,
+                                                                 const int32_t* __restrict__ pos_idx, int m, int padded /* power of two >= m */,
+                                                                 float* __restrict__ sorted) {
     __shared__ float s_v[PGH_TUNE_MAX_POSITIVES];
     const int q = blockIdx.x;
-    for (int k = threadIdx.x; k < padded; k += kBlock) {
+    for (int k = threadIdx.x; k < padded; k += kSlabBlock) {
         float v = INFINITY;                                  // padding sorts last
         if (k < m) {
             const float* __restrict__ row = slab + (int64_t)pos_idx[k] * b;
@@ -91,23 +54,14 @@ __global__ __launch_bounds__(kBlock) void k_probe_positives(const float* __restr
         s_v[k] = v;
     }
     __syncthreads();
-    for (int size = 2; size <= padded; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < padded; t += kBlock) {
-                const int other = t ^ stride;
-                if (other > t) {
-                    const float a = s_v[t], c = s_v[other];
-                    const bool ascending = (t & size) == 0;
-                    if ((a > c) == ascending) {
-                        s_v[t] = c;
-                        s_v[other] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int k = threadIdx.x; k < m; k += kBlock) sorted[(int64_t)q * m + k] = s_v[k];
+    bitonic_sort_lds<kSlabBlock>(
+        padded, [&](int i, int j) { return s_v[i] < s_v[j]; },
+        [&](int i, int j) {
+            const float x = s_v[i];
+            s_v[i] = s_v[j];
+            s_v[j] = x;
+        });
+    for (int k = threadIdx.x; k < m; k += kSlabBlock) sorted[(int64_t)q * m + k] = s_v[k];
 }
 
 // first index of the ascending run s[0 .. m) whose value is not below v (STRICT = false) or is above v (STRICT = true)
@@ -125,19 +79,19 @@ __device__ __forceinline__ int bound(const float* s, int m, float v) {
 // LPR lanes share a row and hold four probes each (the mapping of k_mat_gemm); a row's leading `terms` floats arrive as 16-byte
 // loads when the slab's rows are 16-byte aligned.  IN_LDS: the sorted positives were copied into LDS behind the coefficients.
 template <int LPR, bool IN_LDS>
-__global__ __launch_bounds__(kBlock) void k_probe_stream(const float* __restrict__ slab, int64_t n, int b, int vec_ok, const double* __restrict__ coeffs,
-                                                          int terms, int probes, const uint8_t* __restrict__ cls,
-                                                          const float* __restrict__ sorted, int m, unsigned long long* __restrict__ totals) {
+__global__ __launch_bounds__(kSlabBlock) void k_probe_stream(const float* __restrict__ slab, int64_t n, int b, int vec_ok, const double* __restrict__ coeffs,
+                                                              int terms, int probes, const uint8_t* __restrict__ cls,
+                                                              const float* __restrict__ sorted, int m, unsigned long long* __restrict__ totals) {
     extern __shared__ double s_dyn[];
     __shared__ unsigned long long s_tot[64];
     double* s_c = s_dyn;                                     // [terms * probes]
     float* s_pos = reinterpret_cast<float*>(s_dyn + terms * probes);   // [probes * m] when IN_LDS
-    for (int j = threadIdx.x; j < terms * probes; j += kBlock) s_c[j] = coeffs[j];
+    for (int j = threadIdx.x; j < terms * probes; j += kSlabBlock) s_c[j] = coeffs[j];
     if (IN_LDS)
-        for (int j = threadIdx.x; j < probes * m; j += kBlock) s_pos[j] = sorted[j];
+        for (int j = threadIdx.x; j < probes * m; j += kSlabBlock) s_pos[j] = sorted[j];
     if (threadIdx.x < 64) s_tot[threadIdx.x] = 0;
     __syncthreads();
-    constexpr int ROWS = kBlock / LPR;
+    constexpr int ROWS = kSlabBlock / LPR;
     const int q0 = (threadIdx.x % LPR) * 4, r_in = threadIdx.x / LPR;
     const float* __restrict__ pos = IN_LDS ? s_pos : sorted;
     unsigned long long tot[4] = {0, 0, 0, 0};
@@ -181,13 +135,10 @@ __global__ __launch_bounds__(kBlock) void k_probe_stream(const float* __restrict
     if (threadIdx.x < probes && s_tot[threadIdx.x] != 0) atomicAdd(&totals[threadIdx.x], s_tot[threadIdx.x]);
 }
 
-int decline(const std::string& why) {
-    set_error("pgh_probe_auc declined: " + why);
-    return PGH_TUNE_DECLINED;
-}
+const char* const kAuc = "pgh_probe_auc";
 }  // namespace
 
-PGH_WARM_KERNEL(k_plan_classify)
+PGH_WARM_KERNEL(k_plan_positives)
 
 extern "C" int pgh_probe_plan_create(pgh_vec_t known, pgh_vec_t exclude, pgh_probe_plan_t* out) {
     PGH_CHECK(known && out, "pgh_probe_plan_create: null argument");
@@ -196,40 +147,24 @@ extern "C" int pgh_probe_plan_create(pgh_vec_t known, pgh_vec_t exclude, pgh_pro
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const int64_t n = known->n;
-    pgh_probe_plan_s* plan = new pgh_probe_plan_s();
+    std::unique_ptr<pgh_probe_plan_s, int (*)(pgh_probe_plan_t)> plan(new pgh_probe_plan_s(), pgh_probe_plan_destroy);
     plan->n = n;
-    unsigned long long* counts = nullptr;                  // positives, negatives, append cursor
-    int rc = pool_alloc(sizeof(unsigned long long) * 3, (void**)&counts);
-    if (rc == 0) rc = pool_alloc((size_t)(n > 0 ? n : 1), (void**)&plan->cls);
-    if (rc != 0) {
-        if (counts) pool_free(counts);
-        delete plan;
-        return rc;
+    PGH_TRY(pool_alloc((size_t)(n > 0 ? n : 1), (void**)&plan->cls));
+    unsigned long long counts[4];
+    PGH_TRY(classify_labels(known, exclude, plan->cls, counts));
+    plan->n_pos = (int64_t)counts[1];
+    plan->n_neg = (int64_t)counts[2];
+    PGH_TRY(pool_alloc(sizeof(int32_t) * (size_t)(plan->n_pos > 0 ? plan->n_pos : 1), (void**)&plan->pos_idx));
+    if (plan->n_pos > 0) {
+        PoolBuf cursor;
+        PGH_TRY(cursor.alloc(sizeof(unsigned long long)));
+        PGH_HIP(hipMemsetAsync(cursor.p, 0, sizeof(unsigned long long), r.stream));
+        k_plan_positives<<<grid_capped(n, kSlabBlock * 8), kSlabBlock, 0, r.stream>>>(plan->cls, n, plan->n_pos, plan->pos_idx,
+                                                                             cursor.as<unsigned long long>());
+        PGH_HIP(hipGetLastError());
+        PGH_HIP(hipStreamSynchronize(r.stream));
     }
-    unsigned long long host[3] = {0, 0, 0};
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(unsigned long long) * 3, r.stream);
-    if (e == hipSuccess && n > 0) {
-        k_plan_classify<<<grid_rows(n, kBlock * 8), kBlock, 0, r.stream>>>(known->data, exclude ? exclude->data : nullptr, n, plan->cls, counts);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, counts, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, r.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(r.stream);
-    if (e == hipSuccess) {
-        plan->n_pos = (int64_t)host[0];
-        plan->n_neg = (int64_t)host[1];
-        rc = pool_alloc(sizeof(int32_t) * (size_t)(plan->n_pos > 0 ? plan->n_pos : 1), (void**)&plan->pos_idx);
-        if (rc == 0 && plan->n_pos > 0) {
-            k_plan_positives<<<grid_rows(n, kBlock * 8), kBlock, 0, r.stream>>>(plan->cls, n, plan->n_pos, plan->pos_idx, counts + 2);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(r.stream);
-        }
-    }
-    pool_free(counts);
-    if (e != hipSuccess || rc != 0) {
-        pgh_probe_plan_destroy(plan);
-        return e != hipSuccess ? fail(std::string("pgh_probe_plan_create: ") + hipGetErrorString(e)) : rc;
-    }
-    *out = plan;
+    *out = plan.release();
     return 0;
 }
 
@@ -252,64 +187,53 @@ extern "C" int pgh_probe_auc(pgh_mat_t slab, const double* coeffs_host, int32_t 
                              double* auc_host) {
     PGH_CHECK(slab && coeffs_host && plan && auc_host, "pgh_probe_auc: null argument");
     PGH_CHECK(probes >= 1 && probes <= 64 && terms >= 1, "pgh_probe_auc: 1 <= probes <= 64 and terms >= 1 expected");
-    if (terms > 64) return decline("more than 64 terms (more than one slab)");
+    if (terms > 64) return declined(PGH_TUNE_DECLINED, kAuc, "more than 64 terms (more than one slab)");
     PGH_CHECK(terms <= slab->b && slab->n == plan->n, "pgh_probe_auc: shape mismatch");
-    if (plan->n_pos == 0 || plan->n_neg == 0) return decline("all labels are the same");
-    if (plan->n_pos > PGH_TUNE_MAX_POSITIVES) return decline("more positives than the per-probe sort holds");
+    if (plan->n_pos == 0 || plan->n_neg == 0) return declined(PGH_TUNE_DECLINED, kAuc, "all labels are the same");
+    if (plan->n_pos > PGH_TUNE_MAX_POSITIVES) return declined(PGH_TUNE_DECLINED, kAuc, "more positives than the per-probe sort holds");
     for (int64_t j = 0; j < (int64_t)terms * probes; ++j)
-        if (!std::isfinite(coeffs_host[j])) return decline("non-finite coefficient");
+        if (!std::isfinite(coeffs_host[j])) return declined(PGH_TUNE_DECLINED, kAuc, "non-finite coefficient");
     Runtime& r = rt();
     const int m = (int)plan->n_pos;
     int padded = 1;
     while (padded < m) padded <<= 1;
     const size_t coeff_bytes = sizeof(double) * (size_t)terms * probes;
-    double* d_c = nullptr;
-    float* sorted = nullptr;
-    unsigned long long* totals = nullptr;
-    PGH_TRY(pool_alloc(coeff_bytes, (void**)&d_c));
-    int rc = pool_alloc(sizeof(float) * (size_t)probes * m, (void**)&sorted);
-    if (rc == 0) rc = pool_alloc(sizeof(unsigned long long) * 64, (void**)&totals);
-    if (rc != 0) {
-        pool_free(d_c);
-        if (sorted) pool_free(sorted);
-        return rc;
-    }
-    unsigned long long host[64];
-    hipError_t e = hipMemcpyAsync(d_c, coeffs_host, coeff_bytes, hipMemcpyHostToDevice, r.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(totals, 0, sizeof(unsigned long long) * 64, r.stream);
-    if (e == hipSuccess) {
-        k_probe_positives<<<probes, kBlock, 0, r.stream>>>(slab->data, slab->b, d_c, terms, probes, plan->pos_idx, m, padded, sorted);
-        const size_t lds_all = coeff_bytes + sizeof(float) * (size_t)probes * m;
-        const bool in_lds = lds_all <= PGH_TUNE_LDS_BYTES;
-        const size_t lds = in_lds ? lds_all : coeff_bytes;
-        const int lpr = probes > 32 ? 16 : (probes > 16 ? 8 : (probes > 8 ? 4 : (probes > 4 ? 2 : 1)));
-        const int grid = grid_rows(slab->n, kBlock / lpr);
-        const int vec_ok = slab->b % 4 == 0 && (reinterpret_cast<uintptr_t>(slab->data) & 15) == 0;
+    PoolBuf d_c, sorted, totals;
+    PGH_TRY(d_c.alloc(coeff_bytes));
+    PGH_TRY(sorted.alloc(sizeof(float) * (size_t)probes * m));
+    PGH_TRY(totals.alloc(sizeof(unsigned long long) * 64));
+    StreamFence fence;                                       // the caller's coefficient array may go away
+    PGH_HIP(hipMemcpyAsync(d_c.p, coeffs_host, coeff_bytes, hipMemcpyHostToDevice, r.stream));
+    PGH_HIP(hipMemsetAsync(totals.p, 0, sizeof(unsigned long long) * 64, r.stream));
+    k_probe_positives<<<probes, kSlabBlock, 0, r.stream>>>(slab->data, slab->b, d_c.as<double>(), terms, probes, plan->pos_idx, m, padded,
+                                                       sorted.as<float>());
+    const size_t lds_all = coeff_bytes + sizeof(float) * (size_t)probes * m;
+    const bool in_lds = lds_all <= PGH_TUNE_LDS_BYTES;
+    const size_t lds = in_lds ? lds_all : coeff_bytes;
+    const int lpr = lpr_for(probes);
+    const int grid = grid_capped(slab->n, kSlabBlock / lpr);
+    const int vec_ok = slab->b % 4 == 0 && aligned16(slab->data);
 #define PGH_STREAM(LPR)                                                                                                                   \
     do {                                                                                                                                  \
         if (in_lds)                                                                                                                       \
-            k_probe_stream<LPR, true><<<grid, kBlock, lds, r.stream>>>(slab->data, slab->n, slab->b, vec_ok, d_c, terms, probes, plan->cls, \
-                                                                        sorted, m, totals);                                               \
+            k_probe_stream<LPR, true><<<grid, kSlabBlock, lds, r.stream>>>(slab->data, slab->n, slab->b, vec_ok, d_c.as<double>(), terms, probes, \
+                                                                        plan->cls, sorted.as<float>(), m, totals.as<unsigned long long>()); \
         else                                                                                                                              \
-            k_probe_stream<LPR, false><<<grid, kBlock, lds, r.stream>>>(slab->data, slab->n, slab->b, vec_ok, d_c, terms, probes, plan->cls, \
-                                                                         sorted, m, totals);                                              \
+            k_probe_stream<LPR, false><<<grid, kSlabBlock, lds, r.stream>>>(slab->data, slab->n, slab->b, vec_ok, d_c.as<double>(), terms, probes, \
+                                                                         plan->cls, sorted.as<float>(), m, totals.as<unsigned long long>()); \
     } while (0)
-        switch (lpr) {
-            case 16: PGH_STREAM(16); break;
-            case 8: PGH_STREAM(8); break;
-            case 4: PGH_STREAM(4); break;
-            case 2: PGH_STREAM(2); break;
-            default: PGH_STREAM(1); break;
-        }
-#undef PGH_STREAM
-        e = hipGetLastError();
+    switch (lpr) {
+        case 16: PGH_STREAM(16); break;
+        case 8: PGH_STREAM(8); break;
+        case 4: PGH_STREAM(4); break;
+        case 2: PGH_STREAM(2); break;
+        default: PGH_STREAM(1); break;
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, totals, sizeof(unsigned long long) * probes, hipMemcpyDeviceToHost, r.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(r.stream);  // the caller's coefficient array may go away
-    pool_free(d_c);
-    pool_free(sorted);
-    pool_free(totals);
-    if (e != hipSuccess) return fail(std::string("pgh_probe_auc: ") + hipGetErrorString(e));
+#undef PGH_STREAM
+    PGH_HIP(hipGetLastError());
+    unsigned long long host[64];
+    PGH_HIP(hipMemcpyAsync(host, totals.p, sizeof(unsigned long long) * probes, hipMemcpyDeviceToHost, r.stream));
+    PGH_HIP(fence.wait());
     const unsigned long long full = 2ull * (unsigned long long)m * (unsigned long long)plan->n_neg;
     for (int q = 0; q < probes; ++q) auc_host[q] = (double)(full - host[q]) / (double)full;
     return 0;
