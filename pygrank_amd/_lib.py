@@ -2,7 +2,8 @@
 include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h, the supervised measures' entry of
 include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h, the locally fair PageRank's entries of
 include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h, the rank-based measures' entries of include/pgh_rank.h,
-the Krylov-space filters' entries of include/pgh_krylov.h, the multi-group measures' entries of include/pgh_link.h).
+the Krylov-space filters' entries of include/pgh_krylov.h, the multi-group measures' entries of include/pgh_link.h, the Arnoldi
+passes of include/pgh_arnoldi.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -323,6 +324,15 @@ LINK_DECLINED = 2         # include/pgh_link.h PGH_LINK_DECLINED: nothing was wr
 LINK_MAX_PAIRS = 1 << 27  # include/pgh_link.h PGH_LINK_MAX_PAIRS
 LINK_COS, LINK_DOT = 0, 1                                                           # include/pgh_link.h PGH_LINK_*
 
+# name -> (restype, argtypes); every symbol include/pgh_arnoldi.h declares.  Bound apart like the Krylov entries (arnoldi_entry): on a
+# library without them arnoldi_iteration takes the reference's route, one backend primitive at a time.
+ARNOLDI_SIGNATURES = {
+    "pgh_basis_dots": (C.c_int, [c_mat, C.c_int32, c_vec, c_f64p]),
+    "pgh_arnoldi_close": (C.c_int, [c_mat, C.c_int32, c_vec, c_f64p, c_vec, C.c_int32, c_f64p]),
+}
+ARNOLDI_DECLINED = 2      # include/pgh_arnoldi.h PGH_ARNOLDI_DECLINED: nothing was written, the caller takes the backend-primitive route
+ARNOLDI_MAX_DIMS = 64     # include/pgh_arnoldi.h PGH_ARNOLDI_MAX_DIMS
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -407,6 +417,21 @@ def bind_krylov(cdll):
 def bind_link(cdll):
     """Binds the include/pgh_link.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, LINK_SIGNATURES)
+
+
+def bind_arnoldi(cdll):
+    """Binds the include/pgh_arnoldi.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, ARNOLDI_SIGNATURES)
+
+
+def arnoldi_entry(name):
+    """The bound include/pgh_arnoldi.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_arnoldi_entries", None)
+    if cache is None:
+        cache = bind_arnoldi(cdll)
+        cdll._pgh_arnoldi_entries = cache
+    return cache[name]
 
 
 def link_entry(name):

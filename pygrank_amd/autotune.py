@@ -1,8 +1,8 @@
 """Parameter tuning: the coordinate descent of [krasanakis2022autogf], the tuner built on it and the selection among ready filters.
 
 Restates pygrank/algorithms/autotune/optimization.py:9-25,64-212 (``optimize``), autotune/tuning.py:5-23 (``Tuner``),
-autotune/parameterized.py:9-177 (``default_tuning_optimization``, ``SelfClearDict``, ``ParameterTuner``) and
-autotune/selection.py:10-91 (``AlgorithmSelection``).
+autotune/parameterized.py:9-177 (``default_tuning_optimization``, ``SelfClearDict``, ``ParameterTuner``),
+autotune/selection.py:10-91 (``AlgorithmSelection``) and autotune/hop_tuner.py:14-184 (``HopTuner``).
 
 One addition to the reference.  A coordinate step of ``optimize`` scores ``partitions`` candidates that differ in ONE weight.  When
 the loss object has a callable attribute ``many`` the step hands it the whole candidate list in one call.  ``ParameterTuner`` builds
@@ -19,10 +19,10 @@ from random import random
 import numpy as np
 
 from pygrank_amd import _lib as L
-from pygrank_amd.measures import AUC, split
+from pygrank_amd.measures import AUC, Cos, split
 from pygrank_amd.preprocessing import preprocessor
 from pygrank_amd.signals import NodeRanking, to_signal
-from pygrank_amd.utils import remove_used_args
+from pygrank_amd.utils import ensure_used_args, remove_used_args
 
 
 def _log(text=""):
@@ -367,6 +367,295 @@ class ParameterTuner(Tuner):
                 ret[i] = desc
                 return ret
         return ret + [desc]
+
+
+def hop_parameters(measure_values, num_parameters, autoregression=0):
+    """hop_tuner.py:106-143 on the host in f64: the K x H hop values (K = num_parameters + autoregression hops, H held-out halves) ->
+    the num_parameters hop weights before the offset search and the final normalisation.  The values are mean-centred per half; with
+    autoregression > 0 an Adam loop fits a window that predicts every hop from the `autoregression` hops behind it and the
+    predictions replace the values; the halves are averaged and the mean of the means is added back."""
+    measure_values = np.array(measure_values, dtype=np.float64)
+    mean_value = np.mean(measure_values, axis=0)
+    measure_values = measure_values - mean_value
+    best_parameters = measure_values
+    measure_weights = [1] * measure_values.shape[1]
+    if autoregression != 0:
+        window = np.repeat(1. / autoregression, autoregression)
+        beta1 = 0.9
+        beta2 = 0.999
+        beta1t = 1
+        beta2t = 1
+        rms = window * 0
+        momentum = window * 0
+        error = float('inf')
+        while True:
+            beta1t *= beta1
+            beta2t *= beta2
+            prev_error = error
+            parameters = np.copy(measure_values)
+            for i in range(len(measure_values) - len(window) - 2, -1, -1):
+                parameters[i, :] = np.dot(window, measure_values[(i + 1):(i + len(window) + 1), :])
+            errors = (parameters - measure_values) * measure_weights / np.sum(measure_weights)
+            for j in range(len(window)):
+                gradient = 0
+                for i in range(len(measure_values) - len(window) - 1):
+                    gradient += np.dot(measure_values[i + j + 1, :], errors[i, :])
+                momentum[j] = beta1 * momentum[j] + (1 - beta1) * gradient
+                rms[j] = beta2 * rms[j] + (1 - beta2) * gradient * gradient
+                window[j] -= 0.01 * momentum[j] / (1 - beta1t) / ((rms[j] / (1 - beta2t)) ** 0.5 + 1.E-8)
+            error = np.mean(np.abs(errors))
+            if error == 0 or abs(error - prev_error) / error < 1.E-6:
+                best_parameters = parameters
+                break
+    return np.mean(best_parameters[:num_parameters, :] * np.asarray(measure_weights, dtype=np.float64), axis=1) + np.mean(mean_value)
+
+
+class _HopOffsetLoss:
+    """The loss of HopTuner's offset search (hop_tuner.py:150-155): ``loss([offset])`` is the reference's one-probe evaluation,
+    -best_direction * measure(_run(training, parameters + offset)).  ``many`` exists where a step's candidates share one slab pass:
+      * "krylov" basis, the default generator and AUC: the candidates are GenericGraphFilter variants over the power slab of
+        `training` in the tuner's optimisation dict, scored by ParameterTuner's _ProbeLoss (pgh_probe_auc);
+      * "arnoldi" basis: one pgh_mat_gemm over the basis of the first half turns the candidates into an [n, P] slab that the
+        measure's evaluate_many scores."""
+
+    def __init__(self, tuner, measure, training, validation, parameters, base, args, kwargs):
+        self.tuner, self.measure, self.training, self.parameters, self.base = tuner, measure, training, parameters, base
+        self.args, self.kwargs = args, kwargs
+        self._probe = None
+        if not tuner.fused or args or kwargs:
+            return
+        filter_kwargs = tuner._filter_kwargs
+        if base is not None:
+            from pygrank_amd.device import DeviceMatrix
+            if isinstance(base, DeviceMatrix) and base.b <= 64 and callable(getattr(measure, "evaluate_many", None)):
+                self.many = self._many_arnoldi
+        elif filter_kwargs is not None and tuner.tunable_offset is AUC and filter_kwargs.get("optimization_dict") is not None \
+                and filter_kwargs.get("coefficient_type", "taylor").lower() in ("taylor", "chebyshev") \
+                and filter_kwargs.get("krylov_dims") is None:
+            self._probe = _ProbeLoss(tuner, [(training, validation, training)], filter_kwargs, args, kwargs)
+            self.many = self._many_krylov
+
+    def _weights(self, params):
+        """hop_tuner.py:153 and _run's normalisation (hop_tuner.py:172-175)."""
+        weights = np.array([self.parameters[i] + params[0] for i in range(len(self.parameters))], dtype=np.float64)
+        div = np.sum(np.abs(weights))
+        return weights / div if div != 0 else weights
+
+    def __call__(self, params):
+        weights = [self.parameters[i] + params[0] for i in range(len(self.parameters))]
+        return -self.measure.best_direction() * self.measure(self.tuner._run(self.training, weights, self.base, *self.args, **self.kwargs))
+
+    def _many_krylov(self, candidates):
+        return self._probe.many([[float(w) for w in self._weights(params)] for params in candidates])
+
+    def _many_arnoldi(self, candidates):
+        candidates = list(candidates)
+        losses = []
+        for start in range(0, len(candidates), 64):
+            coefficients = np.stack([self._weights(params) for params in candidates[start:start + 64]], axis=1)
+            ranks = self.base.gemm(coefficients)
+            self.tuner.last_tune["slab_passes"] += 2
+            self.tuner.last_tune["fused_steps"] += 1
+            losses.extend(-self.measure.best_direction() * value for value in self.measure.evaluate_many(ranks))
+        return losses
+
+
+class HopTuner(Tuner):
+    """hop_tuner.py:14-184: tunes a GenericGraphFilter WITHOUT a search.  The training seeds are split in two halves, both are
+    propagated hop by hop, every hop is scored against the held-out validation seeds (the half itself excluded) and the scores become
+    the filter's hop weights.  (The reference marks the approach as experimental.)
+
+    ranker_generator: parameters -> ranker.  None (default): ``GenericGraphFilter(params, **kwargs)`` with a ``SelfClearDict``
+        optimisation dict unless the keywords say otherwise (no Normalize, no immutable preprocessor: the reference adds neither).
+    measure: known scores, exclude -> supervised measure that scores a hop (default Cos).  With Cos the hop-0 score is 0 -- a half and
+        the validation seeds are disjoint --, the filter's first weight is then 0 and the filter ends after 2 iterations with all-zero
+        ranks, as in the reference.
+    basis: "krylov" (the plain powers of the halves) or "arnoldi" (the columns of ``arnoldi_iteration`` of each half; the tuner then
+        returns a Tautology and the combined basis as the personalization: no ranking algorithm comes out of it).
+    tuning_backend: None or "hip" (this package has one engine).
+    autoregression: hops a fitted window predicts every hop from (0: the scores are taken as they are); ``hop_parameters``.
+    num_parameters: hop weights of the filter.
+    tunable_offset: None, or a measure generator: an offset in [0, 1] added to every weight is searched with ``optimize`` on the
+        training seeds against the validation seeds.
+    pre_diffuse: accepted and unused, as in the reference.
+    fused: True (default; an extension) runs the sweep on slabs: the powers of a half are the columns of an
+        [n, K] slab, the K scores of a half come from one slab pass of the measure's ``evaluate_many`` (pgh_pair_forms with the half as
+        `exclude`; pgh_probe_auc for AUC), the "arnoldi" basis comes from the two-pass Arnoldi step (include/pgh_arnoldi.h) and a step
+        of the offset search scores its candidates together.  False -- and more than 64 hops, a graph that is not the engine's, a
+        library without the entries -- is the reference's route, one backend primitive at a time.
+
+    After a run ``last_params`` holds the weights, ``last_values`` the K x 2 hop values (``last_pre_offset`` and ``last_offset`` what
+    the offset search started from and found) and ``last_tune`` the ``route`` ("fused" or
+    "primitive"), the ``sweep`` ("steps", "arnoldi:fused", "arnoldi:primitive" or "primitive"), the ``scoring`` route of each
+    half ("slab" or "columns"), the ``products`` with the adjacency, the ``slab_passes`` of the scoring,
+    the Arnoldi steps and the offset search, and that search's ``fused_steps`` / ``unfused_steps``."""
+
+    def __init__(self, ranker_generator=None, measure=Cos, basis="Krylov", tuning_backend=None, autoregression=0, num_parameters=20,
+                 tunable_offset=None, pre_diffuse=None, fused=True, **kwargs):
+        if tuning_backend not in (None, "hip"):
+            raise Exception("tuning_backend is None or 'hip': this package drives one engine")
+        self._filter_kwargs = None
+        if ranker_generator is None:
+            if "optimization_dict" not in kwargs:
+                kwargs["optimization_dict"] = SelfClearDict()
+            from pygrank_amd.filters import GenericGraphFilter
+            filter_kwargs = self._filter_kwargs = kwargs
+
+            def ranker_generator(params):
+                return GenericGraphFilter(params, **filter_kwargs)
+        else:
+            ensure_used_args(kwargs, [])
+        self.ranker_generator = ranker_generator
+        self.measure = measure
+        self.tuning_backend = tuning_backend
+        self.autoregression = autoregression
+        self.num_parameters = num_parameters
+        self.tunable_offset = tunable_offset
+        self.pre_diffuse = pre_diffuse
+        self.basis = basis.lower()
+        self.fused = fused
+        self.last_tune = self._fresh_stats()
+        self.last_params = self.last_values = None
+
+    fuse = property(lambda self: self.fused)          # what _ProbeLoss asks its tuner
+
+    @staticmethod
+    def _fresh_stats():
+        return dict(route="primitive", sweep="primitive", scoring=[], products=0, slab_passes=0, fused_steps=0, unfused_steps=0)
+
+    def _evaluate(self, splits, params, args, kwargs):
+        """One probe of the offset search as _ProbeLoss calls it: hop_tuner.py:152-154 for weights that are already normalised."""
+        val = 0
+        for training, validation, exclude in splits:
+            measure = self.tunable_offset(validation, exclude)
+            val = val - measure.best_direction() * measure(self._run(training, params, None, *args, **kwargs))
+        return val / len(splits)
+
+    # ---- the hop sweep ---------------------------------------------------------------------------------------------------------------
+    def _score(self, measure, slab, stats):
+        """The score of every column of `slab` under `measure`: one slab pass where the measure has one."""
+        many = getattr(measure, "evaluate_many", None)
+        if callable(many):
+            values = [float(v) for v in many(slab)]
+            route = getattr(measure, "last_route", None) or "columns"
+        else:
+            values, route = [float(measure(slab.column(i))) for i in range(slab.b)], "columns"
+        stats["scoring"].append(route)
+        stats["slab_passes"] += 1 if route == "slab" else slab.b
+        return values
+
+    def _sweep_powers(self, g, halves, hops, stats):
+        """The [n, hops] slabs of the powers (M^T)^i p of both halves, or None where the slab route does not apply.
+        A hop is one single-vector step per half.  Measured on an MI355X (tools/hop_bench.py, profiles/hop/; symmetrised RMAT, 20 hops,
+        medians of 9, the routes alternating): that sweep takes 4.1-4.2 ms at scale 20 and 26.9-27.8 ms at scale 23, while one 2-wide
+        pgh_spmm per hop for both halves takes 7.5-7.7 and 65.0-65.5 ms (disjoint spreads everywhere) -- a multi-seed pass of two
+        columns costs more than two resident steps, so that route was measured and not kept."""
+        from pygrank_amd.device import DeviceMatrix, DeviceVector
+        if g is None or g.shape[0] != g.shape[1] or hops < 1 or hops > 64 \
+                or any(not isinstance(p, DeviceVector) or len(p) != g.shape[0] for p in halves) \
+                or L.supervised_entry("pgh_pair_forms") is None or L.tune_entry("pgh_probe_auc") is None:
+            return None                                      # (a library without the slab measures: nothing to score the slabs with)
+        slabs = [DeviceMatrix.empty(len(p), hops) for p in halves]
+        for slab, p in zip(slabs, halves):
+            slab.set_column(0, p)
+        current = list(halves)
+        for i in range(1, hops):
+            current = [g.conv(p) for p in current]
+            stats["products"] += len(current)
+            for slab, p in zip(slabs, current):
+                slab.set_column(i, p)
+        stats["sweep"] = "steps"
+        return slabs
+
+    def _hop_values(self, M, propagated, measures, hops, stats):
+        """hop_tuner.py:94-101 -> (the hops x 2 list of values, the Arnoldi bases or None)."""
+        from pygrank_amd import backend, krylov
+        from pygrank_amd.device import DeviceMatrix
+        g = krylov._device_graph(M)
+        if self.basis == "krylov":
+            slabs = self._sweep_powers(g, propagated, hops, stats) if self.fused else None
+            if slabs is not None:
+                stats["route"] = "fused"
+                columns = [self._score(measure, slab, stats) for slab, measure in zip(slabs, measures)]
+                return [[column[i] for column in columns] for i in range(hops)], None
+            values = [None] * hops
+            for i in range(hops):
+                values[i] = [float(measure(p)) for p, measure in zip(propagated, measures)]
+                propagated = [backend.conv(p, g if g is not None else M) for p in propagated]
+                stats["products"] += len(propagated)
+            stats["scoring"] = ["columns"] * len(measures)
+            return values, None
+        runs = [krylov.arnoldi_run(M, p, hops, self.fused) for p in propagated]
+        basis = [run[0] for run in runs]
+        routes = set(run[2] for run in runs)
+        stats["route"] = "fused" if routes == {"fused"} else "primitive"
+        stats["sweep"] = "arnoldi:" + stats["route"]
+        stats["products"] += len(runs) * max(hops - 1, 0)
+        for run in runs:
+            stats["slab_passes"] += 2 * max(hops - 1, 0) if run[2] == "fused" else hops * (hops - 1)
+        if stats["route"] == "fused" and all(isinstance(base, DeviceMatrix) and base.b <= 64 for base in basis):
+            columns = [self._score(measure, base, stats) for base, measure in zip(basis, measures)]
+            return [[column[i] for column in columns] for i in range(hops)], basis
+        stats["scoring"] = ["columns"] * len(measures)
+        return [[float(measure(base.column(i))) for base, measure in zip(basis, measures)] for i in range(hops)], basis
+
+    def _tune(self, graph=None, personalization=None, *args, **kwargs):
+        from pygrank_amd import backend
+        from pygrank_amd.postprocess import Tautology
+        stats = self.last_tune = self._fresh_stats()
+        personalization = to_signal(graph, personalization)
+        graph = personalization.graph
+        backend_personalization = to_signal(personalization, backend.to_array(personalization.np))
+        hops = self.num_parameters + self.autoregression
+        M = self.ranker_generator([None] * hops).preprocessor(graph)
+        training, validation = split(backend_personalization, 0.8)
+        training1, training2 = split(training, 0.5)
+        propagated = [training1.np, training2.np]
+        measures = [self.measure(validation, training1), self.measure(validation, training2)]
+        measure_values, basis = self._hop_values(M, propagated, measures, hops, stats)
+        self.last_values = np.array(measure_values, dtype=np.float64)
+        best_parameters = hop_parameters(self.last_values, self.num_parameters, self.autoregression)
+        if self.tunable_offset is not None:
+            div = np.max(best_parameters)
+            if div != 0:
+                best_parameters = best_parameters / div
+            measure = self.tunable_offset(validation, training)
+            base = basis[0] if self.basis != "krylov" else None
+            self.last_pre_offset = np.array(best_parameters, dtype=np.float64)
+            loss = _HopOffsetLoss(self, measure, training, validation, best_parameters, base, args, kwargs)
+            best_offset = optimize(loss, max_vals=[1], min_vals=[0], deviation_tol=0.005, parameter_tol=1, partitions=5, divide_range=1.1)
+            self.last_offset = float(best_offset[0])
+            best_parameters = np.array([best_parameters[i] + best_offset[0] for i in range(len(best_parameters))], dtype=np.float64)
+        if np.sum(np.abs(best_parameters)) != 0:
+            best_parameters = best_parameters / np.mean(np.abs(best_parameters))
+        best_parameters = [float(param) for param in best_parameters]
+        self.last_params = best_parameters
+        if self.basis != "krylov":
+            return Tautology(), self._run(personalization, best_parameters, None, *args, **kwargs)
+        return self.ranker_generator(best_parameters), personalization
+
+    def _run(self, personalization, params, base=None, *args, **kwargs):
+        """hop_tuner.py:171-184: the filter of the normalised weights ("krylov"), or the weighted sum of the Arnoldi basis of the
+        personalization (of `base` where one is given): one pgh_mat_gemv."""
+        from pygrank_amd import krylov
+        from pygrank_amd.device import DeviceMatrix
+        params = np.array(params, dtype=np.float64)
+        div = np.sum(np.abs(params))
+        if div != 0:
+            params = params / div
+        if self.basis != "krylov":
+            if base is None:
+                M = self.ranker_generator(params).preprocessor(personalization.graph)
+                base, _, route = krylov.arnoldi_run(M, personalization.np, len(params), self.fused)
+                self.last_tune["products"] += max(len(params) - 1, 0)
+                self.last_tune["slab_passes"] += 2 * max(len(params) - 1, 0) if route == "fused" else len(params) * (len(params) - 1)
+            if isinstance(base, DeviceMatrix):
+                return to_signal(personalization, base.gemv(params))
+            ret = 0
+            for i in range(len(params)):
+                ret = ret + params[i] * base[:, i]
+            return to_signal(personalization, ret)
+        return self.ranker_generator([float(param) for param in params]).rank(personalization, *args, **kwargs)
 
 
 def _convergence_key(ranker):

@@ -15,7 +15,12 @@ Two routes:
     the entries (the host test double), where an entry declines, where the image has no resident form, and for more than 64
     dimensions (combine_cols holds any width: those run here and do not raise).
 
-A deliberate deviation: a breakdown -- the next Lanczos vector vanishes, the Krylov space is exhausted -- raises an Exception that says
+``arnoldi_iteration`` (krylov_space.py:60-85; its consumer is autotune.HopTuner) has the same two routes, chosen by its ``fused``
+argument (default False: the primitive loop, as before): the fused step is one product, one pgh_basis_dots, a k x k host solve and one
+pgh_arnoldi_close (include/pgh_arnoldi.h).  It never raises on an exhausted space: zero columns follow, as in
+the reference.
+
+A deliberate deviation of the Lanczos route: a breakdown -- the next Lanczos vector vanishes, the Krylov space is exhausted -- raises an Exception that says
 so.  The reference divides by zero there and returns NaN ranks.  "Vanishes" is |next_w| <= 2^-20 * sqrt(a_j^2 + b_{j-1}^2) (or an exact
 zero): |w|^2 = a_j^2 + b_{j-1}^2 + |next_w|^2 for orthogonal Lanczos vectors, and the f32 storage of w leaves rounding noise of about
 2^-24 |w| where the exact result is zero.
@@ -292,13 +297,10 @@ def krylov_error_bound(V, H, M, personalization, measure=measures.Mabs, max_powe
     return max(errors)
 
 
-def arnoldi_iteration(A, b, n):
-    """krylov_space.py:60-85: a basis of the Krylov subspace of A spanned from b by modified Gram-Schmidt, the reference's loop in
-    backend primitives.  Returns (Q as an [m, n] slab, h as an (n + 1) x n list of lists; upper Hessenberg)."""
-    graph = _device_graph(A)
-    A = graph if graph is not None else A
+def _arnoldi_primitive(A, b, n):
+    """krylov_space.py:75-85 as written, in backend primitives: 2 k vector passes at step k."""
     h = [[0 for _ in range(n)] for _ in range(n + 1)]
-    Q = [backend.self_normalize(backend.to_primitive(b))]
+    Q = [backend.self_normalize(b)]
     for k in range(1, n):
         v = backend.conv(Q[k - 1], A)
         for j in range(k):
@@ -307,3 +309,96 @@ def arnoldi_iteration(A, b, n):
         h[k][k - 1] = backend.dot(v, v) ** 0.5
         Q.append(v / h[k][k - 1] if h[k][k - 1] != 0 else v * 0)
     return backend.combine_cols(Q), h
+
+
+def _arnoldi_fused(g, b, n, dots, close):
+    """The fused route (include/pgh_arnoldi.h); None when an entry declined (nothing of the run is kept).
+
+    The slab holds the RAW columns r_j with a scale each, q_j = s_j r_j (s_0 = 1 / sum |b|: the reference's first column is L1-normalised).
+    With (m, rho) = _exact_multiplier(s_{k-1}) and w' = m M^T r_{k-1} the stored product (conv(q_{k-1}) = rho w'), step k is
+      c_j = s_j rho <r_j, w'>                                  one pgh_basis_dots
+      (I + strictly_lower(G)) h = c,  G_ji = <q_j, q_i>        the host, f64: the coefficients of modified Gram-Schmidt for ANY Q
+      r_k = w' - sum_j (h_j s_j / rho) r_j                     one pgh_arnoldi_close, written straight into column k
+      h_{k,k-1} = rho |r_k|,  s_k = 1 / |r_k|,  G_kj = s_k s_j <r_k, r_j>      from the sums the close returns
+    and one pgh_mat_div_cols over the finished slab normalises every column."""
+    lib = L.lib()
+    size, n_int, n_gather = len(b), g._n_int, g._n_gather
+    got = C.c_double()
+    r = DeviceVector.empty(n_int)
+    rg = DeviceVector.empty(n_gather) if n_gather else None
+    L.check(lib.pgh_resident_in(g._h, b._h, 0.0, r._h, None if rg is None else rg._h))
+    L.check(lib.pgh_reduce(L.ABSSUM, r._h, C.byref(got)))
+    scales = [1.0 / got.value if got.value != 0 else 1.0]
+    slab = DeviceMatrix.empty(n_int, n)
+    L.check(lib.pgh_mat_set_col(slab._h, 0, r._h))
+    h = [[0 for _ in range(n)] for _ in range(n + 1)]
+    gram = np.zeros((n, n))
+    for k in range(1, n):
+        m, rho = _exact_multiplier(scales[k - 1])
+        w = DeviceVector.empty(n_int)
+        wg = DeviceVector.empty(n_gather) if n_gather else None      # (the step entry writes the gather form of its outcome)
+        L.check(lib.pgh_resident_step(g._h, 0, r._h, None if rg is None else rg._h, m, None, 0.0, None, None, w._h,
+                                      None if wg is None else wg._h, None))
+        sums = np.zeros(k + 1)
+        status = dots(slab._h, k, w._h, sums.ctypes.data_as(L.c_f64p))
+        if status == L.ARNOLDI_DECLINED:
+            return None
+        L.check(status)
+        s = np.asarray(scales)
+        c = s * rho * sums[:k]
+        coefficients = np.zeros(k)
+        for j in range(k):                                   # the unit lower triangular solve
+            coefficients[j] = c[j] - gram[j, :j] @ coefficients[:j]
+        out = DeviceVector.empty(n_int)
+        status = close(slab._h, k, w._h, np.ascontiguousarray(coefficients * s / rho).ctypes.data_as(L.c_f64p), out._h, k,
+                       sums.ctypes.data_as(L.c_f64p))
+        if status == L.ARNOLDI_DECLINED:
+            return None
+        L.check(status)
+        for j in range(k):
+            h[j][k - 1] = float(coefficients[j])
+        raw_norm = sums[k] ** 0.5
+        h[k][k - 1] = float(rho * raw_norm)
+        scales.append(1.0 / raw_norm if raw_norm != 0 else 1.0)      # krylov_space.py:84: a vanished vector stays a zero column
+        gram[k, :k] = scales[k] * s * sums[:k]
+        r = out
+        if n_gather and k < n - 1:
+            rg = DeviceVector.empty(n_gather)
+            L.check(lib.pgh_resident_gather(g._h, r._h, rg._h))
+    slab = slab.div_cols([1.0 / s for s in scales])        # every column normalised at once (an f32 divisor per column)
+    columns = []
+    for column in slab.columns():
+        vec = DeviceVector.empty(size)
+        L.check(lib.pgh_resident_out(g._h, column._h, 1.0, vec._h))
+        columns.append(vec)
+    return DeviceMatrix.from_columns(columns), h
+
+
+def arnoldi_run(A, b, n, fused=False):
+    """(Q, h, route) of arnoldi_iteration: route is "fused" or "primitive"."""
+    n = int(n)
+    graph = _device_graph(A)
+    A = graph if graph is not None else A
+    b = getattr(b, "np", b)
+    dots = L.arnoldi_entry("pgh_basis_dots") if fused and graph is not None else None
+    close = L.arnoldi_entry("pgh_arnoldi_close") if dots is not None else None
+    if close is not None and 1 <= n <= L.ARNOLDI_MAX_DIMS and isinstance(b, DeviceVector) and graph.shape[0] == graph.shape[1] == len(b) \
+            and len(b) > 0 and graph._resident_lengths():
+        result = _arnoldi_fused(graph, b, n, dots, close)
+        if result is not None:
+            return result[0], result[1], "fused"
+    Q, h = _arnoldi_primitive(A, backend.to_primitive(b), n)
+    return Q, h, "primitive"
+
+
+def arnoldi_iteration(A, b, n, fused=False):
+    """krylov_space.py:60-85: a basis of the Krylov subspace of A spanned from b by modified Gram-Schmidt.  Returns (Q as an [m, n] slab
+    in the caller's ids, h as an (n + 1) x n list of lists; upper Hessenberg).
+
+    fused=False (default): the reference's loop in backend primitives -- a dot and an axpy per earlier column, 2 k vector passes at
+    step k.  fused=True: a step is one product in the graph's resident id space, one pgh_basis_dots, a k x k host solve and one
+    pgh_arnoldi_close (_arnoldi_fused).  Where the library lacks the entries (the host test double), where an
+    entry declines, where the image has no resident form or is not square, for more than 64 columns and for a host `b` the primitive
+    loop runs and nothing raises.  An exhausted space appends zero columns on either route, as in the reference."""
+    Q, h, _ = arnoldi_run(A, b, n, fused)
+    return Q, h

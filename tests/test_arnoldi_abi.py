@@ -1,0 +1,71 @@
+"""include/pgh_arnoldi.h at the C-ABI (no GPU): its table in _lib matches the header and is disjoint from the others, the Makefile builds
+its source against the header, the HIP library exports and binds both entries, and the host test double has neither."""
+import glob
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "pygrank_amd", "csrc", "libpgh_hip.so")
+ENTRIES = ["pgh_arnoldi_close", "pgh_basis_dots"]
+
+
+def _declared(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    return sorted(set(re.findall(r"\b(pgh_[a-z0-9_]+)\s*\(", text)))
+
+
+def _defined(header, name):
+    return int(re.search(r"#define\s+" + name + r"\s+(\d+)", open(os.path.join(ROOT, "include", header)).read()).group(1))
+
+
+@pytest.fixture(scope="module")
+def hip_lib():
+    if not os.path.exists(LIB):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "pygrank_amd", "csrc")])
+    return LIB
+
+
+def test_arnoldi_header_table_and_makefile_agree():
+    import ctypes as C
+    from pygrank_amd import _lib
+    assert sorted(_lib.ARNOLDI_SIGNATURES) == _declared("pgh_arnoldi.h") == ENTRIES
+    tables = [name for name in dir(_lib) if name.endswith("SIGNATURES") and name != "ARNOLDI_SIGNATURES"]
+    assert "SIGNATURES" in tables and "KRYLOV_SIGNATURES" in tables and "LINK_SIGNATURES" in tables
+    for name in tables:
+        assert set(_lib.ARNOLDI_SIGNATURES).isdisjoint(getattr(_lib, name)), name
+    headers = [os.path.basename(path) for path in glob.glob(os.path.join(ROOT, "include", "*.h"))]
+    assert "pgh.h" in headers and "pgh_arnoldi.h" in headers
+    for header in headers:
+        if header != "pgh_arnoldi.h":
+            assert set(ENTRIES).isdisjoint(_declared(header)), header
+    assert _lib.ARNOLDI_DECLINED == _defined("pgh_arnoldi.h", "PGH_ARNOLDI_DECLINED")
+    assert _lib.ARNOLDI_MAX_DIMS == _defined("pgh_arnoldi.h", "PGH_ARNOLDI_MAX_DIMS")
+    vec, mat, dblp = C.c_void_p, C.c_void_p, C.POINTER(C.c_double)
+    restype, argtypes = _lib.ARNOLDI_SIGNATURES["pgh_basis_dots"]
+    assert restype is C.c_int
+    assert argtypes == [mat, C.c_int32, vec, dblp]
+    restype, argtypes = _lib.ARNOLDI_SIGNATURES["pgh_arnoldi_close"]
+    assert restype is C.c_int
+    assert argtypes == [mat, C.c_int32, vec, dblp, vec, C.c_int32, dblp]
+    makefile = open(os.path.join(ROOT, "pygrank_amd", "csrc", "Makefile")).read()
+    assert re.search(r"^SRCS\s*=.*\bpgh_arnoldi\.hip\b", makefile, re.M)
+    assert re.search(r"^_build/%\.o:.*include/pgh_arnoldi\.h\b", makefile, re.M)
+
+
+def test_hip_library_exports_and_binds_the_arnoldi_entries(hip_lib):
+    from pygrank_amd import _lib
+    cdll = _lib.load_library(hip_lib)
+    bound = _lib.bind_arnoldi(cdll)
+    assert sorted(bound) == ENTRIES
+    for name in ENTRIES:
+        assert hasattr(cdll, name), name
+        assert bound[name] is not None and bound[name].argtypes == _lib.ARNOLDI_SIGNATURES[name][1], name
+
+
+def test_host_double_has_no_arnoldi_entry(host_engine):
+    from pygrank_amd import _lib
+    for name in _lib.ARNOLDI_SIGNATURES:
+        assert _lib.arnoldi_entry(name) is None, name
