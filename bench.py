@@ -1,6 +1,10 @@
 """bench.py -- headline benchmark of the propagation path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain `--gpus 1` run does what the headline needs and no more: it builds the graph, warms up, times the K steps, writes the
+outputs when --dump-outputs is given and prints the result line ("roofline", "cpu_baseline" and "parity" are null on it, "secondary"
+is empty).  `--full` adds every leg that takes runs of its own; what is said below about those objects holds for `--full`.
 
 Workload (SURVEY.md 8d / BASELINE.json configs[1]): personalized PageRank, alpha = 0.85, to tol = 1e-6 with the
 L1 residual (the "headline" stopping rule), on a synthetic RMAT graph (a, b, c, d) =
@@ -12,7 +16,7 @@ BASELINE.json configs[4] graph (scale 27, edge factor 8, ~1.07 B edges) at N = 8
 
 A "step" is one full PPR run (personalization resident in HBM -> converged ranks in HBM).  The timed region
 covers exactly K steps; value = nnz * (SpMV launches of all steps) / time  [edges*iterations/s, reported in
-GTEPS].  Extra objects on the JSON line: "roofline" (HIP-event time of EVERY launch of one PPR iteration -- block
+GTEPS].  Extra objects on the JSON line of a `--full` run: "roofline" (HIP-event time of EVERY launch of one PPR iteration -- block
 partial sums, the cold image's phase A, phase B + epilogue, residual, close -- vs the 8*nnz + 16*n algorithmic
 bytes of one iteration) and "cpu_baseline" (the oracle's scipy loop -- exactly the reference's numpy-backend
 arithmetic -- on the same graph, one core; the all-core OpenMP pull kernel beside it), plus the in-run parity of
@@ -182,7 +186,22 @@ def dump_outputs(out_dir, arrays):
         np.save(os.path.join(out_dir, name + ".npy"), values)
 
 
+def rebuild_graph(lib, L, scale, ef):
+    """--full: seconds of the same build again: what a rank() pays from its second call on when the caller does not promise
+    immutability (the reference's default: every rank() re-normalises and re-uploads, pygrank/core/utils/preprocessing.py:233-287)."""
+    from pygrank_amd.synthetic import rmat_graph
+    t0 = time.time()
+    again = rmat_graph(scale, ef, seed=0, normalization="col", **RMAT)
+    L.check(lib.pgh_sync())
+    rebuild_s = time.time() - t0
+    del again
+    return rebuild_s
+
+
 def single_gpu(args):
+    """The --gpus 1 run.  A plain run sets up, warms up, times the steps, dumps the last step's ranks when asked to and returns the
+    headline; the legs that take runs of their own (the rebuild, roofline, secondaries, CPU baseline + parity) belong to --full."""
+    full = getattr(args, "full", False)
     import pygrank_amd as pg
     from pygrank_amd import _lib as L
     from pygrank_amd.synthetic import rmat_graph
@@ -194,13 +213,7 @@ def single_gpu(args):
     L.check(lib.pgh_sync())
     build_s = time.time() - t0
     build_ms = build_profile(lib, L)                 # where that first build of the process spent its time (pgh_last_build_profile)
-    # ... and the same build again: what a rank() pays from its second call on when the caller does not promise immutability
-    # (the reference's default: every rank() re-normalises and re-uploads, pygrank/core/utils/preprocessing.py:233-287)
-    t0 = time.time()
-    again = rmat_graph(scale, ef, seed=0, normalization="col", **RMAT)
-    L.check(lib.pgh_sync())
-    rebuild_s = time.time() - t0
-    del again
+    rebuild_s = rebuild_graph(lib, L, scale, ef) if full else None
     g = adj.array
     n, nnz = g.shape[0], g.nnz
     out_deg = np.asarray(pg.degrees(g))              # row sums of M: > 0 <=> out-degree > 0
@@ -233,6 +246,17 @@ def single_gpu(args):
     gteps = nnz * spmv_total / elapsed / 1e9
     if getattr(args, "dump_outputs", None):         # what the last timed step handed its caller, read back after the clock stopped
         dump_outputs(args.dump_outputs, dict(ranks=ranks.np))
+    headline = dict(
+        metric="edges*iters/sec (GTEPS) for PPR alpha=0.85 to tol=1e-6", value=round(gteps, 2), unit="GTEPS", n_gpus=1,
+        steps=args.steps, warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 4), higher_is_better=True,
+        scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
+        config=dict(workload=f"single-GPU PPR on RMAT scale-{scale} ef-{ef} (BASELINE.json configs[1])", n=n, nnz=nnz,
+                    alpha=ALPHA, tol=TOL, error_type="L1", seeds=SEEDS, iterations_per_step=iters,
+                    spmv_per_step=spmv_total / args.steps, device_loop_ms_per_step=round(loop_ms_total / args.steps, 4),
+                    graph_build_s=round(build_s, 3), graph_rebuild_s=round(rebuild_s, 3) if full else None, graph_build_ms=build_ms,
+                    parallelism="1 GPU", runs_with_a_paused_in_kernel_residual=paused))
+    if not full:                                     # a plain run ends here: every leg below takes runs of its own
+        return dict(headline, roofline=None, cpu_baseline=None, parity=None, secondary={})
 
     # ---- roofline leg: HIP events around every launch of the dominant kernel (one extra, untimed run)
     L.check(lib.pgh_profile_reset())
@@ -405,16 +429,7 @@ def single_gpu(args):
                    all_cores=allcore_cpu_gteps(MT, nnz))
         parity = dict(rel_linf=float(np.max(np.abs(got - want)) / np.max(np.abs(want))), gpu_iterations=int(iters[-1]),
                       cpu_iterations=int(cpu_iters), bound=1e-6)
-    return dict(
-        metric="edges*iters/sec (GTEPS) for PPR alpha=0.85 to tol=1e-6", value=round(gteps, 2), unit="GTEPS", n_gpus=1,
-        steps=args.steps, warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 4), higher_is_better=True,
-        scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
-        config=dict(workload=f"single-GPU PPR on RMAT scale-{scale} ef-{ef} (BASELINE.json configs[1])", n=n, nnz=nnz,
-                    alpha=ALPHA, tol=TOL, error_type="L1", seeds=SEEDS, iterations_per_step=iters,
-                    spmv_per_step=spmv_total / args.steps, device_loop_ms_per_step=round(loop_ms_total / args.steps, 4),
-                    graph_build_s=round(build_s, 3), graph_rebuild_s=round(rebuild_s, 3), graph_build_ms=build_ms, parallelism="1 GPU",
-                    runs_with_a_paused_in_kernel_residual=paused),
-        roofline=roofline, cpu_baseline=cpu, parity=parity, secondary=secondary)
+    return dict(headline, roofline=roofline, cpu_baseline=cpu, parity=parity, secondary=secondary)
 
 
 _REAL_STDOUT = None
@@ -994,6 +1009,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scale", type=int, default=None, help="override the RMAT scale (default: 23 + log2(gpus))")
     ap.add_argument("--ef", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="--gpus 1: after the timed steps also run the legs that take runs of their own (roofline, secondaries, CPU "
+                         "baseline + parity; the rebuild of the graph before them); the --no-* switches below pick among them.  A run "
+                         "of N > 1 ranks always has its legs")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / parity leg")
     ap.add_argument("--no-secondary", action="store_true", help="skip the side measurements (other stopping rules / filters)")
     ap.add_argument("--no-weighted", action="store_true", help="skip the real-valued-weights side measurement")

@@ -7,7 +7,7 @@ import bench
 
 
 def test_single_gpu_leg_fields(host_engine):
-    args = argparse.Namespace(gpus=1, steps=2, warmup=1, scale=10, ef=8, no_cpu=False, no_secondary=False, no_symmetric=False)
+    args = argparse.Namespace(gpus=1, steps=2, warmup=1, scale=10, ef=8, no_cpu=False, no_secondary=False, no_symmetric=False, full=True)
     out = bench.single_gpu(args)
     line = json.loads(json.dumps(out))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -36,6 +36,63 @@ def test_single_gpu_leg_fields(host_engine):
     assert line["roofline"]["frac_of_measured_copy"] is not None and "residual" in line["roofline"]["kernel"]
     assert line["cpu_baseline"]["all_cores"]["cores"] >= 1
     assert line["secondary"]["heat_kernel_t5_31_iterations"]["spmv_per_run"] in (29, 30)
+
+
+def test_plain_run_is_the_headline_alone(host_engine, tmp_path, monkeypatch):
+    """Without --full the single-GPU leg sets up, warms up, times its steps, dumps and returns: one rank() per warm-up and timed step and
+    one graph build, the headline's fields as --full reports them, the legs' objects empty; --full times the same steps on the same
+    inputs (equal iteration counts, the same dumped bits)."""
+    import numpy as np
+    import pygrank_amd as pg
+    from pygrank_amd import synthetic
+    calls = dict(rank=0, build=0)
+    rank, rmat_graph = pg.PageRank.rank, synthetic.rmat_graph
+
+    def counted_rank(self, *a, **k):
+        calls["rank"] += 1
+        return rank(self, *a, **k)
+
+    def counted_build(*a, **k):
+        calls["build"] += 1
+        return rmat_graph(*a, **k)
+    monkeypatch.setattr(pg.PageRank, "rank", counted_rank)
+    monkeypatch.setattr(synthetic, "rmat_graph", counted_build)
+
+    def leg(full, tag):
+        calls.update(rank=0, build=0)
+        args = argparse.Namespace(gpus=1, steps=3, warmup=2, scale=10, ef=8, no_cpu=True, no_secondary=True, no_symmetric=True,
+                                  dump_outputs=str(tmp_path / tag), full=full)
+        line = json.loads(json.dumps(bench.single_gpu(args)))
+        return line, np.load(tmp_path / tag / "ranks.npy"), dict(calls)
+
+    plain, plain_ranks, plain_calls = leg(False, "plain")
+    whole, whole_ranks, whole_calls = leg(True, "full")
+    assert plain_calls == dict(rank=5, build=1), plain_calls
+    assert whole_calls == dict(rank=6, build=2), whole_calls                  # + the roofline leg's run, + the rebuild
+    assert list(plain) == list(whole)                                         # the same keys in the same order
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["parity"] is None and plain["secondary"] == {}
+    assert whole["roofline"]["bound"] == "hbm"
+    for key in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
+        assert plain[key] == whole[key], key
+    assert plain["steps"] == 3 and plain["warmup"] == 2 and plain["ms_per_step"] > 0 and plain["value"] >= 0
+    assert list(plain["config"]) == list(whole["config"])
+    assert plain["config"]["graph_rebuild_s"] is None and whole["config"]["graph_rebuild_s"] >= 0
+    for key in ("workload", "n", "nnz", "iterations_per_step", "spmv_per_step"):
+        assert plain["config"][key] == whole["config"][key], key
+    assert np.array_equal(plain_ranks, whole_ranks)
+
+
+def test_full_is_an_option_of_the_command_line(monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps N --warmup W` is the plain run; --full is off unless given."""
+    seen = []
+    monkeypatch.setattr(bench, "single_gpu", lambda args: seen.append(args) or dict(value=0.0))
+    for key in ("RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(key, raising=False)
+    for extra, want in (([], False), (["--full"], True)):
+        monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"] + extra)
+        bench.main()
+        assert seen[-1].full is want and seen[-1].steps == 2 and seen[-1].warmup == 1
+    assert [json.loads(ln) for ln in capsys.readouterr().out.splitlines()] == [dict(value=0.0)] * 2
 
 
 def test_dump_outputs_are_the_last_timed_step(host_engine, tmp_path):
