@@ -35,7 +35,7 @@ from pygrank_amd.filters import (AbsorbingWalks, ClosedFormGraphFilter, GenericG
 from pygrank_amd.krylov import arnoldi_iteration, krylov2original, krylov_base, krylov_error_bound
 from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector
 from pygrank_amd.autotune import AlgorithmSelection, HopTuner, ParameterTuner, SelfClearDict, Tuner, hop_parameters, optimize
-from pygrank_amd.comparables import create_demo_filters, create_many_filters, create_variations
+from pygrank_amd.comparables import create_demo_filters, create_many_filters, create_many_variation_types, create_variations
 from pygrank_amd.fairness import AdHocFairness, FairPersonalizer
 from pygrank_amd.oversampling import BoostedSeedOversampling, SeedOversampling
 from pygrank_amd.multigroup import ClusteringCoefficient, LinkAssessment, MultiSupervised, MultiUnsupervised

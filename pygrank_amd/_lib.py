@@ -3,7 +3,7 @@ include/pgh_tune.h, the unsupervised measures' entries of include/pgh_measure.h,
 include/pgh_supervised.h, the prior-editing entry of include/pgh_fair.h, the mixed batches of include/pgh_mixed.h, the locally fair PageRank's entries of
 include/pgh_lfpr.h, the seed oversampling passes of include/pgh_oversample.h, the rank-based measures' entries of include/pgh_rank.h,
 the Krylov-space filters' entries of include/pgh_krylov.h, the multi-group measures' entries of include/pgh_link.h, the Arnoldi
-passes of include/pgh_arnoldi.h).
+passes of include/pgh_arnoldi.h, the postprocessors' slab passes of include/pgh_post.h).
 
 The product binds exactly one library: ``pygrank_amd/csrc/libpgh_hip.so`` (hand-written HIP for gfx950).
 There is NO CPU fallback: if the library is missing, if it reports a runtime other than ``hip:*``, or if no MI355X is
@@ -333,6 +333,19 @@ ARNOLDI_SIGNATURES = {
 ARNOLDI_DECLINED = 2      # include/pgh_arnoldi.h PGH_ARNOLDI_DECLINED: nothing was written, the caller takes the backend-primitive route
 ARNOLDI_MAX_DIMS = 64     # include/pgh_arnoldi.h PGH_ARNOLDI_MAX_DIMS
 
+# name -> (restype, argtypes); every symbol include/pgh_post.h declares.  Bound apart like the Arnoldi entries (post_entry): on a library
+# without them a postprocessor's propagate transforms the columns of the inner ranker's batch one by one.
+POST_SIGNATURES = {
+    "pgh_post_kth_largest": (C.c_int, [c_mat, C.c_int64, c_f64p]),
+    "pgh_post_col_threshold": (C.c_int, [c_mat, c_f64p, C.c_int32, c_mat]),
+    "pgh_post_col_affine": (C.c_int, [c_mat, c_f64p, c_f64p, c_mat]),
+    "pgh_post_row_op": (C.c_int, [c_mat, c_vec, C.c_int32, C.c_double, c_mat]),
+    "pgh_post_ordinals": (C.c_int, [c_mat, c_mat]),
+}
+POST_DECLINED = 2         # include/pgh_post.h PGH_POST_DECLINED: nothing was written, the caller takes the columns route
+POST_MAX_COLS = 64        # include/pgh_post.h PGH_POST_MAX_COLS
+POST_ROW_SUB, POST_ROW_SWEEP = 0, 1                                                 # include/pgh_post.h PGH_POST_ROW_*
+
 _lib = None
 _initialised = False
 ACCEPTED_RUNTIMES = ("hip:",)      # pgh_runtime_name() prefixes ensure_init() agrees to drive
@@ -422,6 +435,21 @@ def bind_link(cdll):
 def bind_arnoldi(cdll):
     """Binds the include/pgh_arnoldi.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
     return _bind_optional(cdll, ARNOLDI_SIGNATURES)
+
+
+def bind_post(cdll):
+    """Binds the include/pgh_post.h entries `cdll` exports; returns {name: function or None when the library lacks it}."""
+    return _bind_optional(cdll, POST_SIGNATURES)
+
+
+def post_entry(name):
+    """The bound include/pgh_post.h entry `name` of the loaded library, or None when that library does not export it."""
+    cdll = lib()
+    cache = getattr(cdll, "_pgh_post_entries", None)
+    if cache is None:
+        cache = bind_post(cdll)
+        cdll._pgh_post_entries = cache
+    return cache[name]
 
 
 def arnoldi_entry(name):

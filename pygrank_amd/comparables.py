@@ -2,10 +2,13 @@
 
 The filters of one family share their preprocessor (one uploaded graph image per normalisation), which is also what lets
 ``AlgorithmSelection`` run a family's PageRanks as one mixed batch and its closed-form filters as another (include/pgh_mixed.h).
-``create_variations`` takes ``{"+SO": SeedOversampling, "+BSO": BoostedSeedOversampling}`` (pygrank_amd/oversampling.py);
-``create_many_variation_types`` is not restated.
+``create_variations`` takes ``{"+SO": SeedOversampling, "+BSO": BoostedSeedOversampling}`` (pygrank_amd/oversampling.py) or the six
+wrappers of ``create_many_variation_types``.  Its ``SweepO`` and ``SweepNeigh`` members hand ``SeedOversampling`` a wrapped ranker:
+``Sweep.propagate`` keeps that ranker's batch (pygrank_amd/postprocess.py), so a round of seed sets is still one multi-seed run.
 """
 from pygrank_amd.filters import AbsorbingWalks, HeatKernel, PageRank
+from pygrank_amd.oversampling import SeedOversampling
+from pygrank_amd.postprocess import Sweep, Tautology
 from pygrank_amd.preprocessing import preprocessor as _preprocessor
 
 
@@ -37,6 +40,17 @@ def create_many_filters(tol=1.E-6, max_iters=10000):
     add("HK", ("", "L"), ((("1", 1), ("3", 3), ("5", 5), ("7", 7)), "", lambda t, kw: HeatKernel(t=t, **kw)))
     add("Absorb", ("L", ""), (alphas, ".", lambda alpha, kw: AbsorbingWalks(alpha=alpha, **kw)))
     return family
+
+
+def create_many_variation_types():
+    """comparables.py:80-87: name suffix -> callable(ranker) -> ranker: as it is, swept, seed-oversampled ("safe" and "neighbors"), and
+    swept inside either oversampling."""
+    return {"": Tautology,
+            "Sweep": Sweep,
+            "O": lambda ranker: SeedOversampling(ranker, "safe"),
+            "SweepO": lambda ranker: SeedOversampling(Sweep(ranker), "safe"),
+            "Neigh": lambda ranker: SeedOversampling(ranker, "neighbors"),
+            "SweepNeigh": lambda ranker: SeedOversampling(Sweep(ranker), "neighbors")}
 
 
 def create_variations(algorithms, variations):

@@ -836,6 +836,58 @@ class DeviceMatrix:
         L.check(L.lib().pgh_mat_gemm(self._h, _ptr(c), int(c.shape[0]), int(c.shape[1]), 1 if accumulate else 0, out._h))
         return out
 
+    # ---- the postprocessors' slab passes (include/pgh_post.h, at most 64 columns).  Each returns None when the loaded library lacks the
+    # entry or the entry declines: nothing was written, the caller goes column by column.
+    def _post(self, name, *args):
+        entry = L.post_entry(name)
+        if entry is None:
+            return False
+        status = entry(self._h, *args)
+        if status == L.POST_DECLINED:
+            return False
+        L.check(status)
+        return True
+
+    def col_stats(self):
+        """[b, 4]: every column's sum, sum of squares, max and min (pgh_mat_col_stats)."""
+        entry = L.measure_entry("pgh_mat_col_stats")
+        if entry is None or self.b > 64:
+            return None
+        out = np.empty((self.b, 4), dtype=np.float64)
+        L.check(entry(self._h, _ptr(out)))
+        return out
+
+    def kth_largest(self, k):
+        """Every column's k-th largest value (pgh_post_kth_largest, a radix select: no sort)."""
+        out = np.empty(self.b, dtype=np.float64)
+        return out if self._post("pgh_post_kth_largest", int(k), out.ctypes.data_as(L.c_f64p)) else None
+
+    def col_threshold(self, cuts, inclusive=False):
+        """1 where self[:, j] >= cuts[j] (inclusive) or > cuts[j], 0 elsewhere."""
+        cuts = np.ascontiguousarray(cuts, dtype=np.float64)
+        out = DeviceMatrix.empty(self.n, self.b)
+        return out if self._post("pgh_post_col_threshold", cuts.ctypes.data_as(L.c_f64p), 1 if inclusive else 0, out._h) else None
+
+    def col_affine(self, sub, div):
+        """(self[:, j] - sub[j]) / div[j]; a zero divisor copies the column."""
+        sub, div = np.ascontiguousarray(sub, dtype=np.float64), np.ascontiguousarray(div, dtype=np.float64)
+        out = DeviceMatrix.empty(self.n, self.b)
+        return out if self._post("pgh_post_col_affine", sub.ctypes.data_as(L.c_f64p), div.ctypes.data_as(L.c_f64p), out._h) else None
+
+    def row_op(self, vec, op, offset=0.0):
+        """self[i, :] - vec[i] (POST_ROW_SUB) or self[i, :] / (vec[i] + offset) (POST_ROW_SWEEP)."""
+        out = DeviceMatrix.empty(self.n, self.b)
+        return out if self._post("pgh_post_row_op", vec._h, int(op), float(offset), out._h) else None
+
+    def ordinals(self):
+        """DeviceVector.ordinals of every column."""
+        out = DeviceMatrix.empty(self.n, self.b)
+        return out if self._post("pgh_post_ordinals", out._h) else None
+
+    def flat(self):
+        """The slab's storage as one vector of n * b entries (a view: it keeps the slab alive)."""
+        return DeviceVector.wrap(L.lib().pgh_mat_ptr(self._h), self.n * self.b, keepalive=self)
+
     def set_column(self, j, vec):
         L.check(L.lib().pgh_mat_set_col(self._h, int(j), vec._h))
 

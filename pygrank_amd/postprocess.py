@@ -5,19 +5,97 @@ the callable form of ``use_quotient`` (abstract_filters.py:131-132; the referenc
 ``Normalize``, tests/test_filters.py:41-82).  ``Ordinals`` / ``Top`` / ``Threshold`` / ``Transformer`` / ``Sweep`` /
 ``LinearSweep`` are SURVEY.md 8f-3: elementwise kernels, device reductions and one device radix sort instead of the
 reference's per-node Python dictionaries.  Behaviour follows pygrank/algorithms/postprocess/postprocess.py:7-80,106-290,
-353-450.  The fairness postprocessors are in pygrank_amd/fairness.py, the seed oversampling ones in pygrank_amd/oversampling.py;
+353-450.  ``propagate`` keeps the inner ranker's batch: the inner ``propagate`` runs once and its [n, b] slab goes through the
+passes of include/pgh_post.h (a multi-column radix select for ``Top``, one slab pass each for the others), so a
+chain such as ``PageRank() >> Sweep() >> Normalize() >> Top(10)`` stays on the device between the multi-seed loop and the measures'
+``evaluate_many``.  The fairness postprocessors are in pygrank_amd/fairness.py, the seed oversampling ones in pygrank_amd/oversampling.py;
 subgraph extraction stays out of scope."""
+from pygrank_amd import _lib as L
 from pygrank_amd import backend
-from pygrank_amd.device import DeviceVector
-from pygrank_amd.signals import NodeRanking, to_signal
+from pygrank_amd.device import DeviceMatrix, DeviceVector
+from pygrank_amd.signals import GraphSignal, NodeRanking, to_signal
 from pygrank_amd.utils import call, ensure_used_args, remove_used_args
 
 
+CHUNK = L.POST_MAX_COLS        # most columns of one include/pgh_post.h call
+
+
+def _definer(cls, name):
+    for base in cls.__mro__:
+        if name in vars(base):
+            return base
+    return None
+
+
+def _as_slab(features):
+    F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
+    return F if isinstance(F, DeviceMatrix) else DeviceMatrix.from_columns([F])
+
+
+class _Calls(dict):
+    """The engine calls of one ``propagate``, by entry name."""
+
+    def add(self, name, times=1):
+        self[name] = self.get(name, 0) + times
+
+
 class Postprocessor(NodeRanking):
-    """A ranker wrapped around another ranker: ``rank`` runs the inner one and passes its outcome through ``_transform``."""
+    """A ranker wrapped around another ranker: ``rank`` runs the inner one and passes its outcome through ``_transform``.
+
+    ``propagate`` of a class with a slab form (``_slab``: Normalize, Ordinals, Transformer, Top, Threshold, Sweep, LinearSweep) runs the
+    inner ranker's ``propagate`` ONCE and transforms its outcome.  Two switches, class attributes an instance may set to False:
+    ``batch = False`` is one ``rank()`` per column (NodeRanking.propagate); ``fused = False`` keeps the inner batch but sends its columns
+    through ``_apply`` one by one, on backend primitives.  After a call ``last_propagate`` holds the route ("slab": the entries of
+    include/pgh_post.h, "columns": the inner batch's columns one by one -- also what a library without the entries or a declined call
+    takes --, "ranks": one ``rank()`` per column), the widths of the chunks (at most 64 columns) and the engine calls made for the
+    transformation.  A subclass without a slab form, or one that overrides what the slab form stands for, takes "ranks"."""
+
+    batch = True
+    fused = True
+    _slab = None        # (self, graph, chunk, calls) -> the transformed [n, b <= 64] slab, or None when the engine does not serve it
 
     def __init__(self, ranker=None):
         self.ranker = ranker
+
+    def _has_slab_form(self):
+        cls = type(self)
+        owner = _definer(cls, "_slab")
+        if owner is None or vars(owner)["_slab"] is None or self.ranker is None:
+            return False
+        # the slab form restates _values / _transform / _apply of its own class: a subclass that changes one of them is not restated
+        return all(issubclass(owner, _definer(cls, name)) for name in ("_values", "_transform", "_apply", "transform", "rank")
+                   if _definer(cls, name) is not None)
+
+    def propagate(self, graph, features, *args, **kwargs):
+        calls = _Calls()
+        self.last_propagate = dict(route="ranks", chunks=[], calls=calls)
+        if not self.batch or not self._has_slab_form():
+            return super().propagate(graph, features, *args, **kwargs)
+        inner = self.ranker.propagate(graph, features, *args, **kwargs)
+        leftover = remove_used_args(self.ranker.rank, kwargs)      # keywords the inner ranker did not take, as in rank
+        plain = graph.graph if isinstance(graph, GraphSignal) else graph
+        # (a keyword that _transform has a parameter for would reach it through _apply: the columns route lets it)
+        reaching = len(leftover) - len(remove_used_args(self._transform, leftover))
+        served = all(L.post_entry(name) is not None for name in L.POST_SIGNATURES)      # (a library has all of the header or none)
+        if self.fused and served and isinstance(inner, DeviceMatrix) and inner.n > 0 and not reaching:
+            widths = [min(CHUNK, inner.b - first) for first in range(0, inner.b, CHUNK)]
+            out = DeviceMatrix.empty(inner.n, inner.b) if inner.b > CHUNK else None
+            for first, width in zip(range(0, inner.b, CHUNK), widths):
+                chunk = inner if out is None else inner.get_cols(first, width)
+                done = self._slab(plain, chunk, calls)
+                if done is None:
+                    break
+                if out is None:
+                    out = done
+                else:
+                    out.set_cols(first, done)
+            else:
+                self.last_propagate.update(route="slab", chunks=widths)
+                return out
+            calls.clear()
+        self.last_propagate.update(route="columns", chunks=[inner.b] if isinstance(inner, DeviceMatrix) else [])
+        columns = [self._apply(to_signal(graph, column), leftover)._np for column in backend.separate_cols(inner)]
+        return backend.combine_cols(columns)
 
     def _transform(self, ranks, **kwargs):
         raise Exception("_transform method not implemented for the class " + type(self).__name__)
@@ -66,6 +144,16 @@ class Tautology(Postprocessor):
         inner = self.ranker
         return to_signal(graph, personalization) if inner is None else inner.rank(graph, personalization, *args, **kwargs)
 
+    def propagate(self, graph, features, *args, **kwargs):
+        """The inner ranker's ``propagate``; without one the features themselves, as a slab."""
+        self.last_propagate = dict(route="ranks", chunks=[], calls=_Calls())
+        if not self.batch or type(self).rank is not Tautology.rank:
+            return super().propagate(graph, features, *args, **kwargs)
+        out = _as_slab(features) if self.ranker is None else self.ranker.propagate(graph, features, *args, **kwargs)
+        if isinstance(out, DeviceMatrix):
+            self.last_propagate.update(route="slab", chunks=[min(CHUNK, out.b - first) for first in range(0, out.b, CHUNK)])
+        return out
+
 
 def _is_ranker(obj):
     return callable(getattr(obj, "rank", None))
@@ -103,6 +191,23 @@ class Normalize(_NoOptions):
             return ranks                                           # constant (or zero) signals stay as they are
         return (x - low) / (high - low)
 
+    def _slab(self, graph, chunk, calls):
+        """Every method from one pgh_mat_col_stats (sum, sum of squares, max, min per column), then (x - low) / (high - low) as
+        pgh_post_col_affine; a column with high == low is copied."""
+        how = self.method
+        if how not in self._METHODS:
+            raise Exception("Normalize: method must be one of " + ", ".join(self._METHODS) + ", not " + repr(how))
+        stats = chunk.col_stats()
+        if stats is None:
+            return None
+        calls.add("pgh_mat_col_stats")
+        low = [float(s[3]) if how == "range" else 0.0 for s in stats]
+        high = [float({"sum": s[0], "L2": float(s[1]) ** 0.5}.get(how, s[2])) for s in stats]
+        out = chunk.col_affine(low, [0.0 if h == l else h - l for h, l in zip(high, low)])      # 0: constant (or zero) columns stay
+        if out is not None:
+            calls.add("pgh_post_col_affine")
+        return out
+
 
 def _device(ranks):
     x = ranks.np
@@ -125,6 +230,12 @@ class Ordinals(_NoOptions):
     def _values(self, ranks):
         return _device(ranks).ordinals()
 
+    def _slab(self, graph, chunk, calls):
+        out = chunk.ordinals()
+        if out is not None:
+            calls.add("pgh_post_ordinals")
+        return out
+
 
 class Transformer(_NoOptions):
     """Element-by-element expression, backend.exp by default (postprocess.py:198-243)."""
@@ -133,9 +244,20 @@ class Transformer(_NoOptions):
         ranker, expr = _swap(ranker, expr)
         super().__init__(ranker)
         self.expr = backend.exp if expr is None else expr
+        self._default_expr = self.expr if expr is None else None
 
     def _values(self, ranks):
         return self.expr(ranks.np)
+
+    def _slab(self, graph, chunk, calls):
+        """The default expression is one pgh_ewise_unary over the slab's storage, n * b entries; any other goes column by column."""
+        if self._default_expr is None or self.expr is not self._default_expr:
+            return None
+        out = DeviceMatrix.empty(chunk.n, chunk.b)
+        source, target = chunk.flat(), out.flat()                     # (the views live until the call has been made)
+        L.check(L.lib().pgh_ewise_unary(L.EXP, source._h, target._h))
+        calls.add("pgh_ewise_unary")
+        return out
 
 
 class Top(_NoOptions):
@@ -154,6 +276,21 @@ class Top(_NoOptions):
         threshold = x.kth_largest(keep) if 1 <= keep <= len(x) else 0     # the reference's loop leaves 0 otherwise
         return (x >= threshold) * 1.0
 
+    def _slab(self, graph, chunk, calls):
+        """Every column's cut from one radix select (pgh_post_kth_largest), then one compare pass (pgh_post_col_threshold)."""
+        keep = self.fraction_of_training
+        keep = int(keep * chunk.n) if keep < 1 else int(keep)
+        cuts = [0.0] * chunk.b                                         # the reference's loop leaves 0 for a keep outside [1, n]
+        if 1 <= keep <= chunk.n:
+            cuts = chunk.kth_largest(keep)
+            if cuts is None:
+                return None
+            calls.add("pgh_post_kth_largest")
+        out = chunk.col_threshold(cuts, inclusive=True)
+        if out is not None:
+            calls.add("pgh_post_col_threshold")
+        return out
+
 
 class Threshold(_NoOptions):
     """1 above a threshold, 0 elsewhere (postprocess.py:293-350); "gap" = the score after the largest relative drop."""
@@ -170,6 +307,19 @@ class Threshold(_NoOptions):
         cut = x.gap_threshold() if self.threshold == "gap" else self.threshold
         return ((x >= cut) if self.inclusive else (x > cut)) * 1.0
 
+    def _slab(self, graph, chunk, calls):
+        """A fixed cut goes straight to pgh_post_col_threshold; "gap" takes every column's cut from pgh_vec_gap_threshold first."""
+        if self.threshold == "gap":
+            cuts = [column.gap_threshold() for column in chunk.columns()]
+            calls.add("pgh_mat_get_col", chunk.b)
+            calls.add("pgh_vec_gap_threshold", chunk.b)
+        else:
+            cuts = [float(self.threshold)] * chunk.b
+        out = chunk.col_threshold(cuts, inclusive=bool(self.inclusive))
+        if out is not None:
+            calls.add("pgh_post_col_threshold")
+        return out
+
 
 class _UniformBaseline(_NoOptions):
     """Sweep family: personalized ranks set against the same ranker's non-personalized outcome, computed once per graph."""
@@ -180,10 +330,20 @@ class _UniformBaseline(_NoOptions):
         self._baseline = {}
 
     def _uniforms(self, ranks):
-        key = id(ranks.graph)
+        return self._uniforms_on(ranks.graph)
+
+    def _uniforms_on(self, graph):
+        key = id(graph)
         if key not in self._baseline:
-            self._baseline[key] = (ranks.graph, _device(self.uniform_ranker.rank(ranks.graph)))   # keeps the graph alive: ids are not reused
+            self._baseline[key] = (graph, _device(self.uniform_ranker.rank(graph)))   # keeps the graph alive: ids are not reused
         return self._baseline[key][1]
+
+    def _row_slab(self, graph, chunk, calls, op, offset=0.0):
+        """One baseline vector per graph, then one pgh_post_row_op over the slab."""
+        out = chunk.row_op(self._uniforms_on(graph), op, offset)
+        if out is not None:
+            calls.add("pgh_post_row_op")
+        return out
 
     def __lshift__(self, ranker):
         self.uniform_ranker = super().__lshift__(ranker)
@@ -196,9 +356,15 @@ class Sweep(_UniformBaseline):
     def _values(self, ranks):
         return _device(ranks) / (self._uniforms(ranks) + 1.E-12)
 
+    def _slab(self, graph, chunk, calls):
+        return self._row_slab(graph, chunk, calls, L.POST_ROW_SWEEP, 1.E-12)
+
 
 class LinearSweep(_UniformBaseline):
     """ranks - uniform ranks (postprocess.py:407-450)."""
 
     def _values(self, ranks):
         return _device(ranks) - self._uniforms(ranks)
+
+    def _slab(self, graph, chunk, calls):
+        return self._row_slab(graph, chunk, calls, L.POST_ROW_SUB)
