@@ -19,7 +19,7 @@ from random import random
 import numpy as np
 
 from pygrank_amd import _lib as L
-from pygrank_amd.measures import AUC, Cos, split
+from pygrank_amd.measures import AUC, Cos, _ProbePlan, split
 from pygrank_amd.preprocessing import preprocessor
 from pygrank_amd.signals import NodeRanking, to_signal
 from pygrank_amd.utils import ensure_used_args, remove_used_args
@@ -171,25 +171,6 @@ class Tuner(NodeRanking):
         raise Exception("Tuners should implement a _tune method")
 
 
-class _ProbePlan:
-    """The node classes of one validation split on the device (pgh_probe_plan_create, include/pgh_tune.h)."""
-
-    def __init__(self, known, exclude):
-        self._h = L.c_plan()
-        L.check(L.tune_entry("pgh_probe_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
-        pos, neg = C.c_int64(), C.c_int64()
-        L.check(L.tune_entry("pgh_probe_plan_info")(self._h, C.byref(pos), C.byref(neg)))
-        self.num_positive, self.num_negative = pos.value, neg.value
-
-    def __del__(self):
-        try:
-            if self._h is not None and L._lib is not None:
-                L.tune_entry("pgh_probe_plan_destroy")(self._h)
-        except Exception:
-            pass
-        self._h = None
-
-
 class _ProbeLoss:
     """The tuner's loss for its default setting: ``loss(params)`` is the reference's one-probe evaluation
     (parameterized.py:135-145), ``loss.many(candidates)`` scores a coordinate step's candidates together.
@@ -220,7 +201,7 @@ class _ProbeLoss:
 
     def _fused(self, index, validation, exclude, slab, coefficients):
         """[AUC of every column of `coefficients`] through pgh_probe_auc, or None when the entry is missing or declines."""
-        entry = L.tune_entry("pgh_probe_auc")
+        entry = L.entry("pgh_probe_auc")
         if entry is None or slab.chebyshev or len(slab.slabs) < 1:     # (more than one slab of terms: the entry declines)
             return None
         plan = self._plan(index, validation, exclude)
@@ -228,7 +209,7 @@ class _ProbeLoss:
         flat = np.ascontiguousarray(coefficients, dtype=np.float64)
         out = (C.c_double * probes)()
         status = entry(slab.slabs[0]._h, flat.ctypes.data_as(C.c_void_p), terms, probes, plan._h, out)
-        if status == L.TUNE_DECLINED:
+        if status == L.DECLINED:
             if plan.num_positive == 0 or plan.num_negative == 0:
                 raise Exception("Cannot evaluate AUC when all labels are the same")
             return None
@@ -553,7 +534,7 @@ class HopTuner(Tuner):
         from pygrank_amd.device import DeviceMatrix, DeviceVector
         if g is None or g.shape[0] != g.shape[1] or hops < 1 or hops > 64 \
                 or any(not isinstance(p, DeviceVector) or len(p) != g.shape[0] for p in halves) \
-                or L.supervised_entry("pgh_pair_forms") is None or L.tune_entry("pgh_probe_auc") is None:
+                or L.entry("pgh_pair_forms") is None or L.entry("pgh_probe_auc") is None:
             return None                                      # (a library without the slab measures: nothing to score the slabs with)
         slabs = [DeviceMatrix.empty(len(p), hops) for p in halves]
         for slab, p in zip(slabs, halves):
@@ -741,7 +722,7 @@ class AlgorithmSelection(Tuner):
         """Ranks the (ranker, split) pairs of one group as mixed batches.  columns_of[split] gains (ranker index, ranks vector) pairs;
         returns False (nothing gained) when the entry is missing or declines."""
         from pygrank_amd.device import DeviceMatrix
-        entry = L.mixed_entry("pgh_ppr_run_batch_mixed" if kind == "mixed_ppr" else "pgh_poly_run_batch_mixed")
+        entry = L.entry("pgh_ppr_run_batch_mixed" if kind == "mixed_ppr" else "pgh_poly_run_batch_mixed")
         if entry is None:
             return False
         first = rankers[members[0]]
@@ -770,7 +751,7 @@ class AlgorithmSelection(Tuner):
                 schedule = {r: rankers[r]._coefficient_schedule(terms) for r in members}
                 coeffs = np.ascontiguousarray(np.array([schedule[r] for r, _ in chunk], dtype=np.float64).T.reshape(terms, slab.b))
                 status = entry(g._h, P._h, coeffs.ctypes.data_as(C.c_void_p), terms, R._h, C.byref(cfg), scales, results)
-            if status == L.MIXED_DECLINED and not gained:
+            if status == L.DECLINED and not gained:
                 return False
             L.check(status)
             calls.append(dict(kind=kind, width=slab.b, iterations=[res.iterations for res in results], loop_ms=results[0].loop_ms))

@@ -19,6 +19,19 @@ def _ptr(arr):
     return arr.ctypes.data_as(C.c_void_p)
 
 
+class EnginePlan:
+    """An engine-side plan of an optional header: `_h` is its handle (None while there is none), `_DESTROY` the entry that frees it."""
+    _DESTROY = None
+
+    def __del__(self):
+        try:
+            if self._h is not None and L._lib is not None:
+                L.entry(self._DESTROY)(self._h)
+        except Exception:
+            pass
+        self._h = None
+
+
 class DeviceVector:
     """Dense f32 vector in HBM."""
 
@@ -839,18 +852,12 @@ class DeviceMatrix:
     # ---- the postprocessors' slab passes (include/pgh_post.h, at most 64 columns).  Each returns None when the loaded library lacks the
     # entry or the entry declines: nothing was written, the caller goes column by column.
     def _post(self, name, *args):
-        entry = L.post_entry(name)
-        if entry is None:
-            return False
-        status = entry(self._h, *args)
-        if status == L.POST_DECLINED:
-            return False
-        L.check(status)
-        return True
+        entry = L.entry(name)
+        return entry is not None and L.accepted(entry(self._h, *args))
 
     def col_stats(self):
         """[b, 4]: every column's sum, sum of squares, max and min (pgh_mat_col_stats)."""
-        entry = L.measure_entry("pgh_mat_col_stats")
+        entry = L.entry("pgh_mat_col_stats")
         if entry is None or self.b > 64:
             return None
         out = np.empty((self.b, 4), dtype=np.float64)
@@ -898,6 +905,12 @@ class DeviceMatrix:
 
     def set_cols(self, first, src):
         L.check(L.lib().pgh_mat_set_cols(self._h, int(first), src._h))
+
+    def chunks(self, width=64):
+        """(first, part) for every run of at most `width` columns, in order: the slab entries take at most 64 columns a call.  A slab
+        that fits is its own only part -- no copy, no engine call; a wider one is cut with get_cols."""
+        for first in range(0, self.b, width):
+            yield first, self if self.b <= width else self.get_cols(first, min(width, self.b - first))
 
     def __sub__(self, other):
         return DeviceMatrix.from_columns([a - b for a, b in zip(self.columns(), other.columns())])

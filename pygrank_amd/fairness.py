@@ -81,7 +81,7 @@ class _EditLoss:
 
     def _slab(self, chunk):
         """The chunk's edited priors through pgh_prior_edit, or None when the library lacks the entry or the entry declines."""
-        entry = L.fair_entry("pgh_prior_edit")
+        entry = L.entry("pgh_prior_edit")
         if entry is None:
             return None
         owner = self.owner
@@ -93,9 +93,8 @@ class _EditLoss:
         out = DeviceMatrix.empty(len(personalization), probes)
         status = entry(personalization._h, sensitive._h, ranks._h, float(self.rank_max), flat.ctypes.data_as(C.c_void_p), buckets, probes,
                        1 if owner.error_skewing else 0, out._h)
-        if status == L.FAIR_DECLINED:
+        if not L.accepted(status):
             return None
-        L.check(status)
         return out
 
     def _many(self, candidates):

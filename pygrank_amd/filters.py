@@ -51,8 +51,7 @@ def _propagate_in_batches(ranker, features, cfg, run):
     cfg.start_from_p = 1
     batches = []
     out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
-    for start in range(0, F.b, 64):
-        chunk = F if F.b <= 64 else F.get_cols(start, min(64, F.b - start))
+    for start, chunk in F.chunks():
         norms = chunk.col_abssum()
         P = chunk.div_cols(norms)
         R = DeviceMatrix.empty(chunk.n, chunk.b)
@@ -60,7 +59,7 @@ def _propagate_in_batches(ranker, features, cfg, run):
         scales = (C.c_double * chunk.b)(*[(float(nrm) if ranker.preserve_norm else 1.0) for nrm in norms])
         ranker.convergence.start()
         status = run(P, R, C.byref(cfg), scales, results)
-        if status == L.BATCH_DECLINED and not batches:
+        if status == L.DECLINED and not batches:
             return None
         L.check(status)
         batches.append([dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms,
@@ -428,8 +427,7 @@ class PageRank(RecursiveGraphFilter):
             F = DeviceMatrix.from_columns([F])
         self.last_batches = []
         out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
-        for start in range(0, F.b, 64):
-            chunk = F if F.b <= 64 else F.get_cols(start, min(64, F.b - start))
+        for start, chunk in F.chunks():
             norms = chunk.col_abssum()                                            # abstract_filters.py:52-55 per column
             P = chunk.div_cols(norms)                                             # zero columns stay zero (:53-54)
             R = DeviceMatrix.empty(chunk.n, chunk.b)
@@ -501,7 +499,7 @@ class AbsorbingWalks(RecursiveGraphFilter):
         columns through pgh_absorb_run_batch (include/pgh_batch.h) wherever a single rank() would run the f32 loop of pgh_absorb_run;
         every column keeps its own quotient, residual and stopping iteration.  The column loop otherwise."""
         g = self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",))
-        entry = L.batch_entry("pgh_absorb_run_batch") if g is not None else None
+        entry = L.entry("pgh_absorb_run_batch") if g is not None else None
         if entry is not None:
             lam = (to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np
             if isinstance(lam, DeviceVector) and len(lam) == g.shape[0]:
@@ -582,18 +580,16 @@ class LFPR(RecursiveGraphFilter):
         phi = float(backend.sum(s) / backend.length(s) * self.target_prule)
         out_r, out_b = backend.conv(s, M), backend.conv(1. - s, M)
         original = self._original_ranks(personalization)
-        setup = L.lfpr_entry("pgh_lfpr_setup") if self.fused else None
+        setup = L.entry("pgh_lfpr_setup") if self.fused else None
         if setup is not None and all(isinstance(v, DeviceVector) for v in (s, out_r, out_b)) \
                 and (original is None or isinstance(original, DeviceVector)):
             made = [DeviceVector.empty(len(s)) for _ in range(5)]
             sums = (C.c_double * 2)()
             status = setup(s._h, out_r._h, out_b._h, None if original is None else original._h, phi, *[v._h for v in made], sums)
-            if status == 0:
+            if L.accepted(status):
                 self.d, self.dR, self.dB, self.xR, self.xB = made
                 self.sum_xR, self.sum_xB = float(sums[0]), float(sums[1])
                 return
-            if status != L.LFPR_DECLINED:
-                L.check(status)
         case1 = out_r < (out_r + out_b) * phi
         case2 = (1 - case1) * (out_r != 0)
         case3 = (1 - case1) * (1 - case2)
@@ -636,7 +632,7 @@ class LFPR(RecursiveGraphFilter):
 
     def _fused_route(self, M, personalization):
         """(device graph, pgh_lfpr_close) when this run takes the fused route, else None."""
-        close = L.lfpr_entry("pgh_lfpr_close") if self.fused and not self._warm else None
+        close = L.entry("pgh_lfpr_close") if self.fused and not self._warm else None
         cm = self.convergence
         g = _device_graph(M)
         if close is None or g is None or g.shape[0] != g.shape[1] or g.shape[0] == 0 or not self._plain_quotient() \
@@ -707,7 +703,7 @@ class LFPR(RecursiveGraphFilter):
             y_scale = backend.safe_inv(predicted) if quotient else 1.0
             status = close(y._h, x._h, x_scale, xR._h, xB._h, d._h, dR._h, dB._h, cR, cB, y_scale,
                            L.ERR_L1 if counts_only else kind, y._h, u._h, sums)
-            if status == L.LFPR_DECLINED:
+            if status == L.DECLINED:
                 # the iterate before this step goes back to the caller's ids; the step is taken again there
                 out = DeviceVector.empty(n)
                 L.check(lib.pgh_resident_out(g._h, x._h, x_scale, out._h))
@@ -742,13 +738,13 @@ class LFPR(RecursiveGraphFilter):
         # step's epilogue applied (1 - alpha) as an f32 coefficient, and the same f32 value is taken off here.  x_scale and
         # preserve_norm ride on the way out of the id space, which runs once
         out = DeviceVector.empty(n)
-        status = L.LFPR_DECLINED
+        status = L.DECLINED
         if x_scale != 0.0:
             # the close as an f64 axpy, y <- x + c p:  y0 = x,  xR = p with cR = c,  xB with cB = 0 adds nothing;  the residual operand
             # (x again), d / dR / dB, the five sums and u are by-products nobody reads
             c = -float(np.float32(1.0 - alpha)) / x_scale
             status = close(x._h, x._h, 1.0, p_int._h, p_int._h, d._h, dR._h, dB._h, c, 0.0, 1.0, L.ERR_L1, y._h, u._h, sums)
-        if status == L.LFPR_DECLINED:                      # (a zero quotient, or the entry declined: _end in backend primitives)
+        if status == L.DECLINED:                           # (a zero quotient, or the entry declined: _end in backend primitives)
             L.check(lib.pgh_resident_out(g._h, x._h, x_scale, out._h))
             ranks.np = out
             return self._finish_fused(M, personalization, ranks, out_scale, args, kwargs)
@@ -808,7 +804,7 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
         """signals.py:225-226 as multi-seed batches of up to 64 columns through pgh_sarw_run_batch (include/pgh_batch.h) wherever a
         single rank() would run the f32 loop of pgh_sarw_run; the column loop otherwise."""
         g = self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs)
-        entry = L.batch_entry("pgh_sarw_run_batch") if g is not None else None
+        entry = L.entry("pgh_sarw_run_batch") if g is not None else None
         if entry is not None:
             cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
             out = _propagate_in_batches(self, features, cfg,
@@ -1336,7 +1332,7 @@ class ClosedFormGraphFilter(GraphFilter):
                 and type(self)._recursion is own._recursion and type(self)._start is own._start \
                 and type(self)._retrieve_power is own._retrieve_power and type(self)._prepare is own._prepare:
             g = self._batch_graph(graph, args, kwargs)
-        entry = L.batch_entry("pgh_poly_run_batch") if g is not None else None
+        entry = L.entry("pgh_poly_run_batch") if g is not None else None
         if entry is not None:
             cfg = self._loop_cfg(0.0, False, 1.0)
             coeffs = np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64)

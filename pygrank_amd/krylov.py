@@ -113,7 +113,7 @@ class KrylovBasis:
 
     def residual_entry(self, fused=True):
         """pgh_krylov_residuals when `residuals` can use it on this basis, else None."""
-        return L.krylov_entry("pgh_krylov_residuals") if fused and self.dims <= L.KRYLOV_MAX_DIMS else None
+        return L.entry("pgh_krylov_residuals") if fused and self.dims <= L.KRYLOV_MAX_DIMS else None
 
     def residuals(self, deltas, fused=True):
         """(sum_i |V @ d_t|, max_i |V @ d_t|, fused passes it took) for the columns d_t of the [k, T] matrix `deltas`: ONE pass over the
@@ -125,10 +125,8 @@ class KrylovBasis:
         if entry is not None and self.dims <= L.KRYLOV_MAX_DIMS and 1 <= d.shape[1] <= L.KRYLOV_MAX_PROBES:
             as_doubles = lambda a: a.ctypes.data_as(L.c_f64p)                 # noqa: E731
             status = entry(self.V._h, as_doubles(d), int(d.shape[0]), int(d.shape[1]), as_doubles(sums), as_doubles(tops))
-            if status == 0:
+            if L.accepted(status):
                 return sums, tops, 1
-            if status != L.KRYLOV_DECLINED:
-                L.check(status)
         for t in range(d.shape[1]):
             change = abs(self.V.gemv(np.ascontiguousarray(d[:, t])))
             sums[t], tops[t] = change.sum(), (change.max() if len(change) else 0.0)
@@ -183,9 +181,8 @@ def _lanczos_fused(g, p, degree, close):
         out = DeviceVector.empty(n_int)
         status = close(w._h, r._h, a * s / rho, None if previous is None else previous._h, norms[j - 1] * previous_s / rho if j else 0.0,
                        out._h, None if last else slab._h, 0 if last else j + 1, sums)
-        if status == L.KRYLOV_DECLINED:
+        if not L.accepted(status):
             return None
-        L.check(status)
         raw_norm = sums[0] ** 0.5
         norm = rho * raw_norm
         alphas.append(a)
@@ -250,7 +247,7 @@ def lanczos(M, personalization, krylov_space_degree, fused=True):
         raise Exception("krylov_space_degree must be at least 1")
     p = backend.to_primitive(getattr(personalization, "np", personalization))
     g = _device_graph(M)
-    close =L.krylov_entry("pgh_lanczos_close") if fused and g is not None else None
+    close = L.entry("pgh_lanczos_close") if fused and g is not None else None
     if close is not None and degree <= MAX_FUSED_DIMS and isinstance(p, DeviceVector) and g.shape[0] == g.shape[1] == len(p) \
             and len(p) > 0 and g._resident_lengths():
         basis = _lanczos_fused(g, p, degree, close)
@@ -341,9 +338,8 @@ def _arnoldi_fused(g, b, n, dots, close):
                                       None if wg is None else wg._h, None))
         sums = np.zeros(k + 1)
         status = dots(slab._h, k, w._h, sums.ctypes.data_as(L.c_f64p))
-        if status == L.ARNOLDI_DECLINED:
+        if not L.accepted(status):
             return None
-        L.check(status)
         s = np.asarray(scales)
         c = s * rho * sums[:k]
         coefficients = np.zeros(k)
@@ -352,9 +348,8 @@ def _arnoldi_fused(g, b, n, dots, close):
         out = DeviceVector.empty(n_int)
         status = close(slab._h, k, w._h, np.ascontiguousarray(coefficients * s / rho).ctypes.data_as(L.c_f64p), out._h, k,
                        sums.ctypes.data_as(L.c_f64p))
-        if status == L.ARNOLDI_DECLINED:
+        if not L.accepted(status):
             return None
-        L.check(status)
         for j in range(k):
             h[j][k - 1] = float(coefficients[j])
         raw_norm = sums[k] ** 0.5
@@ -380,8 +375,8 @@ def arnoldi_run(A, b, n, fused=False):
     graph = _device_graph(A)
     A = graph if graph is not None else A
     b = getattr(b, "np", b)
-    dots = L.arnoldi_entry("pgh_basis_dots") if fused and graph is not None else None
-    close = L.arnoldi_entry("pgh_arnoldi_close") if dots is not None else None
+    dots = L.entry("pgh_basis_dots") if fused and graph is not None else None
+    close = L.entry("pgh_arnoldi_close") if dots is not None else None
     if close is not None and 1 <= n <= L.ARNOLDI_MAX_DIMS and isinstance(b, DeviceVector) and graph.shape[0] == graph.shape[1] == len(b) \
             and len(b) > 0 and graph._resident_lengths():
         result = _arnoldi_fused(graph, b, n, dots, close)

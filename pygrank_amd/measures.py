@@ -25,12 +25,13 @@ Modularity (unsupervised.py:148-201) is a closed form over the same entries in p
 """
 import collections.abc
 import ctypes as C
+import itertools
 import numbers
 import random
 
 from pygrank_amd import _lib as L
 from pygrank_amd import backend
-from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector, lazy_residual
+from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector, EnginePlan, lazy_residual
 from pygrank_amd.preprocessing import AdjacencyWrapper, preprocessor as default_preprocessor
 from pygrank_amd.signals import GraphSignal, to_signal
 
@@ -102,7 +103,7 @@ class Supervised(Measure):
         return backend.to_array([obj] if isinstance(obj, numbers.Number) else obj)
 
     def _slab_available(self):
-        return self._from_slots is not None and L.supervised_entry("pgh_pair_forms") is not None
+        return self._from_slots is not None and L.entry("pgh_pair_forms") is not None
 
     def _operand(self, anchor, side, rows, name):
         """(vector, matrix) of the known scores or the exclude values for a slab of `rows` rows; one of them is None (both for None)."""
@@ -127,7 +128,7 @@ class Supervised(Measure):
         """The slab route: one pgh_pair_forms call per 64 columns, the values derived on the host from its slots.  None when the engine
         declines."""
         import numpy as np
-        entry = L.supervised_entry("pgh_pair_forms")
+        entry = L.entry("pgh_pair_forms")
         matrix = self._matrix(anchor, columns)
         known_vec, known_mat = self._operand(anchor, self.known_scores, matrix.n, "known scores")
         exclude_vec, exclude_mat = self._operand(anchor, self.exclude, matrix.n, "exclude values")
@@ -138,21 +139,21 @@ class Supervised(Measure):
             sums = matrix.col_abssum()
             factors = np.where(sums != 0, 1.0 / np.where(sums != 0, sums, 1.0), 1.0)
         out = []
-        for first in range(0, matrix.b, 64):
-            width = min(64, matrix.b - first)
-            whole = matrix.b <= 64
-            part = matrix if whole else matrix.get_cols(first, width)
-            kmat = known_mat if whole or known_mat is None else known_mat.get_cols(first, width)
-            emat = exclude_mat if whole or exclude_mat is None else exclude_mat.get_cols(first, width)
+
+        # a side given per column is cut in step with the scores; evaluate_many has checked that it holds as many columns as they do
+        # (zip would stop at the shorter one without a word)
+        def cut(side):
+            return itertools.repeat((0, None)) if side is None else side.chunks()
+        for (first, part), (_, kmat), (_, emat) in zip(matrix.chunks(), cut(known_mat), cut(exclude_mat)):
+            width = part.b
             chunk = None if factors is None else np.ascontiguousarray(factors[first:first + width])
             slots = np.empty((width, L.PAIR_SLOTS), dtype=np.float64)
             status = entry(part._h, None if known_vec is None else known_vec._h, None if kmat is None else kmat._h,
                            None if exclude_vec is None else exclude_vec._h, None if emat is None else emat._h,
                            None if chunk is None else chunk.ctypes.data_as(C.c_void_p), eps, self._GROUP,
                            slots.ctypes.data_as(C.c_void_p))
-            if status == L.PAIR_DECLINED:
+            if not L.accepted(status):
                 return None
-            L.check(status)
             out.extend(self._from_slots([float(v) for v in slots[j]], eps) for j in range(width))
         return out
 
@@ -327,23 +328,16 @@ class Cos(_Pairwise):                                        # supervised.py:208
         return backend.safe_div(s[5], _ieee_sqrt(s[4] * s[2]))
 
 
-class _ProbePlan:
+class _ProbePlan(EnginePlan):
     """The node classes of one (known scores, exclude) pair on the device (pgh_probe_plan_create, include/pgh_tune.h)."""
+    _DESTROY = "pgh_probe_plan_destroy"
 
     def __init__(self, known, exclude):
         self._h = L.c_plan()
-        L.check(L.tune_entry("pgh_probe_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
+        L.check(L.entry("pgh_probe_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
         positive, negative = C.c_int64(), C.c_int64()
-        L.check(L.tune_entry("pgh_probe_plan_info")(self._h, C.byref(positive), C.byref(negative)))
+        L.check(L.entry("pgh_probe_plan_info")(self._h, C.byref(positive), C.byref(negative)))
         self.num_positive, self.num_negative = positive.value, negative.value
-
-    def __del__(self):
-        try:
-            if self._h is not None and L._lib is not None:
-                L.tune_entry("pgh_probe_plan_destroy")(self._h)
-        except Exception:
-            pass
-        self._h = None
 
 
 class AUC(_Pairwise):                                        # supervised.py:255-263 (sklearn roc_curve + auc in the reference)
@@ -369,7 +363,7 @@ class AUC(_Pairwise):                                        # supervised.py:255
         return self._of_auc(self._auc(scores))
 
     def _slab_available(self):
-        return all(L.tune_entry(name) is not None for name in L.TUNE_SIGNATURES)
+        return all(L.entry(name) is not None for name in L.TUNE_SIGNATURES)
 
     def _slab(self, anchor, columns, count):
         import numpy as np
@@ -382,15 +376,13 @@ class AUC(_Pairwise):                                        # supervised.py:255
         if plan.num_positive == 0 or plan.num_negative == 0:
             raise Exception(self._SAME_CLASS)
         out = []
-        for first in range(0, matrix.b, 64):
-            width = min(64, matrix.b - first)
-            part = matrix if matrix.b <= 64 else matrix.get_cols(first, width)
+        for _, part in matrix.chunks():
+            width = part.b
             identity = np.ascontiguousarray(np.eye(width, dtype=np.float64))
             aucs = (C.c_double * width)()
-            status = L.tune_entry("pgh_probe_auc")(part._h, identity.ctypes.data_as(C.c_void_p), width, width, plan._h, aucs)
-            if status == L.TUNE_DECLINED:
+            status = L.entry("pgh_probe_auc")(part._h, identity.ctypes.data_as(C.c_void_p), width, width, plan._h, aucs)
+            if not L.accepted(status):
                 return None
-            L.check(status)
             out.extend(self._of_auc(float(v)) for v in aucs)
         return out
 
@@ -618,23 +610,16 @@ class MannWhitneyParity(AUC):                                # supervised.py:336
         return 1 - 2 * abs(auc - 0.5)
 
 
-class _RankPlan:
+class _RankPlan(EnginePlan):
     """What the columns of every NDCG / SpearmanCorrelation call share on the device (pgh_rank_plan_create, include/pgh_rank.h)."""
+    _DESTROY = "pgh_rank_plan_destroy"
 
     def __init__(self, known, exclude):
         self._h = L.c_rank_plan()
-        L.check(L.rank_entry("pgh_rank_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
+        L.check(L.entry("pgh_rank_plan_create")(known._h, None if exclude is None else exclude._h, C.byref(self._h)))
         kept, relevant, negative = C.c_int64(), C.c_int64(), C.c_int32()
-        L.check(L.rank_entry("pgh_rank_plan_info")(self._h, C.byref(kept), C.byref(relevant), C.byref(negative)))
+        L.check(L.entry("pgh_rank_plan_info")(self._h, C.byref(kept), C.byref(relevant), C.byref(negative)))
         self.num_kept, self.num_relevant, self.has_negative = kept.value, relevant.value, bool(negative.value)
-
-    def __del__(self):
-        try:
-            if self._h is not None and L._lib is not None:
-                L.rank_entry("pgh_rank_plan_destroy")(self._h)
-        except Exception:
-            pass
-        self._h = None
 
 
 class _Ranked(_Pairwise):
@@ -648,7 +633,7 @@ class _Ranked(_Pairwise):
     _MANY_IS_EXACT = True         # evaluate is the one-column case of the same entry, whose per-column result does not depend on the width
 
     def _slab_available(self):
-        return all(L.rank_entry(name) is not None for name in ("pgh_rank_plan_create", "pgh_rank_plan_info", "pgh_rank_plan_destroy")
+        return all(L.entry(name) is not None for name in ("pgh_rank_plan_create", "pgh_rank_plan_info", "pgh_rank_plan_destroy")
                    + self._ENTRIES)
 
     def _plan_for(self, anchor, rows):
@@ -675,10 +660,8 @@ class _Ranked(_Pairwise):
         matrix = self._matrix(anchor, columns)
         plan = self._plan_for(anchor, matrix.n)
         out = []
-        for first in range(0, matrix.b, 64):
-            width = min(64, matrix.b - first)
-            part = matrix if matrix.b <= 64 else matrix.get_cols(first, width)
-            values = self._of_entry(part._h, plan, width, False)
+        for _, part in matrix.chunks():
+            values = self._of_entry(part._h, plan, part.b, False)
             if values is None:
                 return None
             out.extend(values)
@@ -734,10 +717,9 @@ class NDCG(_Ranked):                                         # supervised.py:68-
         if plan.num_kept == 0 or k < 1:
             self._quotient(0, 0, 0, k)
         dcg, idcg = (C.c_double * width)(), C.c_double()
-        status = L.rank_entry("pgh_ndcg_vec" if vector else "pgh_ndcg")(handle, plan._h, k, L.RANK_AUTO, dcg, C.byref(idcg))
-        if status == L.RANK_DECLINED:
+        status = L.entry("pgh_ndcg_vec" if vector else "pgh_ndcg")(handle, plan._h, k, L.RANK_AUTO, dcg, C.byref(idcg))
+        if not L.accepted(status):
             return None
-        L.check(status)
         return [self._quotient(float(v), idcg.value, plan.num_kept, k) for v in dcg]
 
     def _columns_value(self, known, scores):
@@ -765,10 +747,9 @@ class SpearmanCorrelation(_Ranked):                          # supervised.py:274
 
     def _of_entry(self, handle, plan, width, vector):
         rho = (C.c_double * width)()
-        status = L.rank_entry("pgh_spearman_vec" if vector else "pgh_spearman")(handle, plan._h, rho)
-        if status == L.RANK_DECLINED:
+        status = L.entry("pgh_spearman_vec" if vector else "pgh_spearman")(handle, plan._h, rho)
+        if not L.accepted(status):
             return None
-        L.check(status)
         return [float(v) for v in rho]
 
     @staticmethod
@@ -844,28 +825,26 @@ class Unsupervised(Measure):
 
     def _slab(self, graph, device_graph, matrix):
         """The slab route over a DeviceMatrix, 64 columns at a time; None when the engine declines."""
-        stats_fn, forms_fn = L.measure_entry("pgh_mat_col_stats"), L.measure_entry("pgh_cut_forms")
+        stats_fn, forms_fn = L.entry("pgh_mat_col_stats"), L.entry("pgh_cut_forms")
         import numpy as np
         out = []
-        for first in range(0, matrix.b, 64):
-            part = matrix if matrix.b <= 64 else matrix.get_cols(first, min(64, matrix.b - first))
+        for _, part in matrix.chunks():
             stats = np.empty((part.b, 4), dtype=np.float64)
             L.check(stats_fn(part._h, stats.ctypes.data_as(C.c_void_p)))
             factors = self._plan(stats)
             forms = np.empty((part.b, 4), dtype=np.float64)
             status = forms_fn(device_graph._h, part._h, None if factors is None else factors.ctypes.data_as(C.c_void_p),
                               float(getattr(self, "max_rank", 1)), self._FORMS, forms.ctypes.data_as(C.c_void_p))
-            if status == L.MEASURE_DECLINED:
+            if not L.accepted(status):
                 return None
-            L.check(status)
             out.extend(self._from_forms(graph, [float(v) for v in forms[j]], [float(v) for v in stats[j]]) for j in range(part.b))
         return out
 
     def _route(self, graph, adjacency, columns):
         """Scores of `columns` (a DeviceMatrix or a list of vectors) on the preprocessed graph."""
         device_graph = getattr(adjacency, "array", adjacency)
-        if not _FORCE_PER_COLUMN and isinstance(device_graph, DeviceGraph) and L.measure_entry("pgh_cut_forms") is not None \
-                and L.measure_entry("pgh_mat_col_stats") is not None:
+        if not _FORCE_PER_COLUMN and isinstance(device_graph, DeviceGraph) and L.entry("pgh_cut_forms") is not None \
+                and L.entry("pgh_mat_col_stats") is not None:
             matrix = columns if isinstance(columns, DeviceMatrix) else DeviceMatrix.from_columns(columns)
             out = self._slab(graph, device_graph, matrix)
             if out is not None:
@@ -1045,23 +1024,20 @@ class Modularity(Unsupervised):
 
     def _slab(self, prepared, matrix):
         import numpy as np
-        forms_fn, pair_fn = L.measure_entry("pgh_cut_forms"), L.supervised_entry("pgh_pair_forms")
+        forms_fn, pair_fn = L.entry("pgh_cut_forms"), L.entry("pgh_pair_forms")
         out = []
-        for first in range(0, matrix.b, 64):
-            part = matrix if matrix.b <= 64 else matrix.get_cols(first, min(64, matrix.b - first))
+        for _, part in matrix.chunks():
             factors = np.full(part.b, 1.0 / self.max_rank, dtype=np.float64)
             forms = np.empty((part.b, 4), dtype=np.float64)
             status = forms_fn(prepared["graph"]._h, part._h, factors.ctypes.data_as(C.c_void_p), 1.0, L.CUT_INTERNAL,
                               forms.ctypes.data_as(C.c_void_p))
-            if status == L.MEASURE_DECLINED:
+            if not L.accepted(status):
                 return None
-            L.check(status)
             slots = np.empty((part.b, L.PAIR_SLOTS), dtype=np.float64)
             status = pair_fn(part._h, prepared["weighted_degree"]._h, None, None, None, None, backend.epsilon(), L.PAIR_MOMENTS,
                              slots.ctypes.data_as(C.c_void_p))
-            if status == L.PAIR_DECLINED:
+            if not L.accepted(status):
                 return None
-            L.check(status)
             out.extend(self._value(prepared, float(forms[j][0]), float(slots[j][5]) / self.max_rank) for j in range(part.b))
         return out
 
@@ -1075,7 +1051,7 @@ class Modularity(Unsupervised):
         if prepared["edges"] == 0:
             return [0] * count
         if self.fused and not _FORCE_PER_COLUMN and isinstance(prepared["graph"], DeviceGraph) \
-                and L.measure_entry("pgh_cut_forms") is not None and L.supervised_entry("pgh_pair_forms") is not None:
+                and L.entry("pgh_cut_forms") is not None and L.entry("pgh_pair_forms") is not None:
             matrix = columns if isinstance(columns, DeviceMatrix) else DeviceMatrix.from_columns(columns)
             out = self._slab(prepared, matrix)
             if out is not None:

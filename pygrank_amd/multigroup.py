@@ -34,7 +34,7 @@ import scipy.sparse as sp
 
 from pygrank_amd import _lib as L
 from pygrank_amd import backend
-from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector
+from pygrank_amd.device import DeviceGraph, DeviceMatrix, DeviceVector, EnginePlan
 from pygrank_amd.measures import AUC
 from pygrank_amd.preprocessing import AdjacencyWrapper, graph_to_scipy
 from pygrank_amd.signals import GraphSignal, to_signal
@@ -153,9 +153,10 @@ def host_auc(predicted, labels):
     return two_wins / (2.0 * P * N), P, N
 
 
-class _LinkPlan:
+class _LinkPlan(EnginePlan):
     """The pairs of one (graph, hops, samples, seed): ids and labels on the host, and -- once a fused evaluation asked for it -- on the
     device (pgh_link_plan_create)."""
+    _DESTROY = "pgh_link_plan_destroy"
 
     def __init__(self, n, candidates, first, second, label):
         self.n = int(n)
@@ -174,19 +175,11 @@ class _LinkPlan:
                                 "take smaller max_positive_samples / max_negative_samples")
             L.ensure_init()
             handle = L.c_link_plan()
-            L.check(L.link_entry("pgh_link_plan_create")(
+            L.check(L.entry("pgh_link_plan_create")(
                 self.n, self.num_pairs, self.first.ctypes.data_as(L.c_i32p), self.second.ctypes.data_as(L.c_i32p),
                 self.label.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(handle)))
             self._h = handle
         return self._h
-
-    def __del__(self):
-        try:
-            if self._h is not None and L._lib is not None:
-                L.link_entry("pgh_link_plan_destroy")(self._h)
-        except Exception:
-            pass
-        self._h = None
 
 
 def _identity(x):
@@ -254,7 +247,7 @@ class LinkAssessment:
         return self._plan
 
     def _device_available(self):
-        return self.fused and all(L.link_entry(name) is not None for name in L.LINK_SIGNATURES)
+        return self.fused and all(L.entry(name) is not None for name in L.LINK_SIGNATURES)
 
     def predictions(self, scores):
         """(similarities, labels) of the plan's pairs as f64 / uint8 host arrays."""
@@ -262,10 +255,9 @@ class LinkAssessment:
         matrix = slab_of(self.G, scores)
         if self._device_available() and plan.num_pairs <= L.LINK_MAX_PAIRS:
             out = np.empty(plan.num_pairs, dtype=np.float64)
-            status = L.link_entry("pgh_link_predictions")(matrix._h, plan.handle(), _SIMILARITIES[self.similarity], 0, plan.num_pairs,
-                                                          out.ctypes.data_as(L.c_f64p))
-            if status != L.LINK_DECLINED:
-                L.check(status)
+            status = L.entry("pgh_link_predictions")(matrix._h, plan.handle(), _SIMILARITIES[self.similarity], 0, plan.num_pairs,
+                                                     out.ctypes.data_as(L.c_f64p))
+            if L.accepted(status):
                 self.last_route = "device"
                 return out, plan.label
         self.last_route = "host"
@@ -279,10 +271,9 @@ class LinkAssessment:
         value = None
         if self._device_available():
             auc, positive, negative = C.c_double(), C.c_int64(), C.c_int64()
-            status = L.link_entry("pgh_link_auc")(matrix._h, plan.handle(), _SIMILARITIES[self.similarity], C.byref(auc), C.byref(positive),
-                                                  C.byref(negative))
-            if status != L.LINK_DECLINED:
-                L.check(status)
+            status = L.entry("pgh_link_auc")(matrix._h, plan.handle(), _SIMILARITIES[self.similarity], C.byref(auc), C.byref(positive),
+                                             C.byref(negative))
+            if L.accepted(status):
                 self.last_route = "device"
                 value = auc.value
         if value is None:
@@ -342,7 +333,7 @@ class ClusteringCoefficient:
         matrix = slab_of(self.G, scores)
         if prepared["denominator"] == 0:
             return 0
-        entry = L.link_entry("pgh_link_factors") if self.fused else None
+        entry = L.entry("pgh_link_factors") if self.fused else None
         if entry is not None:
             if prepared["graph"] is None:
                 # the engine's conv(x, M) is M^T x and P t is wanted: upload P^T

@@ -43,7 +43,7 @@ class _SlabPasses:
     ``calls`` counts the passes by route."""
 
     def __init__(self, fused):
-        self.entries = {name: L.oversample_entry(name) for name in _ENTRIES} if fused else {}
+        self.entries = {name: L.entry(name) for name in _ENTRIES} if fused else {}
         if any(entry is None for entry in self.entries.values()):
             self.entries = {}
         self.calls = dict(fused=0, primitive=0)
@@ -53,11 +53,9 @@ class _SlabPasses:
         entry = self.entries.get(name)
         if entry is not None:
             status = entry(*args)
-            if status == 0:
+            if L.accepted(status):
                 self.calls["fused"] += 1
                 return True
-            if status != L.OVERSAMPLE_DECLINED:
-                L.check(status)
             self.entries = {}
         self.calls["primitive"] += 1
         return False
@@ -160,8 +158,7 @@ class _Oversampler(Postprocessor):
         self._reset()
         passes = _SlabPasses(self.fused)
         out = DeviceMatrix.empty(F.n, F.b) if F.b > width else None
-        for first in range(0, F.b, width):
-            chunk = F if F.b <= width else F.get_cols(first, min(width, F.b - first))
+        for first, chunk in F.chunks(width):
             ranks = self._loop(graph, chunk, passes, kwargs)
             self.last_passes = dict(passes.calls)
             if out is None:

@@ -76,12 +76,11 @@ class Postprocessor(NodeRanking):
         plain = graph.graph if isinstance(graph, GraphSignal) else graph
         # (a keyword that _transform has a parameter for would reach it through _apply: the columns route lets it)
         reaching = len(leftover) - len(remove_used_args(self._transform, leftover))
-        served = all(L.post_entry(name) is not None for name in L.POST_SIGNATURES)      # (a library has all of the header or none)
+        served = all(L.entry(name) is not None for name in L.POST_SIGNATURES)      # (a library has all of the header or none)
         if self.fused and served and isinstance(inner, DeviceMatrix) and inner.n > 0 and not reaching:
             widths = [min(CHUNK, inner.b - first) for first in range(0, inner.b, CHUNK)]
             out = DeviceMatrix.empty(inner.n, inner.b) if inner.b > CHUNK else None
-            for first, width in zip(range(0, inner.b, CHUNK), widths):
-                chunk = inner if out is None else inner.get_cols(first, width)
+            for first, chunk in inner.chunks(CHUNK):
                 done = self._slab(plain, chunk, calls)
                 if done is None:
                     break

@@ -111,14 +111,14 @@ class Plan:
         self.known = pg.DeviceVector.from_host(np.asarray(known, dtype=np.float64))
         self.exclude = None if exclude is None else pg.DeviceVector.from_host(np.asarray(exclude, dtype=np.float64))
         self.h = L.c_rank_plan()
-        L.check(L.rank_entry("pgh_rank_plan_create")(self.known._h, None if self.exclude is None else self.exclude._h, C.byref(self.h)))
+        L.check(L.entry("pgh_rank_plan_create")(self.known._h, None if self.exclude is None else self.exclude._h, C.byref(self.h)))
         kept, relevant, negative = C.c_int64(), C.c_int64(), C.c_int32()
-        L.check(L.rank_entry("pgh_rank_plan_info")(self.h, C.byref(kept), C.byref(relevant), C.byref(negative)))
+        L.check(L.entry("pgh_rank_plan_info")(self.h, C.byref(kept), C.byref(relevant), C.byref(negative)))
         self.kept, self.relevant, self.negative = kept.value, relevant.value, negative.value
 
     def __del__(self):
         try:
-            self.L.rank_entry("pgh_rank_plan_destroy")(self.h)
+            self.L.entry("pgh_rank_plan_destroy")(self.h)
         except Exception:
             pass
 
@@ -127,7 +127,7 @@ class Plan:
         L = self.L
         width = getattr(slab, "b", 1)
         out, ideal = (C.c_double * width)(*([-7.0] * width)), C.c_double(-7.0)
-        entry = L.rank_entry("pgh_ndcg" if hasattr(slab, "b") else "pgh_ndcg_vec")
+        entry = L.entry("pgh_ndcg" if hasattr(slab, "b") else "pgh_ndcg_vec")
         status = entry(slab._h, self.h, int(k), route, out, C.byref(ideal))
         if status not in (0, DECLINED):
             L.check(status)
@@ -137,7 +137,7 @@ class Plan:
         L = self.L
         width = getattr(slab, "b", 1)
         out = (C.c_double * width)(*([-7.0] * width))
-        status = L.rank_entry("pgh_spearman" if hasattr(slab, "b") else "pgh_spearman_vec")(slab._h, self.h, out)
+        status = L.entry("pgh_spearman" if hasattr(slab, "b") else "pgh_spearman_vec")(slab._h, self.h, out)
         L.check(status)
         return [float(v) for v in out]
 

@@ -41,7 +41,7 @@ def test_arnoldi_header_table_and_makefile_agree():
     for header in headers:
         if header != "pgh_arnoldi.h":
             assert set(ENTRIES).isdisjoint(_declared(header)), header
-    assert _lib.ARNOLDI_DECLINED == _defined("pgh_arnoldi.h", "PGH_ARNOLDI_DECLINED")
+    assert _lib.DECLINED == _defined("pgh_arnoldi.h", "PGH_ARNOLDI_DECLINED")
     assert _lib.ARNOLDI_MAX_DIMS == _defined("pgh_arnoldi.h", "PGH_ARNOLDI_MAX_DIMS")
     vec, mat, dblp = C.c_void_p, C.c_void_p, C.POINTER(C.c_double)
     restype, argtypes = _lib.ARNOLDI_SIGNATURES["pgh_basis_dots"]
@@ -58,7 +58,7 @@ def test_arnoldi_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_arnoldi_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_arnoldi(cdll)
+    bound = _lib.bind_optional(cdll, _lib.ARNOLDI_SIGNATURES)
     assert sorted(bound) == ENTRIES
     for name in ENTRIES:
         assert hasattr(cdll, name), name
@@ -68,4 +68,4 @@ def test_hip_library_exports_and_binds_the_arnoldi_entries(hip_lib):
 def test_host_double_has_no_arnoldi_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.ARNOLDI_SIGNATURES:
-        assert _lib.arnoldi_entry(name) is None, name
+        assert _lib.entry(name) is None, name

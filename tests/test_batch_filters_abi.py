@@ -26,13 +26,18 @@ def hip_lib():
 def test_batch_header_and_table_agree():
     from pygrank_amd import _lib
     assert sorted(_lib.BATCH_SIGNATURES) == _declared("pgh_batch.h")
-    assert set(_lib.BATCH_SIGNATURES).isdisjoint(_lib.SIGNATURES)
+    assert _lib.OPTIONAL["pgh_batch.h"] is _lib.BATCH_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_batch.h":
+            assert set(_lib.BATCH_SIGNATURES).isdisjoint(other), header
+    defined = re.search(r"#define\s+PGH_BATCH_DECLINED\s+(\d+)", open(os.path.join(ROOT, "include", "pgh_batch.h")).read())
+    assert _lib.DECLINED == int(defined.group(1))
 
 
 def test_hip_library_exports_and_binds_the_batch_loops(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_batch(cdll)
+    bound = _lib.bind_optional(cdll, _lib.BATCH_SIGNATURES)
     for name in _declared("pgh_batch.h"):
         assert hasattr(cdll, name), name
         assert bound[name] is not None and bound[name].argtypes == _lib.BATCH_SIGNATURES[name][1], name
@@ -48,7 +53,7 @@ def test_host_double_falls_back_to_the_column_loop(host_engine, algo):
     from pygrank_amd import _lib
     from pygrank_amd.signals import NodeRanking
     pg = host_engine
-    assert _lib.batch_entry("pgh_poly_run_batch") is None
+    assert _lib.entry("pgh_poly_run_batch") is None
     rng = np.random.default_rng(2)
     n = 60
     A = (rng.random((n, n)) < 0.1).astype(float)

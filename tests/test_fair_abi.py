@@ -30,9 +30,11 @@ def test_fair_header_table_and_makefile_agree():
     import ctypes as C
     from pygrank_amd import _lib
     assert sorted(_lib.FAIR_SIGNATURES) == _declared("pgh_fair.h") == ["pgh_prior_edit"]
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES, _lib.MEASURE_SIGNATURES, _lib.SUPERVISED_SIGNATURES):
-        assert set(_lib.FAIR_SIGNATURES).isdisjoint(other)
-    assert _lib.FAIR_DECLINED == _defined("pgh_fair.h", "PGH_FAIR_DECLINED")
+    assert _lib.OPTIONAL["pgh_fair.h"] is _lib.FAIR_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_fair.h":
+            assert set(_lib.FAIR_SIGNATURES).isdisjoint(other), header
+    assert _lib.DECLINED == _defined("pgh_fair.h", "PGH_FAIR_DECLINED")
     assert _lib.FAIR_MAX_PROBES == _defined("pgh_fair.h", "PGH_FAIR_MAX_PROBES")
     assert _lib.FAIR_MAX_BUCKETS == _defined("pgh_fair.h", "PGH_FAIR_MAX_BUCKETS")
     restype, argtypes = _lib.FAIR_SIGNATURES["pgh_prior_edit"]
@@ -46,7 +48,7 @@ def test_fair_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_fair_entry(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_fair(cdll)
+    bound = _lib.bind_optional(cdll, _lib.FAIR_SIGNATURES)
     assert sorted(bound) == _declared("pgh_fair.h")
     for name in _declared("pgh_fair.h"):
         assert hasattr(cdll, name), name
@@ -56,4 +58,4 @@ def test_hip_library_exports_and_binds_the_fair_entry(hip_lib):
 def test_host_double_has_no_fair_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.FAIR_SIGNATURES:
-        assert _lib.fair_entry(name) is None, name
+        assert _lib.entry(name) is None, name

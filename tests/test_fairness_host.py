@@ -16,7 +16,7 @@ def fx():
 
 def test_many_without_the_entry_equals_the_loop(host_engine, fx):
     from pygrank_amd import _lib as L
-    assert L.fair_entry("pgh_prior_edit") is None
+    assert L.entry("pgh_prior_edit") is None
     case = fc.Case(host_engine, fx, "weighted300")
     personalizer = case.personalizer(fx, max_residual=1)
     loss = case.open(personalizer)

@@ -26,7 +26,7 @@ SENTINEL = -7.0
 
 def _entries():
     from pygrank_amd import _lib as L
-    dots, close = L.arnoldi_entry("pgh_basis_dots"), L.arnoldi_entry("pgh_arnoldi_close")
+    dots, close = L.entry("pgh_basis_dots"), L.entry("pgh_arnoldi_close")
     assert dots is not None and close is not None
     return dots, close
 

@@ -59,7 +59,7 @@ def pg():
     pygrank_amd.load_backend("hip")
     assert _lib.runtime_name().startswith("hip:")
     for name in ("pgh_poly_run_batch", "pgh_absorb_run_batch", "pgh_sarw_run_batch"):
-        assert _lib.batch_entry(name) is not None, name
+        assert _lib.entry(name) is not None, name
     return pygrank_amd
 
 

@@ -34,7 +34,7 @@ def pg():
     from pygrank_amd import _lib
     pygrank_amd.load_backend("hip")
     assert _lib.runtime_name().startswith("hip:")
-    assert _lib.batch_entry("pgh_poly_run_batch") is not None
+    assert _lib.entry("pgh_poly_run_batch") is not None
     return pygrank_amd
 
 

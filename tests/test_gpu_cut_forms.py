@@ -80,8 +80,8 @@ def _scores(n, b, max_rank, seed):
 def _call(L, g, mat, factors, max_rank, forms):
     b = mat.b
     out = np.full(4 * b + 4, SENTINEL)
-    status = L.measure_entry("pgh_cut_forms")(g._h, mat._h, None if factors is None else factors.ctypes.data_as(C.c_void_p), float(max_rank),
-                                              forms, out.ctypes.data_as(C.c_void_p))
+    status = L.entry("pgh_cut_forms")(g._h, mat._h, None if factors is None else factors.ctypes.data_as(C.c_void_p), float(max_rank),
+                                      forms, out.ctypes.data_as(C.c_void_p))
     return status, out
 
 
@@ -113,7 +113,7 @@ def test_cut_forms_and_col_stats_against_numpy(gpu_engine, graphs, key, b):
 
     # ---- column statistics
     stats = np.full(4 * b + 4, SENTINEL)
-    L.check(L.measure_entry("pgh_mat_col_stats")(mat._h, stats.ctypes.data_as(C.c_void_p)))
+    L.check(L.entry("pgh_mat_col_stats")(mat._h, stats.ctypes.data_as(C.c_void_p)))
     assert np.all(stats[4 * b:] == SENTINEL)
     stats = stats[:4 * b].reshape(b, 4)
     S64 = S.astype(np.float64)
@@ -161,7 +161,7 @@ def test_cut_forms_refusals_leave_the_output_alone(gpu_engine, graphs):
     rng = np.random.default_rng(5)
 
     def untouched(status, out, declined=True):
-        assert (status == L.MEASURE_DECLINED) if declined else (status not in (0, L.MEASURE_DECLINED)), status
+        assert (status == L.DECLINED) if declined else (status not in (0, L.DECLINED)), status
         assert np.all(out == SENTINEL)
     wide = DeviceMatrix.from_host(rng.random((n, 65)))
     untouched(*_call(L, g, wide, None, 1, L.CUT_ALL))

@@ -34,7 +34,7 @@ def all_cases(gpu_engine, fx):
 @pytest.mark.parametrize("key", fc.GRAPHS)
 def test_routes_agree(gpu_engine, fx, all_cases, key):
     from pygrank_amd import _lib as L
-    assert L.fair_entry("pgh_prior_edit") is not None
+    assert L.entry("pgh_prior_edit") is not None
     case = all_cases(key)
     largest = 0.0
     for buckets, skew in ((1, False), (2, True)):

@@ -20,7 +20,7 @@ SMALL = [name for name, case in kc.CASES.items() if case[4] <= kc.BASIS_DIMS]
 @pytest.mark.parametrize("name", list(kc.CASES))
 def test_golden_case_both_routes(gpu_engine, name):
     from pygrank_amd import _lib as L
-    assert L.krylov_entry("pgh_lanczos_close") is not None and L.krylov_entry("pgh_krylov_residuals") is not None
+    assert L.entry("pgh_lanczos_close") is not None and L.entry("pgh_krylov_residuals") is not None
     dims = kc.CASES[name][4]
     fused, a = kc.check(gpu_engine, name, fused=True)
     assert fused.last_loop["spmv"] == dims and fused.last_loop["residual_passes"] >= 1 and fused.last_loop["converged"]

@@ -31,7 +31,7 @@ SENTINEL = -7.0
 
 def _entries():
     from pygrank_amd import _lib as L
-    close, residuals = L.krylov_entry("pgh_lanczos_close"), L.krylov_entry("pgh_krylov_residuals")
+    close, residuals = L.entry("pgh_lanczos_close"), L.entry("pgh_krylov_residuals")
     assert close is not None and residuals is not None
     return close, residuals
 

@@ -20,7 +20,7 @@ class Counted:
     def __enter__(self):
         from pygrank_amd import _lib as L
         self.lib, self.counts = L.lib(), collections.Counter()
-        assert L.lfpr_entry("pgh_lfpr_setup") is not None and L.lfpr_entry("pgh_lfpr_close") is not None
+        assert L.entry("pgh_lfpr_setup") is not None and L.entry("pgh_lfpr_close") is not None
         self.originals = {name: getattr(self.lib, name) for name in WATCHED}
         self.entries = self.lib._pgh_lfpr_entries
         for name, fn in self.originals.items():

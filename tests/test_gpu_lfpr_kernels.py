@@ -25,7 +25,7 @@ MABS, L1, LINF, ITERS = range(4)
 
 def _entries():
     from pygrank_amd import _lib as L
-    setup, close = L.lfpr_entry("pgh_lfpr_setup"), L.lfpr_entry("pgh_lfpr_close")
+    setup, close = L.entry("pgh_lfpr_setup"), L.entry("pgh_lfpr_close")
     assert setup is not None and close is not None
     return setup, close
 
@@ -149,7 +149,7 @@ def test_refusals_leave_the_outputs_untouched(gpu_engine):
     def untouched():
         return all(np.all(v.numpy(np.float32) == -7.0) for v in outs) and np.all(short.numpy(np.float32) == -7.0)
     for phi in (float("nan"), float("inf")):
-        assert setup(s._h, R._h, B._h, None, phi, *handles, sums) == L.LFPR_DECLINED and untouched()
+        assert setup(s._h, R._h, B._h, None, phi, *handles, sums) == L.DECLINED and untouched()
     for bad in ((s._h, R._h, B._h, None, 0.2, short._h, *handles[1:], sums),              # a length mismatch
                 (s._h, R._h, short._h, None, 0.2, *handles, sums),
                 (s._h, R._h, B._h, short._h, 0.2, *handles, sums),
@@ -159,7 +159,7 @@ def test_refusals_leave_the_outputs_untouched(gpu_engine):
                 (s._h, R._h, B._h, None, 0.2, *handles[:4], None, sums),
                 (s._h, R._h, B._h, None, 0.2, *handles, None)):
         status = setup(*bad)
-        assert status not in (0, L.LFPR_DECLINED) and untouched(), bad
+        assert status not in (0, L.DECLINED) and untouched(), bad
     assert list(sums) == [-1.0, -1.0]
     assert np.array_equal(s.numpy(np.float32) != 0, s.numpy(np.float32) == 1)           # the input an output was aliased with
 
@@ -177,12 +177,12 @@ def test_refusals_leave_the_outputs_untouched(gpu_engine):
             all(np.array_equal(v.numpy(np.float32), h) for v, h in zip(dev, host)) and np.all(short.numpy(np.float32) == -7.0)
     for declined in (dict(cR=float("nan")), dict(cB=float("inf")), dict(x_scale=float("nan")), dict(y_scale=float("-inf")),
                      dict(kind=ITERS), dict(kind=-1), dict(kind=7)):
-        assert call(**declined) == L.LFPR_DECLINED and untouched2(), declined
+        assert call(**declined) == L.DECLINED and untouched2(), declined
     for bad in (dict(u_=short._h), dict(y_=short._h), dict(x=short._h), dict(rest=(short._h, *ins[3:])),
                 dict(u_=y._h), dict(u_=ins[0]), dict(u_=ins[1]), dict(u_=ins[4]), dict(y_=ins[1]), dict(y_=ins[5]),
                 dict(y0=None), dict(y_=None), dict(u_=None), dict(sums_=None), dict(rest=(None, *ins[3:]))):
         status = call(**bad)
-        assert status not in (0, L.LFPR_DECLINED) and untouched2(), bad
+        assert status not in (0, L.DECLINED) and untouched2(), bad
     assert list(sums) == [-1.0] * 5
     assert call() == 0 and not untouched2()                                               # the same arguments, nothing refused
 

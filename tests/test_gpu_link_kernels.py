@@ -31,7 +31,7 @@ SENTINEL = -7.0
 def _entries():
     from pygrank_amd import _lib as L
     names = ["pgh_link_plan_create", "pgh_link_plan_info", "pgh_link_plan_destroy", "pgh_link_auc", "pgh_link_predictions", "pgh_link_factors"]
-    entries = [L.link_entry(name) for name in names]
+    entries = [L.entry(name) for name in names]
     assert all(entry is not None for entry in entries)
     return entries
 

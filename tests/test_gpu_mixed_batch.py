@@ -34,7 +34,7 @@ def pg():
     pygrank_amd.load_backend("hip")
     assert _lib.runtime_name().startswith("hip:")
     for name in _lib.MIXED_SIGNATURES:
-        assert _lib.mixed_entry(name) is not None, name
+        assert _lib.entry(name) is not None, name
     return pygrank_amd
 
 
@@ -101,7 +101,7 @@ def _run_ppr(pg, G, P, alphas, rule, use_quotient=True, start=None, scales="norm
     sc = (C.c_double * b)(*norms) if scales == "norms" else None
     if entry == "pgh_ppr_run_batch_mixed":
         al = (C.c_double * b)(*alphas) if alphas is not None else None
-        status = L.mixed_entry(entry)(G["g"]._h, Pd._h, R._h, C.byref(cfg), al, sc, results)
+        status = L.entry(entry)(G["g"]._h, Pd._h, R._h, C.byref(cfg), al, sc, results)
     else:
         cfg.alpha = float(alphas[0])
         status = L.lib().pgh_ppr_run_batch(G["g"]._h, Pd._h, R._h, C.byref(cfg), sc, results)
@@ -122,8 +122,8 @@ def _run_poly(pg, G, P, schedules, rule):
     cfg = _cfg(rule, False, True)
     results = (L.LoopResult * b)()
     sc = (C.c_double * b)(*norms)
-    status = L.mixed_entry("pgh_poly_run_batch_mixed")(G["g"]._h, Pd._h, coeffs.ctypes.data_as(C.c_void_p), terms, R._h, C.byref(cfg),
-                                                       sc, results)
+    status = L.entry("pgh_poly_run_batch_mixed")(G["g"]._h, Pd._h, coeffs.ctypes.data_as(C.c_void_p), terms, R._h, C.byref(cfg),
+                                                 sc, results)
     return status, R.numpy(), results
 
 
@@ -381,10 +381,10 @@ def test_refusals(pg, graphs):
     rect = dict(g=pg.DeviceGraph.from_scipy(M), n=200)
     P = _columns(200, 3, seed=1)
     status, out, _ = _run_ppr(pg, rect, P, [0.5, 0.85, 0.9], L1)
-    assert status == L.MIXED_DECLINED and "square" in _last_error()
+    assert status == L.DECLINED and "square" in _last_error()
     assert np.all(out == 7.0)
     status, out, _ = _run_poly(pg, rect, P, [[1.0, 0.5]] * 3, L1)
-    assert status == L.MIXED_DECLINED and "square" in _last_error()
+    assert status == L.DECLINED and "square" in _last_error()
     assert np.all(out == 7.0)
     # a row-major graph (PGH_FORMAT=csr at upload): declined, nothing written
     A, directed, _ = cases.GRAPHS["rmat10_dir"]()
@@ -401,26 +401,26 @@ def test_refusals(pg, graphs):
     rm = dict(g=g, n=A.shape[0])
     P = _columns(A.shape[0], 3, seed=2)
     status, out, _ = _run_ppr(pg, rm, P, [0.5, 0.85, 0.9], L1)
-    assert status == L.MIXED_DECLINED and "blocked layout" in _last_error()
+    assert status == L.DECLINED and "blocked layout" in _last_error()
     assert np.all(out == 7.0)
     status, out, _ = _run_poly(pg, rm, P, [[1.0, 0.5]] * 3, L1)
-    assert status == L.MIXED_DECLINED and "blocked layout" in _last_error()
+    assert status == L.DECLINED and "blocked layout" in _last_error()
     assert np.all(out == 7.0)
     # errors, not declines: 65 columns, no columns, null alphas, a non-finite alpha
     G = graphs("rmat10_dir")
     status, out, _ = _run_ppr(pg, G, _columns(G["n"], 65, seed=3), [0.85] * 65, L1)
-    assert status not in (0, L.MIXED_DECLINED) and "[1, 64]" in _last_error()
+    assert status not in (0, L.DECLINED) and "[1, 64]" in _last_error()
     assert np.all(out == 7.0)
     status, out, _ = _run_poly(pg, G, _columns(G["n"], 65, seed=3), [[1.0, 0.5]] * 65, L1)
-    assert status not in (0, L.MIXED_DECLINED) and "[1, 64]" in _last_error()
+    assert status not in (0, L.DECLINED) and "[1, 64]" in _last_error()
     with pytest.raises(L.EngineError):                      # b = 0: no such slab exists for the entries to be handed
         DeviceMatrix.empty(G["n"], 0)
     P = _columns(G["n"], 3, seed=4)
     status, out, _ = _run_ppr(pg, G, P, None, L1)
-    assert status not in (0, L.MIXED_DECLINED) and "null" in _last_error()
+    assert status not in (0, L.DECLINED) and "null" in _last_error()
     assert np.all(out == 7.0)
     status, out, _ = _run_ppr(pg, G, P, [0.5, float("nan"), 0.9], L1)
-    assert status not in (0, L.MIXED_DECLINED) and "non-finite" in _last_error()
+    assert status not in (0, L.DECLINED) and "non-finite" in _last_error()
     assert np.all(out == 7.0)
     # ... and the same inputs with their alphas run
     status, out, res = _run_ppr(pg, G, P, [0.5, 0.85, 0.9], L1)

@@ -25,7 +25,7 @@ SENTINEL = -77.0
 
 def _entry(name):
     from pygrank_amd import _lib as L
-    fn = L.oversample_entry(name)
+    fn = L.entry(name)
     assert fn is not None, name
     return fn
 
@@ -168,7 +168,7 @@ def test_update_then_floor_agree(gpu_engine):
 def test_declined_and_erroneous_calls_write_nothing(gpu_engine):
     pg = gpu_engine
     from pygrank_amd import _lib as L
-    DECLINED = L.OVERSAMPLE_DECLINED
+    DECLINED = L.DECLINED
     floor, resample, forms, update = (_entry(name) for name in ("pgh_seed_floor", "pgh_seed_resample", "pgh_boost_forms", "pgh_boost_update"))
     n = 65
 

@@ -31,8 +31,8 @@ def _handle(x):
 def _call(L, scores, known_vec, known_mat, exclude_vec, exclude_mat, factors, eps, groups, b=None):
     b = scores.b if b is None else b
     out = np.full(SLOTS * b + 4, SENTINEL)
-    status = L.supervised_entry("pgh_pair_forms")(_handle(scores), _handle(known_vec), _handle(known_mat), _handle(exclude_vec),
-                                                  _handle(exclude_mat), _ptr(factors), float(eps), groups, _ptr(out))
+    status = L.entry("pgh_pair_forms")(_handle(scores), _handle(known_vec), _handle(known_mat), _handle(exclude_vec),
+                                       _handle(exclude_mat), _ptr(factors), float(eps), groups, _ptr(out))
     return status, out
 
 
@@ -90,7 +90,7 @@ SHAPES = [(n, b) for n in (1, 3, 257, 1024, 20037) for b in (1, 3, 5, 32, 33, 64
 def test_pair_forms_against_numpy(gpu_engine, n, b):
     from pygrank_amd import _lib as L
     from pygrank_amd.device import DeviceMatrix, DeviceVector
-    assert L.supervised_entry("pgh_pair_forms") is not None
+    assert L.entry("pgh_pair_forms") is not None
     S0, k, K, factors, patterns, E = _inputs(n, b, seed=7000 + 64 * n + b)
     eps = float(np.finfo(np.float32).eps)
     dk, dK = DeviceVector.from_host(k), DeviceMatrix.from_host(K)
@@ -143,7 +143,7 @@ def test_pair_forms_against_numpy(gpu_engine, n, b):
 def test_pair_forms_non_finite_slots_agree_with_numpy_in_kind(gpu_engine):
     from pygrank_amd import _lib as L
     from pygrank_amd.device import DeviceMatrix, DeviceVector
-    assert L.supervised_entry("pgh_pair_forms") is not None
+    assert L.entry("pgh_pair_forms") is not None
     n, eps = 1000, float(np.finfo(np.float32).eps)
     rng = np.random.default_rng(31)
     k = (rng.random(n) < 0.3).astype(np.float32)                      # 0 / 1 labels: log(k) is -inf or 0
@@ -166,12 +166,12 @@ def test_pair_forms_non_finite_slots_agree_with_numpy_in_kind(gpu_engine):
 def test_pair_forms_refusals_leave_the_output_alone(gpu_engine):
     from pygrank_amd import _lib as L
     from pygrank_amd.device import DeviceMatrix, DeviceVector
-    assert L.supervised_entry("pgh_pair_forms") is not None
+    assert L.entry("pgh_pair_forms") is not None
     n, eps = 300, float(np.finfo(np.float32).eps)
     rng = np.random.default_rng(5)
 
     def untouched(status, out, declined=True):
-        assert (status == L.PAIR_DECLINED) if declined else (status not in (0, L.PAIR_DECLINED)), status
+        assert (status == L.DECLINED) if declined else (status not in (0, L.DECLINED)), status
         assert np.all(out == SENTINEL)
     k, K = DeviceVector.from_host(rng.random(n)), DeviceMatrix.from_host(rng.random((n, 4)))
     mat = DeviceMatrix.from_host(rng.random((n, 4)))
@@ -194,8 +194,8 @@ def test_pair_forms_refusals_leave_the_output_alone(gpu_engine):
     untouched(*_call(L, mat, None, None, None, None, None, eps, L.PAIR_MOMENTS), declined=False)
     untouched(*_call(L, mat, k, None, k, K, None, eps, L.PAIR_MOMENTS), declined=False)
     untouched(*_call(L, mat, k, None, None, None, None, eps, 7), declined=False)
-    status = L.supervised_entry("pgh_pair_forms")(mat._h, k._h, None, None, None, None, eps, L.PAIR_MOMENTS, None)
-    assert status not in (0, L.PAIR_DECLINED)
+    status = L.entry("pgh_pair_forms")(mat._h, k._h, None, None, None, None, eps, L.PAIR_MOMENTS, None)
+    assert status not in (0, L.DECLINED)
     # and the entry still serves the next request
     status, out = _call(L, mat, k, None, None, None, None, eps, L.PAIR_LOGS)
     assert status == 0 and np.all(out[:12] != SENTINEL)

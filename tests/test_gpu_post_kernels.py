@@ -23,7 +23,7 @@ SENTINEL = -77.0
 
 def _entry(name):
     from pygrank_amd import _lib as L
-    fn = L.post_entry(name)
+    fn = L.entry(name)
     assert fn is not None, name
     return fn
 
@@ -106,8 +106,8 @@ def test_kth_largest_declines_65_columns_and_keeps_a_nan_to_its_column(gpu_engin
     select = _entry("pgh_post_kth_largest")
     wide = pg.DeviceMatrix.from_host(np.ones((5, 65)))
     values = _doubles(65)
-    assert select(wide._h, 1, values) == L.POST_DECLINED and list(values) == [SENTINEL] * 65
-    assert select(None, 1, values) not in (0, L.POST_DECLINED)
+    assert select(wide._h, 1, values) == L.DECLINED and list(values) == [SENTINEL] * 65
+    assert select(None, 1, values) not in (0, L.DECLINED)
     for n in (1, 65, 4099):
         S = _slab(n, 64)[:, :3].copy()
         S[n // 2, 1] = np.nan
@@ -123,11 +123,11 @@ def test_kth_largest_declines_65_columns_and_keeps_a_nan_to_its_column(gpu_engin
 def _refusals(call, pg, L, n=5):
     """call(m, out) -> status: 65 columns decline, other shapes and out == m are errors; the output keeps its sentinel."""
     wide, wide_out = pg.DeviceMatrix.from_host(np.ones((n, 65))), pg.DeviceMatrix.from_host(np.full((n, 65), SENTINEL))
-    assert call(wide, wide_out) == L.POST_DECLINED
+    assert call(wide, wide_out) == L.DECLINED
     assert np.all(wide_out.numpy() == SENTINEL)
     m, other = pg.DeviceMatrix.from_host(np.ones((n, 3))), pg.DeviceMatrix.from_host(np.full((n, 2), SENTINEL))
-    assert call(m, other) not in (0, L.POST_DECLINED) and np.all(other.numpy() == SENTINEL)
-    assert call(m, m) not in (0, L.POST_DECLINED) and np.all(m.numpy() == 1.0)
+    assert call(m, other) not in (0, L.DECLINED) and np.all(other.numpy() == SENTINEL)
+    assert call(m, m) not in (0, L.DECLINED) and np.all(m.numpy() == 1.0)
 
 
 def _sentinel_slab(pg, n, b):
@@ -262,7 +262,7 @@ def test_refusals_leave_the_output_untouched(gpu_engine):
     _refusals(lambda m, out: _entry("pgh_post_row_op")(m._h, v._h, L.POST_ROW_SWEEP, 0.0, out._h), pg, L)
     _refusals(lambda m, out: _entry("pgh_post_ordinals")(m._h, out._h), pg, L)
     m, out = pg.DeviceMatrix.from_host(np.ones((5, 3))), _sentinel_slab(pg, 5, 3)
-    assert _entry("pgh_post_row_op")(m._h, v._h, 7, 0.0, out._h) not in (0, L.POST_DECLINED)            # an unknown op
-    assert _entry("pgh_post_row_op")(m._h, short._h, L.POST_ROW_SUB, 0.0, out._h) not in (0, L.POST_DECLINED)
-    assert _entry("pgh_post_col_threshold")(m._h, None, 1, out._h) not in (0, L.POST_DECLINED)
+    assert _entry("pgh_post_row_op")(m._h, v._h, 7, 0.0, out._h) not in (0, L.DECLINED)            # an unknown op
+    assert _entry("pgh_post_row_op")(m._h, short._h, L.POST_ROW_SUB, 0.0, out._h) not in (0, L.DECLINED)
+    assert _entry("pgh_post_col_threshold")(m._h, None, 1, out._h) not in (0, L.DECLINED)
     assert np.all(out.numpy() == SENTINEL)

@@ -56,7 +56,7 @@ def _expected(pers, sens, ranks, rank_max, P, buckets, skew):
 
 def _call(vectors, rank_max, P, buckets, probes, skew, out):
     from pygrank_amd import _lib as L
-    entry = L.fair_entry("pgh_prior_edit")
+    entry = L.entry("pgh_prior_edit")
     assert entry is not None
     return entry(vectors[0]._h, vectors[1]._h, vectors[2]._h, float(rank_max), P.ctypes.data_as(C.c_void_p), buckets, probes, skew, out._h)
 
@@ -107,14 +107,14 @@ def test_refusals_write_nothing(gpu_engine):
     declined = [(_params(rng, 65, 1), 1, 65, 1.0, filled(n, 65)), (_params(rng, 10, 5), 5, 10, 1.0, filled(n, 10)),
                 (nan, 1, 10, 1.0, filled(n, 10)), (good, 1, 10, 0.0, filled(n, 10)), (good, 1, 10, float("inf"), filled(n, 10))]
     for P, buckets, probes, rank_max, out in declined:
-        assert _call(vectors, rank_max, P, buckets, probes, 0, out) == L.FAIR_DECLINED, (buckets, probes, rank_max)
+        assert _call(vectors, rank_max, P, buckets, probes, 0, out) == L.DECLINED, (buckets, probes, rank_max)
         assert b"declined" in L.lib().pgh_last_error()
         assert untouched(out)
     short = pg.DeviceVector.from_host(np.ones(n - 1))
     errors = [([vectors[0], short, vectors[2]], filled(n, 10)), (vectors, filled(n - 1, 10)), (vectors, filled(n, 9))]
     for operands, out in errors:
         status = _call(operands, 1.0, good, 1, 10, 0, out)
-        assert status not in (0, L.FAIR_DECLINED)
+        assert status not in (0, L.DECLINED)
         assert untouched(out)
     out = filled(n, 10)
     assert _call(vectors, 1.0, good, 1, 10, 0, out) == 0 and not untouched(out)

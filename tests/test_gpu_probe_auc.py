@@ -47,18 +47,18 @@ def _check(pg, n, terms, probes, n_pos, kind="dense", exclude="some", seed=0, ne
     d_known = DeviceVector.from_host(known)
     d_ex = DeviceVector.from_host(ex) if exclude != "none" else None
     plan = L.c_plan()
-    L.check(L.tune_entry("pgh_probe_plan_create")(d_known._h, None if d_ex is None else d_ex._h, C.byref(plan)))
+    L.check(L.entry("pgh_probe_plan_create")(d_known._h, None if d_ex is None else d_ex._h, C.byref(plan)))
     try:
         pos_count, neg_count = C.c_int64(), C.c_int64()
-        L.check(L.tune_entry("pgh_probe_plan_info")(plan, C.byref(pos_count), C.byref(neg_count)))
+        L.check(L.entry("pgh_probe_plan_info")(plan, C.byref(pos_count), C.byref(neg_count)))
         keep = ex == 0
         assert pos_count.value == n_pos == int(np.sum(keep & (known != 0)))
         assert neg_count.value == int(np.sum(keep & (known == 0)))
         out = (C.c_double * probes)(*([-7.0] * probes))
         flat = np.ascontiguousarray(coeffs, dtype=np.float64)
-        L.check(L.tune_entry("pgh_probe_auc")(slab._h, flat.ctypes.data_as(C.c_void_p), terms, probes, plan, out))
+        L.check(L.entry("pgh_probe_auc")(slab._h, flat.ctypes.data_as(C.c_void_p), terms, probes, plan, out))
     finally:
-        L.check(L.tune_entry("pgh_probe_plan_destroy")(plan))
+        L.check(L.entry("pgh_probe_plan_destroy")(plan))
     product = slab.gemm(coeffs)
     scores = product.numpy()                                 # f32 values, exactly
     worst = 0.0
@@ -119,7 +119,7 @@ def test_declines_write_nothing(gpu_engine):
     slab = DeviceMatrix.from_host(rng.random((n, 64)))
     known = np.zeros(n)
     known[rng.choice(n, 30, replace=False)] = 1.0
-    create, destroy, auc = (L.tune_entry(name) for name in ("pgh_probe_plan_create", "pgh_probe_plan_destroy", "pgh_probe_auc"))
+    create, destroy, auc = (L.entry(name) for name in ("pgh_probe_plan_create", "pgh_probe_plan_destroy", "pgh_probe_auc"))
 
     def call(known_host, coeffs, terms, probes):
         plan = L.c_plan()
@@ -130,14 +130,14 @@ def test_declines_write_nothing(gpu_engine):
         status = auc(slab._h, flat.ctypes.data_as(C.c_void_p), terms, probes, plan, out)
         L.check(destroy(plan))
         return status, list(out)
-    assert call(known, rng.random((65, 3)), 65, 3) == (L.TUNE_DECLINED, [-7.0] * 3)
-    assert call(np.zeros(n), rng.random((10, 3)), 10, 3) == (L.TUNE_DECLINED, [-7.0] * 3)
-    assert call(np.ones(n), rng.random((10, 3)), 10, 3) == (L.TUNE_DECLINED, [-7.0] * 3)
+    assert call(known, rng.random((65, 3)), 65, 3) == (L.DECLINED, [-7.0] * 3)
+    assert call(np.zeros(n), rng.random((10, 3)), 10, 3) == (L.DECLINED, [-7.0] * 3)
+    assert call(np.ones(n), rng.random((10, 3)), 10, 3) == (L.DECLINED, [-7.0] * 3)
     bad = rng.random((10, 3))
     bad[4, 1] = np.nan
-    assert call(known, bad, 10, 3) == (L.TUNE_DECLINED, [-7.0] * 3)
+    assert call(known, bad, 10, 3) == (L.DECLINED, [-7.0] * 3)
     bad[4, 1] = np.inf
-    assert call(known, bad, 10, 3) == (L.TUNE_DECLINED, [-7.0] * 3)
+    assert call(known, bad, 10, 3) == (L.DECLINED, [-7.0] * 3)
     assert b"declined" in L.lib().pgh_last_error()
     status, out = call(known, rng.random((10, 3)), 10, 3)
     assert status == 0 and all(0.0 <= v <= 1.0 for v in out)
@@ -152,9 +152,9 @@ def test_too_many_positives_decline(gpu_engine):
     known[:L.TUNE_MAX_POSITIVES + 1] = 1.0
     plan = L.c_plan()
     d_known = DeviceVector.from_host(known)                  # (kept in a name: the handle must outlive the call)
-    L.check(L.tune_entry("pgh_probe_plan_create")(d_known._h, None, C.byref(plan)))
+    L.check(L.entry("pgh_probe_plan_create")(d_known._h, None, C.byref(plan)))
     out = (C.c_double * 2)(-7.0, -7.0)
     coeffs = np.ones((8, 2))
-    status = L.tune_entry("pgh_probe_auc")(slab._h, coeffs.ctypes.data_as(C.c_void_p), 8, 2, plan, out)
-    L.check(L.tune_entry("pgh_probe_plan_destroy")(plan))
-    assert status == L.TUNE_DECLINED and list(out) == [-7.0, -7.0], L.lib().pgh_last_error()
+    status = L.entry("pgh_probe_auc")(slab._h, coeffs.ctypes.data_as(C.c_void_p), 8, 2, plan, out)
+    L.check(L.entry("pgh_probe_plan_destroy")(plan))
+    assert status == L.DECLINED and list(out) == [-7.0, -7.0], L.lib().pgh_last_error()

@@ -45,7 +45,7 @@ def per_column():
 @pytest.mark.parametrize("key", rc.GRAPHS)
 def test_golden_cases_on_both_routes(gpu_engine, fx, rankings, per_column, key):
     from pygrank_amd import _lib as L
-    assert all(L.rank_entry(name) is not None for name in L.RANK_SIGNATURES)
+    assert all(L.entry(name) is not None for name in L.RANK_SIGNATURES)
     ranking = rankings(key)
     for excluded in (False, True):
         per_column(False)

@@ -19,7 +19,7 @@ def fx():
 def pg(gpu_engine):
     from pygrank_amd import _lib
     for name in _lib.MIXED_SIGNATURES:
-        assert _lib.mixed_entry(name) is not None, name
+        assert _lib.entry(name) is not None, name
     return gpu_engine
 
 

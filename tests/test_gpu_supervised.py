@@ -47,7 +47,7 @@ def per_column():
 @pytest.mark.parametrize("key", GRAPHS)
 def test_golden_cases_on_both_routes(gpu_engine, fx, all_bases, per_column, key):
     from pygrank_amd import _lib as L
-    assert L.supervised_entry("pgh_pair_forms") is not None
+    assert L.entry("pgh_pair_forms") is not None
     bases = all_bases(key)
     columns = [bases.signals[base] for base in sc.BASES]
     for excluded in (False, True):

@@ -41,7 +41,7 @@ def test_krylov_header_table_and_makefile_agree():
     for header in headers:
         if header != "pgh_krylov.h":
             assert set(ENTRIES).isdisjoint(_declared(header)), header
-    assert _lib.KRYLOV_DECLINED == _defined("pgh_krylov.h", "PGH_KRYLOV_DECLINED")
+    assert _lib.DECLINED == _defined("pgh_krylov.h", "PGH_KRYLOV_DECLINED")
     assert _lib.KRYLOV_MAX_DIMS == _defined("pgh_krylov.h", "PGH_KRYLOV_MAX_DIMS")
     assert _lib.KRYLOV_MAX_PROBES == _defined("pgh_krylov.h", "PGH_KRYLOV_MAX_PROBES")
     vec, mat, dbl, dblp = C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double)
@@ -59,7 +59,7 @@ def test_krylov_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_krylov_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_krylov(cdll)
+    bound = _lib.bind_optional(cdll, _lib.KRYLOV_SIGNATURES)
     assert sorted(bound) == ENTRIES
     for name in ENTRIES:
         assert hasattr(cdll, name), name
@@ -69,4 +69,4 @@ def test_hip_library_exports_and_binds_the_krylov_entries(hip_lib):
 def test_host_double_has_no_krylov_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.KRYLOV_SIGNATURES:
-        assert _lib.krylov_entry(name) is None, name
+        assert _lib.entry(name) is None, name

@@ -19,7 +19,7 @@ SMALL = [name for name, case in kc.CASES.items() if case[4] <= kc.BASIS_DIMS]
 @pytest.mark.parametrize("name", list(kc.CASES))
 def test_golden_case(host_engine, name):
     from pygrank_amd import _lib as L
-    assert L.krylov_entry("pgh_lanczos_close") is None and L.krylov_entry("pgh_krylov_residuals") is None
+    assert L.entry("pgh_lanczos_close") is None and L.entry("pgh_krylov_residuals") is None
     algo, _ = kc.check(host_engine, name)
     dims = kc.CASES[name][4]
     assert algo.last_loop["spmv"] == dims and algo.last_loop["dims"] == dims and algo.last_loop["converged"]
@@ -223,7 +223,7 @@ class _NumpyEntries:
     def __enter__(self):
         from pygrank_amd import _lib as L
         self.lib = L.lib()
-        assert L.krylov_entry("pgh_lanczos_close") is None
+        assert L.entry("pgh_lanczos_close") is None
         entries = kc.numpy_entries(self.lib)
 
         def close(*args):

@@ -31,12 +31,12 @@ def test_lfpr_header_table_and_makefile_agree():
     import ctypes as C
     from pygrank_amd import _lib
     assert sorted(_lib.LFPR_SIGNATURES) == _declared("pgh_lfpr.h") == ENTRIES
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES, _lib.MEASURE_SIGNATURES, _lib.SUPERVISED_SIGNATURES,
-                  _lib.FAIR_SIGNATURES, _lib.MIXED_SIGNATURES):
-        assert set(_lib.LFPR_SIGNATURES).isdisjoint(other)
-    for header in ("pgh.h", "pgh_batch.h", "pgh_tune.h", "pgh_measure.h", "pgh_supervised.h", "pgh_fair.h", "pgh_mixed.h"):
-        assert set(ENTRIES).isdisjoint(_declared(header)), header
-    assert _lib.LFPR_DECLINED == _defined("pgh_lfpr.h", "PGH_LFPR_DECLINED")
+    assert _lib.OPTIONAL["pgh_lfpr.h"] is _lib.LFPR_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_lfpr.h":
+            assert set(_lib.LFPR_SIGNATURES).isdisjoint(other), header
+            assert set(ENTRIES).isdisjoint(_declared(header)), header
+    assert _lib.DECLINED == _defined("pgh_lfpr.h", "PGH_LFPR_DECLINED")
     vec, dbl = C.c_void_p, C.c_double
     restype, argtypes = _lib.LFPR_SIGNATURES["pgh_lfpr_setup"]
     assert restype is C.c_int
@@ -52,7 +52,7 @@ def test_lfpr_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_lfpr_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_lfpr(cdll)
+    bound = _lib.bind_optional(cdll, _lib.LFPR_SIGNATURES)
     assert sorted(bound) == ENTRIES
     for name in ENTRIES:
         assert hasattr(cdll, name), name
@@ -62,4 +62,4 @@ def test_hip_library_exports_and_binds_the_lfpr_entries(hip_lib):
 def test_host_double_has_no_lfpr_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.LFPR_SIGNATURES:
-        assert _lib.lfpr_entry(name) is None, name
+        assert _lib.entry(name) is None, name

@@ -10,7 +10,7 @@ import lfpr_common as lc
 @pytest.mark.parametrize("key", lc.GRAPHS)
 def test_golden_case(host_engine, key, name):
     from pygrank_amd import _lib as L
-    assert L.lfpr_entry("pgh_lfpr_setup") is None and L.lfpr_entry("pgh_lfpr_close") is None
+    assert L.entry("pgh_lfpr_setup") is None and L.entry("pgh_lfpr_close") is None
     algo, _ = lc.Case(host_engine, key).check(name)
     if name == "original":                                  # the shared manager counts the inner PageRank and the outer loop
         assert algo.convergence.iteration > int(lc.fixture()[f"{key}/original/inner"]) > 0
@@ -72,7 +72,7 @@ def test_fused_loop_with_numpy_entries(host_engine, key, name):
     """The fused loop's host side on the double's resident iterates, the two entries replaced by numpy evaluations of their header."""
     from pygrank_amd import _lib as L
     cdll = L.lib()
-    assert L.lfpr_entry("pgh_lfpr_close") is None
+    assert L.entry("pgh_lfpr_close") is None
     calls = dict(pgh_lfpr_setup=0, pgh_lfpr_close=0)
 
     def counted(fn, which):
@@ -110,13 +110,13 @@ def test_close_declining_in_mid_loop_goes_on_in_primitives(host_engine, name, at
     with the manager's count intact -- the ranks and the iteration count of the primitive route."""
     from pygrank_amd import _lib as L
     cdll = L.lib()
-    assert L.lfpr_entry("pgh_lfpr_close") is None
+    assert L.entry("pgh_lfpr_close") is None
     entries = lc.numpy_entries(cdll)
     closes = []
 
     def close(*args):
         closes.append(len(closes) + 1)
-        return L.LFPR_DECLINED if len(closes) == at else entries["pgh_lfpr_close"](*args)
+        return L.DECLINED if len(closes) == at else entries["pgh_lfpr_close"](*args)
     saved = _with_entries(cdll, dict(entries, pgh_lfpr_close=close))
     try:
         case = lc.Case(host_engine, "weighted300")
@@ -135,14 +135,14 @@ def test_end_declining_falls_back_to_the_primitive_end(host_engine):
     """The close that stands for _end declines (as the loop itself decides for a zero quotient): _end runs in backend primitives."""
     from pygrank_amd import _lib as L
     cdll = L.lib()
-    assert L.lfpr_entry("pgh_lfpr_close") is None
+    assert L.entry("pgh_lfpr_close") is None
     entries = lc.numpy_entries(cdll)
     declined = []
 
     def close(y0, x, *rest):
         if y0 == x:                                           # only _end passes the iterate as both operands
             declined.append(1)
-            return L.LFPR_DECLINED
+            return L.DECLINED
         return entries["pgh_lfpr_close"](y0, x, *rest)
     saved = _with_entries(cdll, dict(entries, pgh_lfpr_close=close))
     try:

@@ -41,7 +41,7 @@ def test_link_header_table_and_makefile_agree():
     for header in headers:
         if header != "pgh_link.h":
             assert set(ENTRIES).isdisjoint(_declared(header)), header
-    assert _lib.LINK_DECLINED == _defined("pgh_link.h", "PGH_LINK_DECLINED") == 2
+    assert _lib.DECLINED == _defined("pgh_link.h", "PGH_LINK_DECLINED") == 2
     assert _lib.LINK_MAX_PAIRS == _defined("pgh_link.h", "PGH_LINK_MAX_PAIRS") == 2 ** 27
     assert _lib.LINK_COS == _defined("pgh_link.h", "PGH_LINK_COS")
     assert _lib.LINK_DOT == _defined("pgh_link.h", "PGH_LINK_DOT")
@@ -67,7 +67,7 @@ def test_link_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_link_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_link(cdll)
+    bound = _lib.bind_optional(cdll, _lib.LINK_SIGNATURES)
     assert sorted(bound) == ENTRIES
     for name in ENTRIES:
         assert hasattr(cdll, name), name
@@ -77,4 +77,4 @@ def test_hip_library_exports_and_binds_the_link_entries(hip_lib):
 def test_host_double_has_no_link_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.LINK_SIGNATURES:
-        assert _lib.link_entry(name) is None, name
+        assert _lib.entry(name) is None, name

@@ -32,9 +32,11 @@ def hip_lib():
 def test_measure_header_and_table_agree():
     from pygrank_amd import _lib
     assert sorted(_lib.MEASURE_SIGNATURES) == _declared("pgh_measure.h") == ["pgh_cut_forms", "pgh_mat_col_stats"]
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES):
-        assert set(_lib.MEASURE_SIGNATURES).isdisjoint(other)
-    assert _lib.MEASURE_DECLINED == _defined("pgh_measure.h", "PGH_MEASURE_DECLINED")
+    assert _lib.OPTIONAL["pgh_measure.h"] is _lib.MEASURE_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_measure.h":
+            assert set(_lib.MEASURE_SIGNATURES).isdisjoint(other), header
+    assert _lib.DECLINED == _defined("pgh_measure.h", "PGH_MEASURE_DECLINED")
     assert _lib.CUT_ALL == _defined("pgh_measure.h", "PGH_CUT_ALL")
     assert _lib.CUT_INTERNAL == _defined("pgh_measure.h", "PGH_CUT_INTERNAL")
     # pgh.h keeps its own table: nothing of this header leaked into it
@@ -44,7 +46,7 @@ def test_measure_header_and_table_agree():
 def test_hip_library_exports_and_binds_the_measure_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_measure(cdll)
+    bound = _lib.bind_optional(cdll, _lib.MEASURE_SIGNATURES)
     assert sorted(bound) == _declared("pgh_measure.h")
     for name in _declared("pgh_measure.h"):
         assert hasattr(cdll, name), name
@@ -54,4 +56,4 @@ def test_hip_library_exports_and_binds_the_measure_entries(hip_lib):
 def test_host_double_has_no_measure_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.MEASURE_SIGNATURES:
-        assert _lib.measure_entry(name) is None, name
+        assert _lib.entry(name) is None, name

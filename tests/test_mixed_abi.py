@@ -31,10 +31,11 @@ def test_mixed_header_table_and_makefile_agree():
     import ctypes as C
     from pygrank_amd import _lib
     assert sorted(_lib.MIXED_SIGNATURES) == _declared("pgh_mixed.h") == ENTRIES
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES, _lib.MEASURE_SIGNATURES, _lib.SUPERVISED_SIGNATURES,
-                  _lib.FAIR_SIGNATURES):
-        assert set(_lib.MIXED_SIGNATURES).isdisjoint(other)
-    assert _lib.MIXED_DECLINED == _defined("pgh_mixed.h", "PGH_MIXED_DECLINED")
+    assert _lib.OPTIONAL["pgh_mixed.h"] is _lib.MIXED_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_mixed.h":
+            assert set(_lib.MIXED_SIGNATURES).isdisjoint(other), header
+    assert _lib.DECLINED == _defined("pgh_mixed.h", "PGH_MIXED_DECLINED")
     cfg, res = C.POINTER(_lib.LoopCfg), C.POINTER(_lib.LoopResult)
     restype, argtypes = _lib.MIXED_SIGNATURES["pgh_ppr_run_batch_mixed"]
     assert restype is C.c_int
@@ -57,7 +58,7 @@ def test_mixed_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_mixed_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_mixed(cdll)
+    bound = _lib.bind_optional(cdll, _lib.MIXED_SIGNATURES)
     assert sorted(bound) == _declared("pgh_mixed.h")
     for name in _declared("pgh_mixed.h"):
         assert hasattr(cdll, name), name
@@ -67,4 +68,4 @@ def test_hip_library_exports_and_binds_the_mixed_entries(hip_lib):
 def test_host_double_has_no_mixed_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.MIXED_SIGNATURES:
-        assert _lib.mixed_entry(name) is None, name
+        assert _lib.entry(name) is None, name

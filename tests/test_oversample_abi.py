@@ -9,7 +9,6 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "pygrank_amd", "csrc", "libpgh_hip.so")
 ENTRIES = ["pgh_boost_forms", "pgh_boost_update", "pgh_seed_floor", "pgh_seed_resample"]
-OTHER_HEADERS = ("pgh.h", "pgh_batch.h", "pgh_tune.h", "pgh_measure.h", "pgh_supervised.h", "pgh_fair.h", "pgh_mixed.h", "pgh_lfpr.h")
 
 
 def _declared(header):
@@ -32,12 +31,12 @@ def test_oversample_header_table_and_makefile_agree():
     import ctypes as C
     from pygrank_amd import _lib
     assert sorted(_lib.OVERSAMPLE_SIGNATURES) == _declared("pgh_oversample.h") == ENTRIES
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES, _lib.MEASURE_SIGNATURES, _lib.SUPERVISED_SIGNATURES,
-                  _lib.FAIR_SIGNATURES, _lib.MIXED_SIGNATURES, _lib.LFPR_SIGNATURES):
-        assert set(_lib.OVERSAMPLE_SIGNATURES).isdisjoint(other)
-    for header in OTHER_HEADERS:
-        assert set(ENTRIES).isdisjoint(_declared(header)), header
-    assert _lib.OVERSAMPLE_DECLINED == _defined("pgh_oversample.h", "PGH_OVERSAMPLE_DECLINED")
+    assert _lib.OPTIONAL["pgh_oversample.h"] is _lib.OVERSAMPLE_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_oversample.h":
+            assert set(_lib.OVERSAMPLE_SIGNATURES).isdisjoint(other), header
+            assert set(ENTRIES).isdisjoint(_declared(header)), header
+    assert _lib.DECLINED == _defined("pgh_oversample.h", "PGH_OVERSAMPLE_DECLINED")
     assert _lib.OVERSAMPLE_MAX_COLS == _defined("pgh_oversample.h", "PGH_OVERSAMPLE_MAX_COLS") == 64
     mat, f64p, i64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)
     want = dict(pgh_seed_floor=[mat, mat, f64p, i64p],
@@ -54,7 +53,7 @@ def test_oversample_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_oversample_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_oversample(cdll)
+    bound = _lib.bind_optional(cdll, _lib.OVERSAMPLE_SIGNATURES)
     assert sorted(bound) == ENTRIES
     for name in ENTRIES:
         assert hasattr(cdll, name), name
@@ -64,4 +63,4 @@ def test_hip_library_exports_and_binds_the_oversample_entries(hip_lib):
 def test_host_double_has_no_oversample_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.OVERSAMPLE_SIGNATURES:
-        assert _lib.oversample_entry(name) is None, name
+        assert _lib.entry(name) is None, name

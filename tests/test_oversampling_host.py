@@ -12,7 +12,7 @@ import oversampling_common as oc
 @pytest.mark.parametrize("key", oc.GRAPHS)
 def test_seed_oversampling_golden_case(host_engine, key, method):
     from pygrank_amd import _lib as L
-    assert all(L.oversample_entry(name) is None for name in L.OVERSAMPLE_SIGNATURES)
+    assert all(L.entry(name) is None for name in L.OVERSAMPLE_SIGNATURES)
     algo, _ = oc.Case(host_engine, key).check_seed_oversampling(method)
     assert algo.last_passes["fused"] == 0
 
@@ -170,7 +170,7 @@ def test_fused_route_with_numpy_entries(host_engine, which):
     pg = host_engine
     from pygrank_amd import _lib as L
     cdll = L.lib()
-    assert L.oversample_entry("pgh_seed_floor") is None
+    assert L.entry("pgh_seed_floor") is None
     calls = {name: 0 for name in L.OVERSAMPLE_SIGNATURES}
 
     def counted(fn, name):
@@ -208,13 +208,13 @@ def test_a_declined_entry_sends_the_rest_of_the_run_to_the_primitives(host_engin
     pg = host_engine
     from pygrank_amd import _lib as L
     cdll = L.lib()
-    assert L.oversample_entry("pgh_boost_update") is None
+    assert L.entry("pgh_boost_update") is None
     entries = oc.numpy_entries(cdll)
     updates = []
 
     def update(*args):
         updates.append(1)
-        return L.OVERSAMPLE_DECLINED if len(updates) == 2 else entries["pgh_boost_update"](*args)
+        return L.DECLINED if len(updates) == 2 else entries["pgh_boost_update"](*args)
     saved = cdll._pgh_oversample_entries
     cdll._pgh_oversample_entries = dict(entries, pgh_boost_update=update)
     try:

@@ -9,8 +9,6 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "pygrank_amd", "csrc", "libpgh_hip.so")
 ENTRIES = ["pgh_post_col_affine", "pgh_post_col_threshold", "pgh_post_kth_largest", "pgh_post_ordinals", "pgh_post_row_op"]
-OTHER_HEADERS = ("pgh.h", "pgh_batch.h", "pgh_tune.h", "pgh_measure.h", "pgh_supervised.h", "pgh_fair.h", "pgh_mixed.h", "pgh_lfpr.h",
-                 "pgh_oversample.h", "pgh_rank.h", "pgh_krylov.h", "pgh_link.h", "pgh_arnoldi.h")
 
 
 def _declared(header):
@@ -33,13 +31,12 @@ def test_post_header_table_and_makefile_agree():
     import ctypes as C
     from pygrank_amd import _lib
     assert sorted(_lib.POST_SIGNATURES) == _declared("pgh_post.h") == ENTRIES
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES, _lib.MEASURE_SIGNATURES, _lib.SUPERVISED_SIGNATURES,
-                  _lib.FAIR_SIGNATURES, _lib.MIXED_SIGNATURES, _lib.LFPR_SIGNATURES, _lib.OVERSAMPLE_SIGNATURES, _lib.RANK_SIGNATURES,
-                  _lib.KRYLOV_SIGNATURES, _lib.LINK_SIGNATURES, _lib.ARNOLDI_SIGNATURES):
-        assert set(_lib.POST_SIGNATURES).isdisjoint(other)
-    for header in OTHER_HEADERS:
-        assert set(ENTRIES).isdisjoint(_declared(header)), header
-    assert _lib.POST_DECLINED == _defined("pgh_post.h", "PGH_POST_DECLINED") == 2
+    assert _lib.OPTIONAL["pgh_post.h"] is _lib.POST_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_post.h":
+            assert set(_lib.POST_SIGNATURES).isdisjoint(other), header
+            assert set(ENTRIES).isdisjoint(_declared(header)), header
+    assert _lib.DECLINED == _defined("pgh_post.h", "PGH_POST_DECLINED") == 2
     assert _lib.POST_MAX_COLS == _defined("pgh_post.h", "PGH_POST_MAX_COLS") == 64
     assert _lib.POST_ROW_SUB == _defined("pgh_post.h", "PGH_POST_ROW_SUB")
     assert _lib.POST_ROW_SWEEP == _defined("pgh_post.h", "PGH_POST_ROW_SWEEP")
@@ -59,7 +56,7 @@ def test_post_header_table_and_makefile_agree():
 def test_hip_library_exports_and_binds_the_post_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_post(cdll)
+    bound = _lib.bind_optional(cdll, _lib.POST_SIGNATURES)
     assert sorted(bound) == ENTRIES
     for name in ENTRIES:
         assert hasattr(cdll, name), name
@@ -69,4 +66,4 @@ def test_hip_library_exports_and_binds_the_post_entries(hip_lib):
 def test_host_double_has_no_post_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.POST_SIGNATURES:
-        assert _lib.post_entry(name) is None, name
+        assert _lib.entry(name) is None, name

@@ -13,7 +13,7 @@ import postprocess_common as pc
 @pytest.mark.parametrize("key", pc.GRAPHS)
 def test_propagate_keeps_the_inner_batch(host_engine, key, width, name):
     from pygrank_amd import _lib as L
-    assert all(L.post_entry(entry) is None for entry in L.POST_SIGNATURES)
+    assert all(L.entry(entry) is None for entry in L.POST_SIGNATURES)
     _, steps, _, _ = pc.check_propagate(host_engine, key, width, name, "columns")
     for step in steps:
         assert step.last_propagate["chunks"] == [width] and dict(step.last_propagate["calls"]) == {}

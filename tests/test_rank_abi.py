@@ -48,10 +48,11 @@ def test_rank_header_and_table_agree():
     for entry, (restype, argtypes) in _lib.RANK_SIGNATURES.items():
         assert len(argtypes) == _argument_count(HEADER, entry), entry
     assert len(_lib.RANK_SIGNATURES["pgh_ndcg"][1]) == 6 and len(_lib.RANK_SIGNATURES["pgh_spearman"][1]) == 3
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES, _lib.MEASURE_SIGNATURES, _lib.SUPERVISED_SIGNATURES,
-                  _lib.FAIR_SIGNATURES, _lib.MIXED_SIGNATURES, _lib.LFPR_SIGNATURES, _lib.OVERSAMPLE_SIGNATURES):
-        assert set(_lib.RANK_SIGNATURES).isdisjoint(other)
-    assert _lib.RANK_DECLINED == _defined(HEADER, "PGH_RANK_DECLINED") == 2
+    assert _lib.OPTIONAL[HEADER] is _lib.RANK_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != HEADER:
+            assert set(_lib.RANK_SIGNATURES).isdisjoint(other), header
+    assert _lib.DECLINED == _defined(HEADER, "PGH_RANK_DECLINED") == 2
     assert _lib.RANK_MAX_RELEVANT == _defined(HEADER, "PGH_RANK_MAX_RELEVANT") == 8192
     assert _lib.RANK_LDS_BYTES == _defined(HEADER, "PGH_RANK_LDS_BYTES")
     assert (_lib.RANK_AUTO, _lib.RANK_STREAMING, _lib.RANK_SORTED) == tuple(
@@ -63,7 +64,7 @@ def test_rank_header_and_table_agree():
 def test_hip_library_exports_and_binds_the_rank_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_rank(cdll)
+    bound = _lib.bind_optional(cdll, _lib.RANK_SIGNATURES)
     assert sorted(bound) == _declared(HEADER)
     for name in _declared(HEADER):
         assert hasattr(cdll, name), name
@@ -83,4 +84,4 @@ def test_the_package_exports_the_new_measures():
 def test_host_double_has_no_rank_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.RANK_SIGNATURES:
-        assert _lib.rank_entry(name) is None, name
+        assert _lib.entry(name) is None, name

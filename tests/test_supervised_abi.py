@@ -46,9 +46,11 @@ def test_supervised_header_and_table_agree():
     for entry, (restype, argtypes) in _lib.SUPERVISED_SIGNATURES.items():
         assert len(argtypes) == _argument_count(HEADER, entry), entry
     assert len(_lib.SUPERVISED_SIGNATURES["pgh_pair_forms"][1]) == 9
-    for other in (_lib.SIGNATURES, _lib.BATCH_SIGNATURES, _lib.TUNE_SIGNATURES, _lib.MEASURE_SIGNATURES):
-        assert set(_lib.SUPERVISED_SIGNATURES).isdisjoint(other)
-    assert _lib.PAIR_DECLINED == _defined(HEADER, "PGH_PAIR_DECLINED")
+    assert _lib.OPTIONAL[HEADER] is _lib.SUPERVISED_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != HEADER:
+            assert set(_lib.SUPERVISED_SIGNATURES).isdisjoint(other), header
+    assert _lib.DECLINED == _defined(HEADER, "PGH_PAIR_DECLINED")
     assert _lib.PAIR_SLOTS == _defined(HEADER, "PGH_PAIR_SLOTS") == 20
     assert _lib.PAIR_MOMENTS == _defined(HEADER, "PGH_PAIR_MOMENTS")
     assert _lib.PAIR_LOGS == _defined(HEADER, "PGH_PAIR_LOGS")
@@ -59,7 +61,7 @@ def test_supervised_header_and_table_agree():
 def test_hip_library_exports_and_binds_the_supervised_entry(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_supervised(cdll)
+    bound = _lib.bind_optional(cdll, _lib.SUPERVISED_SIGNATURES)
     assert sorted(bound) == _declared(HEADER)
     for name in _declared(HEADER):
         assert hasattr(cdll, name), name
@@ -69,4 +71,4 @@ def test_hip_library_exports_and_binds_the_supervised_entry(hip_lib):
 def test_host_double_has_no_supervised_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.SUPERVISED_SIGNATURES:
-        assert _lib.supervised_entry(name) is None, name
+        assert _lib.entry(name) is None, name

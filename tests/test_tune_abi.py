@@ -29,11 +29,13 @@ def hip_lib():
 def test_tune_header_and_table_agree():
     from pygrank_amd import _lib
     assert sorted(_lib.TUNE_SIGNATURES) == _declared("pgh_tune.h")
-    assert set(_lib.TUNE_SIGNATURES).isdisjoint(_lib.SIGNATURES)
-    assert set(_lib.TUNE_SIGNATURES).isdisjoint(_lib.BATCH_SIGNATURES)
+    assert _lib.OPTIONAL["pgh_tune.h"] is _lib.TUNE_SIGNATURES
+    for header, other in [("pgh.h", _lib.SIGNATURES), *_lib.OPTIONAL.items()]:
+        if header != "pgh_tune.h":
+            assert set(_lib.TUNE_SIGNATURES).isdisjoint(other), header
     assert sorted(_lib.SIGNATURES) == _declared("pgh.h")
     assert sorted(_lib.BATCH_SIGNATURES) == _declared("pgh_batch.h")
-    assert _lib.TUNE_DECLINED == _defined("pgh_tune.h", "PGH_TUNE_DECLINED")
+    assert _lib.DECLINED == _defined("pgh_tune.h", "PGH_TUNE_DECLINED")
     assert _lib.TUNE_LDS_BYTES == _defined("pgh_tune.h", "PGH_TUNE_LDS_BYTES")
     assert _lib.TUNE_MAX_POSITIVES == _defined("pgh_tune.h", "PGH_TUNE_MAX_POSITIVES")
 
@@ -41,7 +43,7 @@ def test_tune_header_and_table_agree():
 def test_hip_library_exports_and_binds_the_tune_entries(hip_lib):
     from pygrank_amd import _lib
     cdll = _lib.load_library(hip_lib)
-    bound = _lib.bind_tune(cdll)
+    bound = _lib.bind_optional(cdll, _lib.TUNE_SIGNATURES)
     assert sorted(bound) == _declared("pgh_tune.h")
     for name in _declared("pgh_tune.h"):
         assert hasattr(cdll, name), name
@@ -51,4 +53,4 @@ def test_hip_library_exports_and_binds_the_tune_entries(hip_lib):
 def test_host_double_has_no_tune_entry(host_engine):
     from pygrank_amd import _lib
     for name in _lib.TUNE_SIGNATURES:
-        assert _lib.tune_entry(name) is None, name
+        assert _lib.entry(name) is None, name

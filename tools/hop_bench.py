@@ -79,7 +79,7 @@ def main():
     from pygrank_amd.synthetic import rmat_graph
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if L.arnoldi_entry("pgh_basis_dots") is None or L.arnoldi_entry("pgh_arnoldi_close") is None:
+    if L.entry("pgh_basis_dots") is None or L.entry("pgh_arnoldi_close") is None:
         raise SystemExit("the engine library lacks the entries of include/pgh_arnoldi.h")
     warnings.simplefilter("ignore")
     timer = Timer(L)

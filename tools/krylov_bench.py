@@ -48,7 +48,7 @@ def main():
     from pygrank_amd.synthetic import rmat_graph
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if L.krylov_entry("pgh_lanczos_close") is None or L.krylov_entry("pgh_krylov_residuals") is None:
+    if L.entry("pgh_lanczos_close") is None or L.entry("pgh_krylov_residuals") is None:
         raise SystemExit("the engine library lacks the entries of include/pgh_krylov.h")
     warnings.simplefilter("ignore")                          # "Krylov approximation is not stable yet", once per basis
     timer = Timer(L)

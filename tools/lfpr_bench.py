@@ -49,7 +49,7 @@ def main():
     from pygrank_amd.synthetic import rmat_graph
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if L.lfpr_entry("pgh_lfpr_close") is None:
+    if L.entry("pgh_lfpr_close") is None:
         raise SystemExit("the engine library lacks pgh_lfpr_close")
     timer = Timer(L)
 

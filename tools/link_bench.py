@@ -58,7 +58,7 @@ def main():
     from pygrank_amd.device import DeviceMatrix
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if any(L.link_entry(name) is None for name in L.LINK_SIGNATURES):
+    if any(L.entry(name) is None for name in L.LINK_SIGNATURES):
         raise SystemExit("the engine library lacks the entries of include/pgh_link.h")
     warnings.simplefilter("ignore")
     A = rmat_np.rmat_csr(args.scale, 8, seed=3)

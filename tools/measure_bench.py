@@ -71,7 +71,7 @@ def main():
     from pygrank_amd.synthetic import rmat_device_graph
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    stats_fn, forms_fn = L.measure_entry("pgh_mat_col_stats"), L.measure_entry("pgh_cut_forms")
+    stats_fn, forms_fn = L.entry("pgh_mat_col_stats"), L.entry("pgh_cut_forms")
     if stats_fn is None or forms_fn is None:
         raise SystemExit("the engine library lacks the entries of include/pgh_measure.h")
     lib = L.lib()

@@ -46,7 +46,7 @@ def main():
     from pygrank_amd.synthetic import rmat_graph
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if L.oversample_entry("pgh_boost_update") is None:
+    if L.entry("pgh_boost_update") is None:
         raise SystemExit("the engine library lacks pgh_boost_update")
     timer = Timer(L)
 

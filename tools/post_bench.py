@@ -58,7 +58,7 @@ def main():
     from pygrank_amd.synthetic import rmat_graph
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if L.post_entry("pgh_post_kth_largest") is None:
+    if L.entry("pgh_post_kth_largest") is None:
         raise SystemExit("the engine library lacks the entries of include/pgh_post.h")
     timer = Timer(L)
 

@@ -76,7 +76,7 @@ def main():
     from pygrank_amd.device import DeviceMatrix, DeviceVector
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if any(L.rank_entry(name) is None for name in L.RANK_SIGNATURES):
+    if any(L.entry(name) is None for name in L.RANK_SIGNATURES):
         raise SystemExit("the engine library lacks the entries of include/pgh_rank.h")
     n, b = 1 << args.scale, args.columns
     few = b if args.baseline_columns is None else min(b, args.baseline_columns)
@@ -90,7 +90,7 @@ def main():
     host_known[rng.choice(n, min(args.relevant, n), replace=False)] = rng.choice([0.25, 0.5, 1.0], min(args.relevant, n))
     known = DeviceVector.from_host(host_known)
     timer = Timer(L)
-    stats_fn = L.measure_entry("pgh_mat_col_stats")
+    stats_fn = L.entry("pgh_mat_col_stats")
     k = 1000 if args.measure == "ndcg" else None
     measure = pg.NDCG(known, k=k) if args.measure == "ndcg" else pg.SpearmanCorrelation(known)
 
@@ -111,17 +111,14 @@ def main():
     def sorted_route():
         plan = measure._plan_cache[4]
         out = []
-        for first in range(0, b, 64):
-            width = min(64, b - first)
-            part = slab if b <= 64 else slab.get_cols(first, width)
-            dcg, idcg = (C.c_double * width)(), C.c_double()
-            L.check(L.rank_entry("pgh_ndcg")(part._h, plan._h, k, L.RANK_SORTED, dcg, C.byref(idcg)))
+        for _, part in slab.chunks():
+            dcg, idcg = (C.c_double * part.b)(), C.c_double()
+            L.check(L.entry("pgh_ndcg")(part._h, plan._h, k, L.RANK_SORTED, dcg, C.byref(idcg)))
             out.extend(float(v) / idcg.value for v in dcg)
         return out
 
     def col_stats():
-        for first in range(0, b, 64):
-            part = slab if b <= 64 else slab.get_cols(first, min(64, b - first))
+        for _, part in slab.chunks():
             stats = np.empty((part.b, 4))
             L.check(stats_fn(part._h, stats.ctypes.data_as(C.c_void_p)))
         return stats

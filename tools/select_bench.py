@@ -55,7 +55,7 @@ def main():
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
     for name in L.MIXED_SIGNATURES:
-        if L.mixed_entry(name) is None:
+        if L.entry(name) is None:
             raise SystemExit("the engine library lacks " + name)
     adj = rmat_graph(args.scale, args.ef, seed=0, normalization="col", a=0.57, b=0.19, c=0.19)
     n = adj.array.shape[0]

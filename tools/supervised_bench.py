@@ -64,7 +64,7 @@ def main():
     from pygrank_amd.device import DeviceMatrix, DeviceVector
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if L.supervised_entry("pgh_pair_forms") is None:
+    if L.entry("pgh_pair_forms") is None:
         raise SystemExit("the engine library lacks the entry of include/pgh_supervised.h")
     n, b = 1 << args.scale, args.columns
     rng = np.random.default_rng(1)
@@ -73,7 +73,7 @@ def main():
         slab.set_column(j, DeviceVector.from_host(rng.random(n, dtype=np.float32)))
     known = DeviceVector.from_host((rng.random(n) < 0.1).astype(np.float32))
     timer = Timer(L)
-    stats_fn = L.measure_entry("pgh_mat_col_stats")
+    stats_fn = L.entry("pgh_mat_col_stats")
 
     def route(cls, per_column):
         def run():

@@ -65,7 +65,7 @@ def main():
     from pygrank_amd.synthetic import rmat_graph
     pg.load_backend("hip")
     L.ensure_init()                                          # raises without an MI355X
-    if L.tune_entry("pgh_probe_auc") is None:
+    if L.entry("pgh_probe_auc") is None:
         raise SystemExit("the engine library lacks pgh_probe_auc")
     adj = rmat_graph(args.scale, args.ef, seed=0, normalization="col", a=0.57, b=0.19, c=0.19)
     n = adj.array.shape[0]
