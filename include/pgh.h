@@ -265,7 +265,8 @@ typedef struct {
     int32_t converged;      /* 1 = tolerance met; 0 = max_iters reached (caller raises unless ITERS) */
     int32_t spmv_count;     /* SpMV launches that contributed to the result                        */
     int32_t flags;          /* bit 0: the in-kernel residual paused once and the run went on with the separate residual kernel;
-                               bit 1: the run evaluated its residual inside the finish kernel; bit 2: from the first step on */
+                               bit 1: the run evaluated its residual inside the finish kernel; bit 2: from the first step on;
+                               bit 3: step 1 went over the seeds' out-edges; bit 4: step 2's cold tail went over the out-edges */
     double  last_error;     /* residual of the last executed check                                */
     double  loop_ms;        /* HIP-event time of the loop on the engine stream (the way out of the engine's id space that follows
                                is not in it and may still be RUNNING when the call returns: engine calls are ordered on the engine's

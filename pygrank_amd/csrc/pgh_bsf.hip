@@ -1098,6 +1098,63 @@ __global__ __launch_bounds__(WG) void k_bsf_combine(RowSums rs, int64_t n_out,
     }
 }
 
+// k_bsf_combine<EPI_AXPBY, B> behind a pushed cold tail (step 2 of a seed-set run, pgh_push.hip): the cold half of every row sum is the
+// row's 64-bit fixed-point word of the push scratch -- added to the block row sum, and re-armed -- and the launch leaves what a finish
+// launch of the first fused step leaves: sum(y), sum(deg * y), sum(p).  It returns at once unless the run is held (PushTailView::gate).
+// The loads follow the rules above: every one unconditional from a safe address, the use a select.  Like the finish launch it replaces it
+// passes over the isolated tail of every block while the run's operands are zero there (IsoTail): 45 % of the rows at RMAT scale 23.
+template <int B>
+__global__ __launch_bounds__(WG) void k_bsf_combine_tail(RowSums rs, int64_t n_out, const float* __restrict__ dst_scale, EpiParams ep,
+                                                          PushTailView t, double* __restrict__ partial_sum, IsoTail iso) {
+    __shared__ double s_red[4];
+    if (t.gate->done) return;
+    const float a_eff = (float)(ep.a * t.gate->scale);
+    const unsigned int cmax = *t.cmax_bits;
+    // |contribution| <= cmax < 2^e, an item holds fix_bits bits below it (k_push_accum)
+    const double inv_S = __longlong_as_double((long long)(1023 - t.fix_bits + ((int)(cmax >> 23) - 126)) << 52);
+    double sum_y = 0.0, sum_t = 0.0, sum_p = 0.0, delta = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * WG;
+    const char* const zero = reinterpret_cast<const char*>(rs.psum + rs.zero_at);
+    const bool has_ds = dst_scale != nullptr, has_deg = t.deg != nullptr;
+    const char* const ds_base = has_ds ? reinterpret_cast<const char*>(dst_scale) : zero;
+    const char* const deg_base = has_deg ? reinterpret_cast<const char*>(t.deg) : zero;
+    // the row ranges: every block up to its isolated tail, or everything in one piece
+    const bool skip_iso = iso.flag != nullptr && iso.blk > 0 && *iso.flag == 0;
+    const int ranges = skip_iso ? iso.num_blocks : 1;
+    for (int b = 0; b < ranges; ++b) {
+        int first = iso.begin[0];                            // (selects, not an index: IsoTail::holds)
+#pragma unroll
+        for (int k = 1; k < 8; ++k) first = b == k ? iso.begin[k] : first;
+        const int64_t lo = skip_iso ? (int64_t)b * iso.blk : 0;
+        const int64_t hi = skip_iso ? min(lo + (int64_t)first, n_out) : n_out;
+    for (int64_t i = lo + blockIdx.x * (int64_t)WG + threadIdx.x; i < hi; i += stride) {
+        EpiOps ops = epi_load_z<EPI_AXPBY>(ep, (int)i, zero);
+        const float dsc = *reinterpret_cast<const float*>(ds_base + (has_ds ? (uint32_t)i << 2 : 0u));
+        const float dg = *reinterpret_cast<const float*>(deg_base + (has_deg ? (uint32_t)i << 2 : 0u));
+        const long long q = t.acc[i];
+        if (ep.xg_out != nullptr) ops.slot = xg_slot((int)i, ep.xg_blk, ep.xg_live, ep.xg_hot, ep.xg_cold);
+        double s = block_row_sum<B>(rs, i);
+        s += q == kPushNotFinite ? __longlong_as_double(0x7ff8000000000000LL) : (double)q * inv_S;
+        if (q != 0) t.acc[i] = 0;
+        s = has_ds ? s * (double)dsc : s;
+        const float y = epi_apply_z<EPI_AXPBY>(ep, ops, a_eff, (int)i, (float)s, true, sum_y, delta);
+        sum_t += (double)dg * (double)y;
+        sum_p += (double)ops.v;
+    }
+    }
+    const double by = block_reduce_256<0>(sum_y, s_red);
+    __syncthreads();
+    const double bt = block_reduce_256<0>(sum_t, s_red);
+    __syncthreads();
+    const double bp = block_reduce_256<0>(sum_p, s_red);
+    if (threadIdx.x == 0) {
+        partial_sum[blockIdx.x] = by;
+        t.part_t[blockIdx.x] = bt;
+        t.part_d[blockIdx.x] = bp;
+        t.part_r[blockIdx.x] = 0.0;
+    }
+}
+
 BsfView view_of(const BsfFormat& f) {
     BsfView v;
     v.fix_seg = f.fix_seg;
@@ -1228,6 +1285,37 @@ int bsf_launch_combine(pgh_graph_s* g, const EpiParams& ep, const LoopState* sta
             case 2: k_bsf_combine<MODE, 2><<<cgrid, WG, 0, r.stream>>>(rs, f.n_out, f.dst_scale, ep, state, psum, pdel); break;
             case 4: k_bsf_combine<MODE, 4><<<cgrid, WG, 0, r.stream>>>(rs, f.n_out, f.dst_scale, ep, state, psum, pdel); break;
             default: k_bsf_combine<MODE, 8><<<cgrid, WG, 0, r.stream>>>(rs, f.n_out, f.dst_scale, ep, state, psum, pdel); break;
+        }
+    }
+    PGH_HIP(hipGetLastError());
+    if (num_partials) *num_partials = cgrid;
+    return 0;
+}
+
+FixView bsf_fix_view(const BsfFormat& f) {
+    FixView fix;
+    fix.fix_seg = f.fix_seg;
+    fix.tile = f.tile;
+    fix.tail_carry = f.tail_carry;
+    fix.head_partial = f.head_partial;
+    fix.psum = f.psum;
+    fix.num_tiles = f.num_tiles;
+    return fix;
+}
+
+// the epilogue of a step whose cold half was pushed over the out-edges (launched for step 2 of a seed-set run only)
+int bsf_launch_combine_tail(pgh_graph_s* g, const EpiParams& ep, const PushTailView& t, const IsoTail& iso, int* num_partials) {
+    Runtime& r = rt();
+    BsfFormat& f = g->bsf;
+    const RowSums rs = row_sums_of(f);
+    const int cgrid = bsf_combine_grid(f.n_out);
+    {
+        ProfScope prof(PGH_K_COMBINE);
+        switch (f.num_blocks) {
+            case 1: k_bsf_combine_tail<1><<<cgrid, WG, 0, r.stream>>>(rs, f.n_out, f.dst_scale, ep, t, r.d_partials, iso); break;
+            case 2: k_bsf_combine_tail<2><<<cgrid, WG, 0, r.stream>>>(rs, f.n_out, f.dst_scale, ep, t, r.d_partials, iso); break;
+            case 4: k_bsf_combine_tail<4><<<cgrid, WG, 0, r.stream>>>(rs, f.n_out, f.dst_scale, ep, t, r.d_partials, iso); break;
+            default: k_bsf_combine_tail<8><<<cgrid, WG, 0, r.stream>>>(rs, f.n_out, f.dst_scale, ep, t, r.d_partials, iso); break;
         }
     }
     PGH_HIP(hipGetLastError());

@@ -419,7 +419,11 @@ struct PushIndex {
     float*     item_val = nullptr;  // ... and contribution
     int32_t*   seed = nullptr;      // [max_seeds] the run's seeds in ascending caller id
     int32_t*   seed_off = nullptr;  // [max_seeds + 1] prefix of their out-degrees
-    void*      ctl = nullptr;       // device words of a step (PushCtl) followed by the LoopState that gates its residual launch
+    void*      ctl = nullptr;       // device words of a step (PushCtl) followed by the LoopState that gates its residual launch: one such
+                                    // 64-byte block for step 1, one for step 2's cold tail, then the counter of the list below
+    int32_t*   tail_src = nullptr;  // [max_edges] step 2's cold tail: caller ids of the cold sources step 1 made non-zero (any order) ...
+    float*     tail_xg = nullptr;   // ... their values in gather form ...
+    int32_t*   tail_off = nullptr;  // [max_edges + 1] ... and the prefix of their out-degrees
     int        max_seeds = 0, max_edges = 0;
     bool       failed = false;      // the build ran out of memory once: not tried again
     int64_t    device_bytes = 0;

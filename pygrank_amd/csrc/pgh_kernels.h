@@ -51,7 +51,7 @@ struct LoopState {
     int    done;        // convergence flag: once set every later kernel of the loop is a no-op
     int    steps;       // propagation steps executed so far
     int    converged;   // 1 when the tolerance was met
-    int    pad;         // 1: step 1 of the run went over the seeds' out-edges (pgh_push.hip), else 0
+    int    pad;         // bit 0: step 1 of the run went over the seeds' out-edges (pgh_push.hip), bit 1: so did step 2's cold tail
 };
 
 // Residual of a PageRank step INSIDE the finish kernel (k_pb_finish<..., RES>; L1 / Mabs rules).  The residual
@@ -798,8 +798,32 @@ bool push_switched_on();                     // PGH_SEED_PUSH=0 switches the fea
 int push_ensure(pgh_graph_s* g);             // the out-edge index, built on first use (g->push.out_ptr stays null when it cannot be)
 void push_destroy(pgh_graph_s* g);
 int push_partials();                         // partial sums a pushed step leaves in every region it writes
-int push_launch_step(pgh_graph_s* g, const EpiParams& ep, const int32_t* seed_list, const int* seed_count, const float* deg, LoopState* state);
+int push_launch_step(pgh_graph_s* g, const EpiParams& ep, const int32_t* seed_list, const int* seed_count, const float* deg, LoopState* state,
+                     bool list_tail = false);
 const LoopState* push_gate(const pgh_graph_s* g);      // done == 0 only behind a pushed step: the state its residual launch is given
 int push_launch_close(pgh_graph_s* g, const PendingClose& dense, const PendingClose& pushed);
+// step 2's cold tail over the out-edges (pgh_push.hip): the cold sources step 1 made non-zero are pushed, the hot half stays dense
+bool push_tail_switched_on();                // PGH_SEED_PUSH2=0 switches it off
+// behind step 2's block partial sums and in front of its cold-image launches: the plan (it holds a run that qualifies) and the items
+int push_launch_tail(pgh_graph_s* g, LoopState* state);
+// behind step 2's cold-image launches: the epilogue of a held run (pgh_bsf.hip) -- *num_partials sums in regions 0, 2, 3, 4
+int push_launch_tail_combine(pgh_graph_s* g, const EpiParams& ep, const float* deg, const IsoTail& iso, int* num_partials);
+const LoopState* push_tail_gate(const pgh_graph_s* g);      // done == 0 only behind a pushed tail
+bool push_tail_census(const pgh_graph_s* g, int* sources, int* items);      // the last plan's figures (diagnostic: synchronises)
+int push_launch_tail_close(pgh_graph_s* g, const PendingClose& dense, const PendingClose& pushed);
+// what the epilogue of a pushed cold tail reads beside the block partial sums (k_bsf_combine_tail, pgh_bsf.hip)
+struct PushTailView {
+    const LoopState*    gate;       // the launch returns at once unless gate->done == 0; its scale is the step's quotient
+    long long*          acc;        // [n_out] fixed-point cold sums; a row that is read goes back to zero
+    const unsigned int* cmax_bits;  // bit pattern of the largest |contribution|: the scale of the sums (fix_bits bits per item below it)
+    int                 fix_bits;
+    const float*        deg;        // row sums of M, internal ids (sum(deg * y) for the next prediction), or null
+    double*             part_t;
+    double*             part_d;     // sum(p)
+    double*             part_r;     // zeros (the residual comes from the separate kernel)
+};
+constexpr long long kPushNotFinite = (long long)(1ULL << 63);      // a cold sum whose items were not finite
+FixView bsf_fix_view(const BsfFormat& f);
+int bsf_launch_combine_tail(pgh_graph_s* g, const EpiParams& ep, const PushTailView& t, const IsoTail& iso, int* num_partials);
 
 }  // namespace pgh

@@ -2015,6 +2015,11 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
         PGH_TRY(push_ensure(g));
         pushing = g->push.out_ptr != nullptr;
     }
+    // ... and step 2 of such a run may push its COLD half: the cold sources step 1 made non-zero go over their out-edges, the hot half
+    // streams as ever (pgh_push.hip; decided on the device as well).  Only where there is a cold image to pass over -- and one that
+    // holds every cold entry (k1_cold: heavy rows keep theirs in the stream).  PGH_SEED_PUSH2=0: nothing of it is enqueued.
+    const bool push_tail = pushing && max_steps >= 2 && g->bsf.pb.enabled && !g->bsf.pb.k1_cold && g->bsf.pb.num_tasks > 0 &&
+                           g->bsf.pb_slices <= 1 && g->bsf.perm != nullptr && push_tail_switched_on();
     const int32_t* const push_list = g->bsf.seed_list;
     const int* const push_count = pushing ? g->bsf.seed_count + (1 - g->bsf.seed_turn) : nullptr;      // the counter this run's scan filled
     pending_close_slot().active = 0;
@@ -2090,8 +2095,20 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
         }
         const bool push_now = pushing && k == 1;
         // (in front of the dense launches: a run that qualifies is held, and they pass as they do behind a converged step)
-        if (push_now) PGH_TRY(push_launch_step(g, epk, push_list, push_count, fused ? g->bsf.deg_int : nullptr, g_state));
-        const int rc_step = launch_step<MODE>(g, epk, use_xg ? g->bsf.xg : xin, g_state, &count, (overlap && k > 1) ? g_ev_closed : nullptr);
+        if (push_now) PGH_TRY(push_launch_step(g, epk, push_list, push_count, fused ? g->bsf.deg_int : nullptr, g_state, push_tail));
+        const bool tail_now = push_tail && k == 2;
+        int rc_step;
+        if (tail_now) {
+            // the plan of the pushed cold tail sits behind the block partial sums, which must not see its hold, and in front of the
+            // cold-image launches, which pass under it
+            const float* gsrc = use_xg ? g->bsf.xg : xin;
+            rc_step = bsf_launch_partial(g, gsrc, g_state, 1);
+            if (rc_step == 0) rc_step = push_launch_tail(g, g_state);
+            if (rc_step == 0) rc_step = bsf_launch_partial(g, gsrc, g_state, 2);
+            if (rc_step == 0) rc_step = bsf_launch_combine<MODE>(g, epk, g_state, &count);
+        } else {
+            rc_step = launch_step<MODE>(g, epk, use_xg ? g->bsf.xg : xin, g_state, &count, (overlap && k > 1) ? g_ev_closed : nullptr);
+        }
         if (fused) pb_set_residual(nullptr);     // consumed by the finish launch; never left armed behind a step that failed before it
         PGH_TRY(rc_step);
         count_seen = count;
@@ -2127,6 +2144,22 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
             }
             ProfScope prof(PGH_K_FINAL);
             PGH_TRY(push_launch_close(g, pc, pushed));
+        } else if (tail_now) {
+            // epilogue, residual and close of a step 2 whose cold tail was pushed: the epilogue of a graph without a cold image plus the
+            // pushed sums, then the path of a step whose residual is not fused, as behind the pushed step 1 -- all three behind the
+            // tail's gate.  One launch closes either form of the step; the in-kernel residual goes on from step 3.
+            PendingClose pushed = pc;
+            pushed.res_mode = fused ? 2 : 0;
+            int tail_count = 0;
+            PGH_TRY(push_launch_tail_combine(g, epk, fused ? g->bsf.deg_int : nullptr, iso_tail, &tail_count));
+            pushed.num_sum = tail_count;
+            if (pushed.check) {
+                ProfScope prof(PGH_K_RESIDUAL);
+                k_step_residual<<<rgrid, WG, 0, r.stream>>>(yout, xin, n_int, aligned16(yout) && aligned16(xin), cfg->use_quotient, linf,
+                                                            push_tail_gate(g), r.d_partials, tail_count, pres, iso_tail);
+            }
+            ProfScope prof(PGH_K_FINAL);
+            PGH_TRY(push_launch_tail_close(g, pc, pushed));
         } else if (defer) {
             pending_close_slot() = pc;
         } else {
@@ -2208,7 +2241,9 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
     // bit 3: step 1 went over the seeds' out-edges.  Bits 0-2 stay what the run's dense form reports (tests/test_gpu_fullsize.py holds a
     // seed-set run at scale 23 to "fused from the first step on, never paused"): nothing paused, the in-kernel residual is the rule of
     // every dense step -- with bit 3 set, step 1 is not one of them and its residual came from the separate kernel
-    if (pushing && g_state_host->pad == 1) res->flags |= 8;
+    // bit 4: step 2's cold tail went over the out-edges (its residual came from the separate kernel as well)
+    if (pushing && (g_state_host->pad & 1) != 0) res->flags |= 8;
+    if (push_tail && (g_state_host->pad & 2) != 0) res->flags |= 16;
     // result lives in buf[steps & 1]; apply the pending quotient and preserve_norm factor
     const double norm_used = norm_on_device ? g_aux_host->in_norm : host_norm;
     if (norm_wanted) res->in_norm = norm_used;
@@ -2238,6 +2273,11 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
         fprintf(stderr, "[pgh] recursive run: %d steps, err %.6e, in-kernel residual %s%s, worst quotient miss %.3e, sum(p) %.12f\n", steps,
                 g_state_host->err, fuse_env && (res->flags & 1) == 0 && fused ? "on" : "off", (res->flags & 1) ? " (paused once)" : "",
                 h.worst_miss, h.sum_p);
+        if (push_tail) {
+            int sources = 0, items = 0;
+            const bool held = push_tail_census(g, &sources, &items);
+            fprintf(stderr, "[pgh] step 2's cold tail: %d cold sources listed, %d items, %s\n", sources, items, held ? "pushed" : "dense");
+        }
     }
     return 0;
 }
