@@ -1324,12 +1324,8 @@ int bsf_launch_combine_tail(pgh_graph_s* g, const EpiParams& ep, const PushTailV
 }
 
 template <int MODE>
-int bsf_launch(pgh_graph_s* g, const EpiParams& ep, const float* xg, const LoopState* state, int* num_partials,
-               hipEvent_t before_combine) {
+int bsf_launch(pgh_graph_s* g, const EpiParams& ep, const float* xg, const LoopState* state, int* num_partials) {
     PGH_TRY(bsf_launch_partial(g, xg, state, 0));
-    // the epilogue is the first consumer of the previous step's scalars (quotient, done flag): the partial sums above
-    // may run while the previous step's residual / close kernels are still in flight on the side stream
-    if (before_combine != nullptr) PGH_HIP(hipStreamWaitEvent(rt().stream, before_combine, 0));
     return bsf_launch_combine<MODE>(g, ep, state, num_partials);
 }
 
@@ -1500,10 +1496,10 @@ template int bsf_launch_small<EPI_POLY>(pgh_graph_s*, const EpiParams&, const fl
 template int bsf_launch_combine<EPI_AXPBY>(pgh_graph_s*, const EpiParams&, const LoopState*, int*);
 template int bsf_launch_combine<EPI_ABSORB>(pgh_graph_s*, const EpiParams&, const LoopState*, int*);
 template int bsf_launch_combine<EPI_POLY>(pgh_graph_s*, const EpiParams&, const LoopState*, int*);
-template int bsf_launch<EPI_PLAIN>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*, hipEvent_t);
-template int bsf_launch<EPI_AXPBY>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*, hipEvent_t);
-template int bsf_launch<EPI_ABSORB>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*, hipEvent_t);
-template int bsf_launch<EPI_POLY>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*, hipEvent_t);
+template int bsf_launch<EPI_PLAIN>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*);
+template int bsf_launch<EPI_AXPBY>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*);
+template int bsf_launch<EPI_ABSORB>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*);
+template int bsf_launch<EPI_POLY>(pgh_graph_s*, const EpiParams&, const float*, const LoopState*, int*);
 
 // original-space source-side vector -> internal (relabelled, padded) space, optionally times src_scale
 int bsf_to_internal(pgh_graph_s* g, const float* src, float* dst, bool prescale, float hole) {

@@ -35,6 +35,15 @@ int  fail(const std::string& msg);
         if (_rc != 0) return _rc; \
     } while (0)
 
+// ---------------------------------------------------------------- the stopping rule's schedule
+// ConvergenceManager.has_converged (convergence.py:77-94) at iteration `it`: does it compare two iterates there?  Not in counting
+// mode, not at the iteration that hits max_iters (the manager gives up before it compares), and only on multiples of end_modulo.
+// The step that produces iterate k is followed by the check at it = k + 1.  Every loop of the engine asks HERE: the reference's
+// iteration counts rest on all of them answering alike.
+inline bool loop_checks_at(int err_kind, int it, int max_iters, int end_modulo) {
+    return err_kind != PGH_ERR_ITERS && it < max_iters && it % end_modulo == 0;
+}
+
 // ---------------------------------------------------------------- runtime state
 struct Runtime {
     bool        initialised = false;

@@ -910,7 +910,7 @@ extern "C" int pgh_dist_ppr_run(pgh_graph_t g, pgh_comm_t c, pgh_vec_t p_local, 
         cur = nxt;
         ++spmv;
         ++it;
-        const bool check = it < max_iters && kind != PGH_ERR_ITERS && it % cfg->end_modulo == 0;
+        const bool check = loop_checks_at(kind, it, max_iters, cfg->end_modulo);
         // ---- S: the scalars of the step
         PGH_RUN_HIP(hipStreamWaitEvent(c->ss, c->ev_fin2, 0));
         {
@@ -1073,7 +1073,7 @@ extern "C" int pgh_dist_poly_run(pgh_graph_t g, pgh_comm_t c, pgh_vec_t p_local,
     res->flags |= c->lists ? 8 : (c->compact_copy ? 16 : 0);       // how the cold parts of the gather vector travel
     int it = 2, spmv = 0, cur = 0;             // `it` = the iteration has_converged is asked about
     bool converged = false, pending = false, staged = false;
-    if (it < max_iters && kind != PGH_ERR_ITERS && it % cfg->end_modulo == 0 && delta <= cfg->tol) converged = true;
+    if (loop_checks_at(kind, it, max_iters, cfg->end_modulo) && delta <= cfg->tol) converged = true;
     while (!converged && it < max_iters) {
         const int nxt = 1 - cur;
         if (!staged) PGH_RUN(stages());
@@ -1106,7 +1106,7 @@ extern "C" int pgh_dist_poly_run(pgh_graph_t g, pgh_comm_t c, pgh_vec_t p_local,
         cur = nxt;
         ++spmv;
         ++it;
-        const bool check = it < max_iters && kind != PGH_ERR_ITERS && it % cfg->end_modulo == 0;
+        const bool check = loop_checks_at(kind, it, max_iters, cfg->end_modulo);
         PGH_RUN_HIP(hipStreamWaitEvent(c->ss, c->ev_fin2, 0));
         {
             StreamSwap on_scalars(c->ss);

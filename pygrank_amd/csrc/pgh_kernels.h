@@ -759,8 +759,7 @@ template <int MODE>
 int bsf_launch_small(pgh_graph_s* g, const EpiParams& ep, const float* xg, const float* x_prev, const LoopState* state,
                      const PendingClose& pc);
 template <int MODE>
-int bsf_launch(pgh_graph_s* g, const EpiParams& ep, const float* xg, const LoopState* state, int* num_partials,
-               hipEvent_t before_combine = nullptr);
+int bsf_launch(pgh_graph_s* g, const EpiParams& ep, const float* xg, const LoopState* state, int* num_partials);
 int bsf_to_internal(pgh_graph_s* g, const float* src, float* dst, bool prescale, float hole);
 bool bsf_can_bring_pair(const pgh_graph_s* g);
 IsoTail iso_tail_of(const BsfFormat& f);

@@ -1583,7 +1583,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
             k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
         }
     };
-    auto check_of = [&](int k) { const int it = k + 1; return (cfg->err_kind != PGH_ERR_ITERS) && (it < cfg->max_iters) && (it % cfg->end_modulo == 0); };
+    auto check_of = [&](int k) { return loop_checks_at(cfg->err_kind, k + 1, cfg->max_iters, cfg->end_modulo); };
     // the separate residual of step k + its close (first step, max rule, dropout, a paused step)
     auto close_plain = [&](int k, int mode, int resume) -> int {
         const int check = check_of(k) ? 1 : 0;
@@ -2056,7 +2056,7 @@ int poly_batch_impl(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t nu
     k_mm_poly_init<<<cgrid, WG, 0, r.stream>>>(res_slab.as<float>(), row_flags.as<uint8_t>(), n_int, ld, (float)coeff(1), linf,
                                                partial.as<double>());
     k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, 0);
-    const int check2 = (cfg->err_kind != PGH_ERR_ITERS) && (2 < cfg->max_iters) && (2 % cfg->end_modulo == 0);
+    const int check2 = loop_checks_at(cfg->err_kind, 2, cfg->max_iters, cfg->end_modulo);
     k_mm_poly_first<<<1, kLanes, 0, r.stream>>>(state, fold + 4 * kLanes, check2, cfg->err_kind, cfg->tol, (long long)n);
     PGH_HIP(hipGetLastError());
     float* buf[2] = {xg0.as<float>(), xg1.as<float>()};
@@ -2092,7 +2092,7 @@ int poly_batch_impl(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t nu
         }
         const int it = k + 2;
         CloseParams c2 = cp;
-        c2.check = (cfg->err_kind != PGH_ERR_ITERS) && (it < cfg->max_iters) && (it % cfg->end_modulo == 0);
+        c2.check = loop_checks_at(cfg->err_kind, it, cfg->max_iters, cfg->end_modulo);
         if (c2.check) k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, 0);
         k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
         PGH_HIP(hipGetLastError());

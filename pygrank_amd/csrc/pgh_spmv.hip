@@ -1,11 +1,22 @@
-// Merge-path CSR SpMV over CSR(M^T) with fused propagation epilogues -- the hot kernel of the engine.
+// The row-major engine and the whole-loop drivers.
+//
+// What is here:
+//   * the row-major merge-path kernels over CSR(M^T) (k_spmv_merge / k_spmv_fixup) with the propagation epilogues fused in.  They
+//     serve rectangular graphs and graphs uploaded with PGH_FORMAT=csr.  The hot path of a square graph is the blocked image:
+//     pgh_bsf.hip (block partial sums, epilogue, the one-workgroup tail of small graphs) and pgh_pb.hip (the propagation-blocking
+//     image of the cold entries); its f64 twin is pgh_bsf64.hip.
+//   * the single-step and resident-iterate entry points of the C-ABI (pgh_spmv*, pgh_resident_*), on whichever image a graph has;
+//   * the pieces of the row-partitioned step (pgh_dist_*; pgh_dist.hip drives them);
+//   * the whole-loop drivers of the fused single-vector routes, at the end of the file: one run-ahead driver (RunAhead), one close
+//     record (close_record / close_step), the recursive loop (recursive_run), the closed-form loop on its f32 and f64 steppers
+//     (closed_form_run) and the f64-iterate recursive loop (recursive_run_f64).
 //
 // Reference counterpart: conv(signal, M) = signal @ M (pygrank/core/backend/numpy.py:64-65, scipy
 // csc_matvec scatter-add, 87 % of rank() wall time) and the per-iteration vector algebra
 // around it: PageRank._formula (pygrank/algorithms/filters/adhoc.py:34-36), AbsorbingWalks._formula
 // (adhoc.py:166-169), ClosedFormGraphFilter._recursion/_step (abstract_filters.py:215-230,248-256).
 //
-// Design (MI355X / gfx950, HBM-bound, no MFMA):
+// Design of the merge-path kernels (MI355X / gfx950, HBM-bound, no MFMA):
 //   * The (rows + nnz) merge path of CSR(M^T) is cut into equal tiles of 256 * IPT items at upload time
 //     (tile table in HBM), so hub rows of a power-law graph are split across workgroups and runs of
 //     empty rows cost the same as non-zeros: perfect load balance irrespective of the degree skew.
@@ -398,7 +409,7 @@ __global__ __launch_bounds__(WG) void k_step_residual(const float* __restrict__ 
 // variant measured 113 us.)
 // single-workgroup stage that closes a step on the device: folds the partials, updates the loop state and
 // evaluates ConvergenceManager._has_converged (convergence.py:96-101) for the check that follows the step.
-//   check != 0  : this step is followed by a residual comparison (iteration % end_modulo == 0, not "iters")
+//   check != 0  : this step is followed by a residual comparison (loop_checks_at, pgh_common.h)
 //   res_partials: residual partials (recursive filters) or delta partials (polynomial filters)
 __global__ __launch_bounds__(WG) void k_step_close(LoopState* __restrict__ state, const double* __restrict__ partial_sum,
                                                     int num_sum, const double* __restrict__ res_partials, int num_res,
@@ -589,9 +600,8 @@ int launch_merge(pgh_graph_t g, const EpiParams& ep, const float* x, const LoopS
 
 // One propagation step in the graph's internal id space, whichever format the graph carries.
 template <int MODE>
-int launch_step(pgh_graph_t g, const EpiParams& ep, const float* gather_src, const LoopState* state, int* num_partials,
-                hipEvent_t before_combine = nullptr) {
-    if (g->bsf.enabled) return bsf_launch<MODE>(g, ep, gather_src, state, num_partials, before_combine);
+int launch_step(pgh_graph_t g, const EpiParams& ep, const float* gather_src, const LoopState* state, int* num_partials) {
+    if (g->bsf.enabled) return bsf_launch<MODE>(g, ep, gather_src, state, num_partials);
     return launch_merge<MODE>(g, ep, gather_src, state, num_partials);
 }
 
@@ -617,15 +627,22 @@ LoopAux*   g_aux_host = nullptr;     // pinned mirror, fetched with the state
 double g_clock_khz = 100000.0;      // rate of the device's constant clock (hipDeviceAttributeWallClockRate; ensure_state)
 volatile int* g_progress_host = nullptr;
 int* g_progress_dev = nullptr;
-// Side stream of the recursive loops: the residual and close kernels of step k run there, concurrently with the block
-// partial sums of step k + 1 on the engine stream (which do not depend on step k's scalars); the epilogue of step k + 1
-// waits for them (ev_closed), they wait for the epilogue of step k (ev_combined).
-hipStream_t g_side_stream = nullptr;
-hipEvent_t g_ev_combined = nullptr, g_ev_closed = nullptr;
 
 // the deferred close of the last enqueued step (PendingClose): launched as its own kernel when no blocked-format launch
 // follows to carry it
 PendingClose g_pending_close = {};
+
+// switches read once per process
+// PGH_DEFER_CLOSE=0: every close is a launch of its own
+bool defer_close_enabled() {
+    static const bool on = getenv("PGH_DEFER_CLOSE") == nullptr || atoi(getenv("PGH_DEFER_CLOSE")) != 0;
+    return on;
+}
+// PGH_FUSED_RES=0: the residual of every step comes from the separate kernel
+bool fused_res_enabled() {
+    static const bool on = getenv("PGH_FUSED_RES") == nullptr || atoi(getenv("PGH_FUSED_RES")) != 0;
+    return on;
+}
 
 int flush_pending_close() {
     PendingClose& pc = pending_close_slot();
@@ -663,14 +680,6 @@ int ensure_state() {
     g_progress_dev = (int*)dp;
     const char* e = getenv("PGH_POLL");
     if (e != nullptr && atoi(e) == 0) g_progress_dev = nullptr;      // PGH_POLL=0: batch + sync polling (A/B measurements)
-    // measured on MI355X (profiles/r01/overlap_ab.log): 252 GTEPS with the side stream vs 268 without -- the 1024-thread
-    // partial-sum workgroups own every CU and the second queue only perturbs their dispatch -- so it is opt-in
-    const char* o = getenv("PGH_OVERLAP");
-    if (o != nullptr && atoi(o) != 0) {
-        PGH_HIP(hipStreamCreateWithFlags(&g_side_stream, hipStreamNonBlocking));
-        PGH_HIP(hipEventCreateWithFlags(&g_ev_combined, hipEventDisableTiming));
-        PGH_HIP(hipEventCreateWithFlags(&g_ev_closed, hipEventDisableTiming));
-    }
     return 0;
 }
 
@@ -1662,8 +1671,7 @@ namespace pgh {
 PendingClose& pending_close_slot() { return g_pending_close; }
 
 bool dist_can_fuse(const pgh_graph_s* g) {
-    static const bool fuse_env = getenv("PGH_FUSED_RES") == nullptr || atoi(getenv("PGH_FUSED_RES")) != 0;
-    return fuse_env && g != nullptr && g->bsf.enabled && g->bsf.pb.enabled && g->degrees != nullptr;
+    return fused_res_enabled() && g != nullptr && g->bsf.enabled && g->bsf.pb.enabled && g->degrees != nullptr;
 }
 
 int dist_aux_init(LoopAux* aux) {
@@ -1792,6 +1800,90 @@ int window_for(pgh_graph_t g) {
     return 3;
 }
 
+// The host side of a device loop.  With the progress words (poll) it enqueues one step at a time and keeps at most `window` of them
+// ahead of the last step it has seen complete (progress_wait), so the stream never drains and few no-op steps trail the converged one;
+// PGH_POLL=0 enqueues `batch` steps, copies the state back and looks.  Starting one resets the progress words and drops whatever
+// close an earlier run left in the deferred slot.
+// (hipGraphs were measured for this loop, tools/graph_probe.hip + profiles/r02/loop_graph_*.log: dependent tiny kernels cost 2.7 us
+// each in a stream and 1.7 us INSIDE one graph, but between two graph launches the gap is 2.7 us again, hipGraphLaunch takes 8 us of
+// host time and an instantiate 140-300 us.  A graph short enough not to run far past the converged step -- two steps, eight kernels
+// -- gains nothing (2.72 us per kernel), and the loop built on such pairs measured 520 instead of 286 us per run at scale 10 and
+// 469.6 instead of 474.6 GTEPS at scale 23.)
+struct RunAhead {
+    bool poll;
+    int  batch, window;
+    bool done = false;     // the device said so: a close raised the flag (converged, or paused)
+    explicit RunAhead(pgh_graph_t g) : poll(g_progress_dev != nullptr), batch(poll ? 1 : batch_for(g)), window(window_for(g)) {
+        if (poll) progress_reset();
+        pending_close_slot().active = 0;
+    }
+    // enqueues steps *enq + 1 .. last through step(k) until the device ends the loop; *enq counts the steps enqueued.  The close of the
+    // last step of a batch that is looked at, and of step `last`, has no later launch to ride in: it is launched on its own.
+    template <typename Step>
+    int enqueue(int* enq, int last, Step& step) {
+        while (!done && *enq < last) {
+            if (poll) {
+                PGH_TRY(progress_wait(*enq, window, &done));
+                if (done) break;
+            }
+            const int upto = (*enq + batch < last) ? *enq + batch : last;
+            for (; *enq < upto; ++*enq) PGH_TRY(step(*enq + 1));
+            PGH_HIP(hipGetLastError());
+            if (!poll || *enq >= last) PGH_TRY(flush_pending_close());
+            if (!poll) {
+                PGH_TRY(fetch_state());
+                done = g_state_host->done != 0;
+            }
+        }
+        return 0;
+    }
+    // the state of a recursive loop after `enq` enqueued steps, on the host: through the words its last close published, or a copy.
+    // (a loop known to be over: the record still waiting belongs to a step that did nothing -- its launch would return at once)
+    int settle(int enq, unsigned long long run_tag, double* published_ms) {
+        if (done) pending_close_slot().active = 0;
+        else PGH_TRY(flush_pending_close());
+        if (!(poll && published_state(enq, run_tag, published_ms))) PGH_TRY(fetch_state());
+        return 0;
+    }
+};
+
+// The close of a step as a record (PendingClose, pgh_kernels.h), as every loop of this file fills it in.  it: the iteration of the
+// check that follows the step (step k of a recursive loop: k + 1); num_sum / num_res: the step's partials of sum(y) and of the
+// residual (recursive loops) or delta (closed-form loops), in the first two regions of the runtime's partials.
+PendingClose close_record(const pgh_loop_cfg* cfg, int64_t n, int it, int use_quotient, int num_sum, int num_res) {
+    PendingClose pc{};
+    pc.state = g_state;
+    pc.partial_sum = rt().d_partials;
+    pc.res_partials = rt().d_partials + kMaxPartials;
+    pc.progress = g_progress_dev;
+    pc.tol = cfg->tol;
+    pc.n = (long long)n;
+    pc.num_sum = num_sum;
+    pc.num_res = num_res;
+    pc.use_quotient = use_quotient;
+    pc.check = loop_checks_at(cfg->err_kind, it, cfg->max_iters, cfg->end_modulo);
+    pc.err_kind = cfg->err_kind;
+    pc.active = 1;
+    return pc;
+}
+
+// closes a step: the record goes into the slot the next blocked-format launch looks into (defer), or is launched now -- as a record
+// (k_step_close_rec: any res_mode) or, for the closed-form loops, through the plain k_step_close
+int close_step(const PendingClose& pc, bool defer, bool as_record = true) {
+    if (defer) {
+        pending_close_slot() = pc;
+        return 0;
+    }
+    ProfScope prof(PGH_K_FINAL);
+    if (as_record) {
+        k_step_close_rec<<<1, WG, 0, rt().stream>>>(pc);
+    } else {
+        k_step_close<<<1, WG, 0, rt().stream>>>(pc.state, pc.partial_sum, pc.num_sum, pc.res_partials, pc.num_res, pc.use_quotient, pc.check,
+                                                pc.err_kind, pc.tol, pc.n, nullptr, pc.progress);
+    }
+    return 0;
+}
+
 struct LoopTimer {
     hipEvent_t a = nullptr, b = nullptr;
     ~LoopTimer() {
@@ -1834,6 +1926,94 @@ struct InternalSpace {
         return 0;
     }
 };
+
+// a vector handle over memory somebody else owns
+inline pgh_vec_s vec_view(const float* data, int64_t n) {
+    pgh_vec_s v;
+    v.data = const_cast<float*>(data);
+    v.n = n;
+    v.owns = false;
+    return v;
+}
+
+// whatever way a run that watched the isolated rows ends, the flag goes back to "process every row"
+struct IsoGuard {
+    pgh_graph_t g_;
+    bool on;
+    ~IsoGuard() {
+        if (on) (void)iso_flag_release(g_);
+    }
+};
+
+// GraphFilter.rank's prologue (abstract_filters.py:52-56) on layouts without the fused permutation, as launches of its own:
+// p / in_norm (into pn_buf; ep.v then points there) and, from_p, the start vector = that
+int materialise_prologue(EpiParams& ep, pgh_vec_t ranks, int64_t n, float in_norm, bool from_p, DevF32& pn_buf) {
+    pgh_vec_s pv = vec_view(ep.v, n);
+    if (in_norm != 1.f) {
+        PGH_TRY(pn_buf.alloc(n));
+        pgh_vec_s tv = vec_view(pn_buf.p, n);
+        PGH_TRY(pgh_ewise_vs(PGH_DIV, &pv, (double)in_norm, 0, &tv));
+        ep.v = pn_buf.p;
+        pv.data = pn_buf.p;
+    }
+    if (from_p) PGH_TRY(pgh_vec_copy(ranks, &pv));
+    return 0;
+}
+
+// the residual of a recursive step as a launch of its own: partials of |y / sum(y) - x * scale| into the second region of the
+// runtime's partials.  gate: the state whose `done` lets the launch pass (the loop's, or a pushed step's); num_sum: the step's
+// partials of sum(y)
+void launch_residual(const float* yout, const float* xin, int64_t n_int, const pgh_loop_cfg* cfg, const LoopState* gate, int num_sum,
+                     const IsoTail& iso_tail) {
+    Runtime& r = rt();
+    ProfScope prof(PGH_K_RESIDUAL);
+    k_step_residual<<<residual_grid(n_int), WG, 0, r.stream>>>(yout, xin, n_int, aligned16(yout) && aligned16(xin), cfg->use_quotient,
+                                                               cfg->err_kind == PGH_ERR_LINF, gate, r.d_partials, num_sum,
+                                                               r.d_partials + kMaxPartials, iso_tail);
+}
+
+// A close of the in-kernel residual PAUSED the loop (the quotient's prediction missed by more than kPredGuard): the step it was closing
+// is complete but for its residual.  That comes from the separate kernel here, and the step is closed the plain way (pc: its record
+// with res_mode 0); the host then knows the state, and the loop goes on without the fusion.
+int reevaluate_paused_step(const float* yout, const float* xin, int64_t n_int, const pgh_loop_cfg* cfg, const PendingClose& pc,
+                           const IsoTail& iso_tail, RunAhead& ahead) {
+    k_state_resume<<<1, 1, 0, rt().stream>>>(g_state, g_progress_dev);
+    if (ahead.poll) progress_reset();
+    launch_residual(yout, xin, n_int, cfg, g_state, pc.num_sum, iso_tail);
+    PGH_TRY(close_step(pc, false));
+    PGH_HIP(hipGetLastError());
+    PGH_TRY(fetch_state());
+    if (ahead.poll) g_progress_host[0] = g_state_host->steps;
+    ahead.done = g_state_host->done != 0;
+    return 0;
+}
+
+// The way out of a recursive run whose state is on the host: the result (final_buf, internal id space) times the pending quotient and
+// the preserve_norm factor goes to the caller's vector, and the run reports its figures.
+// The clock stops here, and the way out of the id space is left RUNNING when this call returns (every engine call is ordered behind it
+// on the engine's stream; transfers to the host synchronise) -- the caller's host work between two runs, 25-35 us of Python per
+// rank(), overlaps with it instead of following it.  published_ms >= 0: the state came through the mapped words, and so does the time
+// -- device ticks between the run's first kernel and its last close -- and nothing waits for the no-op launches the run-ahead left in
+// the queue.
+int leave_recursive_run(pgh_graph_t g, const pgh_loop_cfg* cfg, pgh_vec_t ranks, const float* final_buf, double norm_used,
+                        double published_ms, LoopTimer& timer, pgh_loop_result* res) {
+    const int64_t n = g->n_cols;
+    const int steps = g_state_host->steps;
+    const double factor = g_state_host->scale * (cfg->out_scale < 0.0 ? norm_used : cfg->out_scale);
+    if (published_ms >= 0.0) res->loop_ms = published_ms;
+    else PGH_TRY(timer.stop(&res->loop_ms));
+    if (g->bsf.enabled) {
+        PGH_TRY(bsf_to_original(g, final_buf, ranks->data, factor));
+    } else if (n > 0 && (final_buf != ranks->data || factor != 1.0)) {
+        k_scale_copy<<<residual_grid(n), WG, 0, rt().stream>>>(final_buf, ranks->data, n, factor);
+    }
+    PGH_HIP(hipGetLastError());
+    res->iterations = steps + 1;                 // ConvergenceManager.iteration at loop exit
+    res->converged = g_state_host->converged;
+    res->spmv_count = steps;
+    res->last_error = g_state_host->err;
+    return 0;
+}
 
 // Recursive filters (PageRank / AbsorbingWalks): RecursiveGraphFilter._step + ConvergenceManager.
 template <int MODE>
@@ -1879,7 +2059,7 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
     const bool norm_on_device = norm_wanted && pair && bsf_can_norm_on_device(g);
     double host_norm = cfg->in_norm;
     if (norm_wanted && !norm_on_device) {
-        pgh_vec_s pv{const_cast<float*>(ep.v), n, false};
+        pgh_vec_s pv = vec_view(ep.v, n);
         PGH_TRY(pgh_reduce(PGH_ABSSUM, &pv, &host_norm));
         res->in_norm = host_norm;
         if (host_norm == 0.0) {
@@ -1889,22 +2069,7 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
     }
     const float in_norm = norm_on_device ? -1.f : ((host_norm != 0.0) ? (float)host_norm : 1.f);
     const bool from_p = cfg->start_from_p != 0;
-    if (!pair && (in_norm != 1.f || from_p)) {       // layouts without the fused permutation: materialise the prologue
-        pgh_vec_s pv, tv;
-        pv.data = const_cast<float*>(ep.v);
-        pv.n = n;
-        pv.owns = false;
-        if (in_norm != 1.f) {
-            PGH_TRY(pn_buf.alloc(n));
-            tv.data = pn_buf.p;
-            tv.n = n;
-            tv.owns = false;
-            PGH_TRY(pgh_ewise_vs(PGH_DIV, &pv, (double)in_norm, 0, &tv));
-            ep.v = pn_buf.p;
-            pv.data = pn_buf.p;
-        }
-        if (from_p) PGH_TRY(pgh_vec_copy(ranks, &pv));
-    }
+    if (!pair && (in_norm != 1.f || from_p)) PGH_TRY(materialise_prologue(ep, ranks, n, in_norm, from_p, pn_buf));
     float* buf[2] = {ranks->data, nullptr};
     // isolated rows (no entry, referenced by nobody; BsfFormat::iso_begin) stay zero when both operands are zero there: the
     // permute pass below watches for that, and the finish / residual kernels then pass over them.  Whatever happens, the
@@ -1913,13 +2078,7 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
     // k_iso_watch looks for below)
     const bool watch_iso = (MODE == EPI_AXPBY || MODE == EPI_ABSORB) && pair && g->bsf.iso_flag != nullptr && g->bsf.pb.enabled &&
                            pre_scale == nullptr;
-    struct IsoGuard {
-        pgh_graph_t g_;
-        bool on;
-        ~IsoGuard() {
-            if (on) (void)iso_flag_release(g_);
-        }
-    } iso_guard{g, watch_iso};
+    IsoGuard iso_guard{g, watch_iso};
     // the iterate a run starts from.  Started from the personalization itself (GraphFilter.rank without warm_start), x0 IS the
     // internal-space personalization: step 1 reads that vector and the even steps' output buffer is never initialised (33 MB fewer
     // written per run at scale 23; the rows a run passes over are read by nobody, see IsoTail)
@@ -1928,9 +2087,7 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
     // PageRank with the L1 / Mabs rule on a graph with a cold image: the residual is evaluated inside the finish kernel
     // against the predicted quotient (ResParams, pgh_kernels.h).  PGH_FUSED_RES=0 keeps the separate kernel.
     // (a dropped matrix has other column sums every step: the quotient cannot be predicted from the degrees)
-    static const bool fuse_env = getenv("PGH_FUSED_RES") == nullptr || atoi(getenv("PGH_FUSED_RES")) != 0;
-    const bool overlap = g_side_stream != nullptr && sp.blocked;     // the row-major kernel applies its epilogue in place
-    bool fused = fuse_env && MODE == EPI_AXPBY && sp.blocked && g->bsf.pb.enabled && !overlap && pre_scale == nullptr && !dropping &&
+    bool fused = fused_res_enabled() && MODE == EPI_AXPBY && sp.blocked && g->bsf.pb.enabled && pre_scale == nullptr && !dropping &&
                  (cfg->err_kind == PGH_ERR_L1 || cfg->err_kind == PGH_ERR_MABS) && ep.v != nullptr;
     if (fused) PGH_TRY(bsf_ensure_degrees(g));
     // ... from the FIRST step on when the pass that brings the operands into the id space can sum what its prediction needs
@@ -1987,28 +2144,21 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
         ep.xg_live = g->bsf.xg_live;
         use_xg = true;
     }
-    const int linf = (cfg->err_kind == PGH_ERR_LINF);
-    const int rgrid = residual_grid(n_int);
-    double* pres = r.d_partials + kMaxPartials;      // residual partials share the delta region
+    const int rgrid = residual_grid(n_int);          // residual partials (they share the delta region)
     // ConvergenceManager.has_converged is evaluated before every step with iteration = step index
     // (convergence.py:85): step k runs iff k < max_iters and the check at iteration k did not fire.
     const int max_steps = cfg->max_iters - 1 > 0 ? cfg->max_iters - 1 : 0;
-    const bool poll = g_progress_dev != nullptr;
-    const int batch = poll ? 1 : batch_for(g);
-    const int window = window_for(g);
-    if (poll) progress_reset();
     // blocked layout: the close of step k rides in the first kernel of step k + 1 (PendingClose); PGH_DEFER_CLOSE=0 keeps
     // the separate launch
-    static const bool defer_env = getenv("PGH_DEFER_CLOSE") == nullptr || atoi(getenv("PGH_DEFER_CLOSE")) != 0;
-    const bool defer = defer_env && sp.blocked && !overlap;
+    const bool defer = defer_close_enabled() && sp.blocked;
     // small graphs (a few thousand rows, no cold image): fix-ups, epilogue, residual and close are ONE launch of one workgroup
     // (k_small_tail, pgh_bsf.hip) -- two launches per iteration instead of four.  PGH_SMALL_TAIL=0 keeps the general sequence.
-    const bool small_tail = (MODE == EPI_AXPBY || MODE == EPI_ABSORB) && sp.blocked && !overlap && bsf_small_tail_usable(g);
+    const bool small_tail = (MODE == EPI_AXPBY || MODE == EPI_ABSORB) && sp.blocked && bsf_small_tail_usable(g);
     if (!state_inited) k_state_init<<<1, 1, 0, r.stream>>>(g_state, 1.0, g_aux);
     // A PageRank run that starts from its personalization, with the seeds listed by the way in: step 1 may go over the seeds' out-edges
     // instead of the whole image (pgh_push.hip).  Whether it does is decided on the device, from that list -- the host enqueues the
     // pushed step AND the dense one, and one of the two returns at once.  PGH_SEED_PUSH=0: nothing of this is built or enqueued.
-    bool pushing = MODE == EPI_AXPBY && sp.blocked && pair && x0 != nullptr && state_inited && !dropping && pre_scale == nullptr && !overlap &&
+    bool pushing = MODE == EPI_AXPBY && sp.blocked && pair && x0 != nullptr && state_inited && !dropping && pre_scale == nullptr &&
                    !small_tail && g->part_perm == nullptr && g->row_begin == 0 && g->bsf.seed_list != nullptr && max_steps >= 1 &&
                    push_switched_on();
     if (pushing) {
@@ -2022,28 +2172,15 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
                            g->bsf.pb_slices <= 1 && g->bsf.perm != nullptr && push_tail_switched_on();
     const int32_t* const push_list = g->bsf.seed_list;
     const int* const push_count = pushing ? g->bsf.seed_count + (1 - g->bsf.seed_turn) : nullptr;      // the counter this run's scan filled
-    pending_close_slot().active = 0;
+    RunAhead ahead(g);
     int count_seen = 0;   // partials per step (the same for every step of a run)
     static unsigned long long run_counter = 0ULL;
     const unsigned long long run_tag = ++run_counter;        // in the checksum of the state the closes publish (published_state)
     double published_ms = -1.0;                              // the loop's time on the device's clock, when the state came that way
     // the close of step k as a record: executed by the next blocked-format launch (deferred) or by k_step_close_rec
     auto make_close = [&](int k) {
-        const int it = k + 1;
-        PendingClose pc{};
-        pc.state = g_state;
-        pc.partial_sum = r.d_partials;
-        pc.res_partials = pres;
-        pc.progress = g_progress_dev;
-        pc.tol = cfg->tol;
-        pc.n = (long long)n;
-        pc.num_sum = count_seen;
-        pc.num_res = rgrid;
-        pc.use_quotient = cfg->use_quotient;
         // the check that follows step k happens at iteration k + 1 (skipped when that iteration hits max_iters)
-        pc.check = (cfg->err_kind != PGH_ERR_ITERS) && (it < cfg->max_iters) && (it % cfg->end_modulo == 0);
-        pc.err_kind = cfg->err_kind;
-        pc.active = 1;
+        PendingClose pc = close_record(cfg, n, k + 1, cfg->use_quotient, count_seen, rgrid);
         pc.res_mode = fused ? ((k == 1 && !first_pred) ? 2 : 1) : 0;
         pc.step = k;
         pc.aux = g_aux;
@@ -2107,29 +2244,13 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
             if (rc_step == 0) rc_step = bsf_launch_partial(g, gsrc, g_state, 2);
             if (rc_step == 0) rc_step = bsf_launch_combine<MODE>(g, epk, g_state, &count);
         } else {
-            rc_step = launch_step<MODE>(g, epk, use_xg ? g->bsf.xg : xin, g_state, &count, (overlap && k > 1) ? g_ev_closed : nullptr);
+            rc_step = launch_step<MODE>(g, epk, use_xg ? g->bsf.xg : xin, g_state, &count);
         }
         if (fused) pb_set_residual(nullptr);     // consumed by the finish launch; never left armed behind a step that failed before it
         PGH_TRY(rc_step);
         count_seen = count;
         const PendingClose pc = make_close(k);
-        hipStream_t main_stream = r.stream;
-        struct StreamGuard {                     // whatever happens below, the engine's stream is put back
-            Runtime& rt_;
-            hipStream_t saved;
-            ~StreamGuard() { rt_.stream = saved; }
-        } guard{r, main_stream};
-        if (overlap) {
-            PGH_HIP(hipEventRecord(g_ev_combined, main_stream));
-            PGH_HIP(hipStreamWaitEvent(g_side_stream, g_ev_combined, 0));
-            r.stream = g_side_stream;            // ProfScope and the launches below follow rt().stream
-        }
-        if (pc.check && pc.res_mode != 1) {
-            ProfScope prof(PGH_K_RESIDUAL);
-            const int vec_ok = aligned16(yout) && aligned16(xin);
-            k_step_residual<<<rgrid, WG, 0, r.stream>>>(yout, xin, n_int, vec_ok, cfg->use_quotient, linf, g_state,
-                                                        r.d_partials, count, pres, iso_tail);
-        }
+        if (pc.check && pc.res_mode != 1) launch_residual(yout, xin, n_int, cfg, g_state, count, iso_tail);
         if (push_now) {
             // residual and close of a pushed step 1: the path of a step whose residual is not fused -- the separate kernel (it runs only
             // behind a pushed step: its state is the gate), then the close that also makes step 2's prediction (res_mode 2).  One
@@ -2137,11 +2258,7 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
             PendingClose pushed = pc;
             pushed.res_mode = fused ? 2 : 0;
             pushed.num_sum = push_partials();
-            if (pushed.check) {
-                ProfScope prof(PGH_K_RESIDUAL);
-                k_step_residual<<<rgrid, WG, 0, r.stream>>>(yout, xin, n_int, aligned16(yout) && aligned16(xin), cfg->use_quotient, linf,
-                                                            push_gate(g), r.d_partials, push_partials(), pres, iso_tail);
-            }
+            if (pushed.check) launch_residual(yout, xin, n_int, cfg, push_gate(g), push_partials(), iso_tail);
             ProfScope prof(PGH_K_FINAL);
             PGH_TRY(push_launch_close(g, pc, pushed));
         } else if (tail_now) {
@@ -2153,90 +2270,32 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
             int tail_count = 0;
             PGH_TRY(push_launch_tail_combine(g, epk, fused ? g->bsf.deg_int : nullptr, iso_tail, &tail_count));
             pushed.num_sum = tail_count;
-            if (pushed.check) {
-                ProfScope prof(PGH_K_RESIDUAL);
-                k_step_residual<<<rgrid, WG, 0, r.stream>>>(yout, xin, n_int, aligned16(yout) && aligned16(xin), cfg->use_quotient, linf,
-                                                            push_tail_gate(g), r.d_partials, tail_count, pres, iso_tail);
-            }
+            if (pushed.check) launch_residual(yout, xin, n_int, cfg, push_tail_gate(g), tail_count, iso_tail);
             ProfScope prof(PGH_K_FINAL);
             PGH_TRY(push_launch_tail_close(g, pc, pushed));
-        } else if (defer) {
-            pending_close_slot() = pc;
         } else {
-            ProfScope prof(PGH_K_FINAL);
-            k_step_close_rec<<<1, WG, 0, r.stream>>>(pc);
-        }
-        if (overlap) {
-            r.stream = main_stream;
-            PGH_HIP(hipEventRecord(g_ev_closed, g_side_stream));
+            PGH_TRY(close_step(pc, defer));
         }
         return 0;
     };
     int enq = 0;          // steps enqueued so far
-    bool done = false, state_fetched = false;
+    bool state_fetched = false;
     res->flags |= (fused ? 2 : 0) | (first_pred ? 4 : 0);
     for (;;) {
-        while (!done && enq < max_steps) {
-            if (poll) {
-                PGH_TRY(progress_wait(enq, window, &done));
-                if (done) break;
-            }
-            // (hipGraphs were measured for this loop, tools/graph_probe.hip + profiles/r02/loop_graph_*.log: dependent tiny kernels
-            // cost 2.7 us each in a stream and 1.7 us INSIDE one graph, but between two graph launches the gap is 2.7 us again,
-            // hipGraphLaunch takes 8 us of host time and an instantiate 140-300 us.  A graph short enough not to run far past the
-            // converged step -- two steps, eight kernels -- gains nothing (2.72 us per kernel), and the loop built on such pairs
-            // measured 520 instead of 286 us per run at scale 10 and 469.6 instead of 474.6 GTEPS at scale 23.)
-            const int upto = (enq + batch < max_steps) ? enq + batch : max_steps;
-            for (; enq < upto; ++enq) PGH_TRY(enqueue_step(enq + 1));
-            PGH_HIP(hipGetLastError());
-            if (!poll || enq >= max_steps) PGH_TRY(flush_pending_close());
-            if (!poll) {
-                if (overlap && enq > 0) PGH_HIP(hipStreamWaitEvent(r.stream, g_ev_closed, 0));
-                PGH_TRY(fetch_state());
-                done = g_state_host->done != 0;
-            }
-        }
+        PGH_TRY(ahead.enqueue(&enq, max_steps, enqueue_step));
         if (!fused) break;
-        // a close of the fused residual may have PAUSED the loop (the quotient's prediction missed by more than kPredGuard):
-        // the step it was closing is complete but for its residual -- evaluate that with the separate kernel, close the step
-        // the plain way and go on without the fusion
-        if (overlap && enq > 0) PGH_HIP(hipStreamWaitEvent(r.stream, g_ev_closed, 0));
-        // (the loop is known to be over: the record still waiting belongs to a step that did nothing -- its launch would return at once)
-        if (done) pending_close_slot().active = 0;
-        else PGH_TRY(flush_pending_close());
-        if (!(poll && published_state(enq, run_tag, &published_ms))) PGH_TRY(fetch_state());
+        // a close of the in-kernel residual may have PAUSED the loop: only the state tells
+        PGH_TRY(ahead.settle(enq, run_tag, &published_ms));
         state_fetched = true;                        // nothing is enqueued between here and the end of the run
         if (g_state_host->done != 2) break;
         state_fetched = false;
         const int k = g_state_host->steps + 1;       // the paused step
-        fused = false;
-        k_state_resume<<<1, 1, 0, r.stream>>>(g_state, g_progress_dev);
-        if (poll) progress_reset();
-        {
-            const float* xin = input_of(k);
-            const float* yout = buf[k & 1];
-            PendingClose pc = make_close(k);
-            {
-                ProfScope prof(PGH_K_RESIDUAL);
-                k_step_residual<<<rgrid, WG, 0, r.stream>>>(yout, xin, n_int, aligned16(yout) && aligned16(xin), cfg->use_quotient, linf,
-                                                            g_state, r.d_partials, count_seen, pres, iso_tail);
-            }
-            ProfScope prof(PGH_K_FINAL);
-            k_step_close_rec<<<1, WG, 0, r.stream>>>(pc);
-            PGH_HIP(hipGetLastError());
-        }
-        PGH_TRY(fetch_state());
-        if (poll) g_progress_host[0] = g_state_host->steps;
+        fused = false;                               // (its record, and every later one, with res_mode 0)
+        PGH_TRY(reevaluate_paused_step(buf[k & 1], input_of(k), n_int, cfg, make_close(k), iso_tail, ahead));
         enq = k;
-        done = g_state_host->done != 0;
         res->flags |= 1;
     }
-    if (!state_fetched) {
-        if (overlap && enq > 0) PGH_HIP(hipStreamWaitEvent(r.stream, g_ev_closed, 0));
-        if (done) pending_close_slot().active = 0;   // (as above)
-        else PGH_TRY(flush_pending_close());
-        if (!(poll && published_state(enq, run_tag, &published_ms))) PGH_TRY(fetch_state());
-    }
+    if (!state_fetched) PGH_TRY(ahead.settle(enq, run_tag, &published_ms));
     const int steps = g_state_host->steps;
     // bit 3: step 1 went over the seeds' out-edges.  Bits 0-2 stay what the run's dense form reports (tests/test_gpu_fullsize.py holds a
     // seed-set run at scale 23 to "fused from the first step on, never paused"): nothing paused, the in-kernel residual is the rule of
@@ -2244,34 +2303,17 @@ int recursive_run(pgh_graph_t g, EpiParams ep, pgh_vec_t ranks, const pgh_loop_c
     // bit 4: step 2's cold tail went over the out-edges (its residual came from the separate kernel as well)
     if (pushing && (g_state_host->pad & 1) != 0) res->flags |= 8;
     if (push_tail && (g_state_host->pad & 2) != 0) res->flags |= 16;
-    // result lives in buf[steps & 1]; apply the pending quotient and preserve_norm factor
+    // the result lives in buf[steps & 1]
     const double norm_used = norm_on_device ? g_aux_host->in_norm : host_norm;
     if (norm_wanted) res->in_norm = norm_used;
-    const double factor = g_state_host->scale * (cfg->out_scale < 0.0 ? norm_used : cfg->out_scale);
     const float* final_buf = (steps == 0 && x0 != nullptr) ? x0 : buf[steps & 1];
-    // the loop is over and its state is on the host: the clock stops here, and the way out of the id space is left RUNNING when this
-    // call returns (every engine call is ordered behind it on the engine's stream; transfers to the host synchronise) -- the caller's
-    // host work between two runs, 25-35 us of Python per rank(), overlaps with it instead of following it
-    // (the state came through the mapped words: so does the time -- device ticks between the run's first kernel and its last close --
-    // and nothing waits for the no-op launches the run-ahead left in the queue)
-    if (published_ms >= 0.0) res->loop_ms = published_ms;
-    else PGH_TRY(timer.stop(&res->loop_ms));
-    if (sp.blocked) {
-        PGH_TRY(bsf_to_original(g, final_buf, ranks->data, factor));
-    } else if (n > 0 && (final_buf != ranks->data || factor != 1.0)) {
-        k_scale_copy<<<residual_grid(n), WG, 0, r.stream>>>(final_buf, ranks->data, n, factor);
-    }
-    PGH_HIP(hipGetLastError());
-    res->iterations = steps + 1;                 // ConvergenceManager.iteration at loop exit
-    res->converged = g_state_host->converged;
-    res->spmv_count = steps;
-    res->last_error = g_state_host->err;
+    PGH_TRY(leave_recursive_run(g, cfg, ranks, final_buf, norm_used, published_ms, timer, res));
     static const bool debug_res = getenv("PGH_DEBUG_RES") != nullptr;
     if (debug_res) {
         LoopAux h{};
         PGH_HIP(hipMemcpy(&h, g_aux, sizeof(h), hipMemcpyDeviceToHost));
         fprintf(stderr, "[pgh] recursive run: %d steps, err %.6e, in-kernel residual %s%s, worst quotient miss %.3e, sum(p) %.12f\n", steps,
-                g_state_host->err, fuse_env && (res->flags & 1) == 0 && fused ? "on" : "off", (res->flags & 1) ? " (paused once)" : "",
+                g_state_host->err, (res->flags & 1) == 0 && fused ? "on" : "off", (res->flags & 1) ? " (paused once)" : "",
                 h.worst_miss, h.sum_p);
         if (push_tail) {
             int sources = 0, items = 0;
@@ -2358,154 +2400,239 @@ struct DevF64 {
     int alloc(int64_t n) { return pool_alloc(sizeof(double) * (size_t)(n > 0 ? n : 1), (void**)&p); }
 };
 
-// The reference's "chebyshev" recurrence in f64 over the row-major CSR(M^T) (see EpiPoly64 for why).  Same loop structure,
-// stopping rule and iteration accounting as the f32 route of pgh_poly_run below.
-int poly_run_f64(pgh_graph_t g, pgh_vec_t p, const double* coeffs, int32_t num_coeffs, pgh_vec_t result, const pgh_loop_cfg* cfg,
-                 pgh_loop_result* res, bool cheb_recurrence) {
-    Runtime& r = rt();
-    const int64_t n = g->n_cols;
+// Closed-form filters: result_k = result_{k-1} + c_k * term_k, term_{k+1} = a * M^T term_k + b * term_k.
+// The reference accumulates first and multiplies afterwards (abstract_filters.py:254-256), which costs one
+// trailing, unused SpMV per run; here step k computes term_{k+1} AND folds it into the result, so the
+// run needs (iterations - 2) SpMVs for the identical result.
+// One loop (closed_form_run) on two steppers.  A stepper supplies what differs between the f32 and the f64 evaluation:
+//   bring(c1, &delta_1)         the operands into its id space, result_1 = c_1 * p, and delta_1 = |result_1 - 0| under the run's rule
+//   launch(k, c_k, pc, &count)  the launches of iteration k's step; count: its partials of sum(y) and of delta
+//   closes_in_step()            the launch closed the step itself, with the record pc (the one-workgroup tail of small graphs)
+//   defers()                    the close of a step rides in the first kernel of the next one
+//   take()                      the result out of the id space, times cfg->out_scale
+
+// delta_1 of a closed-form run: the rule's norm of v = result_1 (len entries; n: the caller-space length Mabs divides by)
+int first_delta(const float* v, int64_t len, int64_t n, const pgh_loop_cfg* cfg, double* delta) {
+    pgh_vec_s rv = vec_view(v, len);
+    const int kind = cfg->err_kind == PGH_ERR_ITERS ? PGH_ERR_L1 : cfg->err_kind;
+    PGH_TRY(pgh_scaled_residual(kind == PGH_ERR_MABS ? PGH_ERR_L1 : kind, &rv, 1.0, &rv, 0.0, delta));
+    if (kind == PGH_ERR_MABS && n > 0) *delta /= (double)n;
+    return 0;
+}
+
+// f32 terms and accumulator on whichever image the graph has (taylor; "chebyshev" only under PGH_CHEB_F32=1)
+struct PolyStepF32 {
+    pgh_graph_t         g;
+    pgh_vec_t           p, result;
+    const pgh_loop_cfg* cfg;
+    bool                chebyshev;
+    InternalSpace       sp;
+    DevF32              p_buf, res_buf, t0, t1;
+    float*              result_int = nullptr;
+    float*              tbuf[2] = {nullptr, nullptr};
+    const float*        term = nullptr;        // term_k, the input of iteration k's step
+    bool                scaled_gather = false, small_tail = false;
+    IsoGuard            iso_guard;
+    PolyStepF32(pgh_graph_t graph, pgh_vec_t p_, pgh_vec_t result_, const pgh_loop_cfg* cfg_, bool chebyshev_)
+        : g(graph), p(p_), result(result_), cfg(cfg_), chebyshev(chebyshev_), sp(graph), iso_guard{graph, false} {}
+
+    int bring(double c1, double* delta1) {
+        Runtime& r = rt();
+        const int64_t n_int = sp.n_int;
+        const float* p_int = nullptr;
+        PGH_TRY(sp.bring(p->data, p_buf, &p_int));
+        result_int = result->data;
+        if (sp.blocked) {
+            PGH_TRY(res_buf.alloc(n_int));
+            result_int = res_buf.p;
+        }
+        if (n_int > 0) k_scale_copy<<<residual_grid(n_int), WG, 0, r.stream>>>(p_int, result_int, n_int, c1);
+        PGH_TRY(t0.alloc(n_int));
+        PGH_TRY(t1.alloc(n_int));
+        tbuf[0] = t0.p, tbuf[1] = t1.p;
+        term = p_int;                     // term_1
+        // isolated rows (BsfFormat::iso_begin): every term after the first is a * 0 + b * previous term there, i.e. zero when the
+        // personalization is zero on them -- the finish kernel then passes over their items (the accumulator keeps c_1 * p = 0)
+        iso_guard.on = sp.blocked && g->bsf.iso_flag != nullptr && g->bsf.pb.enabled && n_int > 0;
+        if (iso_guard.on) {
+            PGH_HIP(hipMemsetAsync(g->bsf.iso_flag, 0, sizeof(int), r.stream));
+            k_iso_watch<<<residual_grid(n_int), WG, 0, r.stream>>>(p_int, n_int, iso_tail_of(g->bsf));
+            PGH_HIP(hipMemsetAsync(t0.p, 0, sizeof(float) * (size_t)n_int, r.stream));
+            PGH_HIP(hipMemsetAsync(t1.p, 0, sizeof(float) * (size_t)n_int, r.stream));
+        }
+        scaled_gather = sp.blocked && g->bsf.src_scale != nullptr;
+        if (scaled_gather) PGH_TRY(bsf_to_internal(g, p->data, g->bsf.xg, true, 0.f));
+        // small graphs: fix-ups, epilogue and close in one one-workgroup launch (k_small_tail)
+        small_tail = sp.blocked && bsf_small_tail_usable(g);
+        // evaluated on the device like every other delta, on the internal-space result
+        return first_delta(result_int, n_int, sp.n, cfg, delta1);
+    }
+    bool closes_in_step() const { return small_tail; }
+    // (blocked layout: as in the recursive loops -- one launch and one dependent boundary fewer per term)
+    bool defers() const { return defer_close_enabled() && sp.blocked && !small_tail; }
+    int launch(int k, double c, const PendingClose& pc, int* count) {
+        EpiParams ep{};
+        const bool cheb = chebyshev && k > 2;      // abstract_filters.py:219-221
+        ep.a = cheb ? 2.0 : 1.0;
+        ep.b = cheb ? -1.0 : 0.0;
+        ep.v = cheb ? term : nullptr;
+        ep.y = tbuf[k & 1];
+        ep.r = result_int;
+        ep.c = c;
+        ep.err_linf = (cfg->err_kind == PGH_ERR_LINF);
+        if (scaled_gather) {
+            ep.xg_out = g->bsf.xg;
+            ep.src_scale = g->bsf.src_scale;
+            ep.xg_blk = g->bsf.blk_size;
+            ep.xg_live = g->bsf.xg_live;
+        }
+        const float* src = scaled_gather ? g->bsf.xg : term;
+        term = tbuf[k & 1];
+        if (small_tail) return bsf_launch_small<EPI_POLY>(g, ep, src, nullptr, g_state, pc);
+        return launch_step<EPI_POLY>(g, ep, src, g_state, count);
+    }
+    int take() {
+        const int64_t n = sp.n;
+        if (sp.blocked) {
+            PGH_TRY(bsf_to_original(g, result_int, result->data, cfg->out_scale));
+        } else if (n > 0 && cfg->out_scale != 1.0) {
+            k_scale_copy<<<residual_grid(n), WG, 0, rt().stream>>>(result->data, result->data, n, cfg->out_scale);
+        }
+        return 0;
+    }
+};
+
+// f64 terms and accumulator: the reference's "chebyshev" recurrence (see EpiPoly64 for why), and the taylor form under a tolerance
+// below fp32 eps.  Square graphs with the blocked layout: the blocked f64 image (pgh_bsf64.hip; vectors live in its internal id
+// space); otherwise the row-major CSR(M^T).
+struct PolyStepF64 {
+    pgh_graph_t         g;
+    pgh_vec_t           p, result;
+    const pgh_loop_cfg* cfg;
+    bool                cheb_recurrence;
+    bool                blocked = false;
+    DevF64              p64, res64, t0, t1, xg64;
+    double*             tbuf[2] = {nullptr, nullptr};
+    const double*       term = nullptr;
+    GraphView           view{};
+    StepGrid            grids{};
+
+    int bring(double c1, double* delta1) {
+        Runtime& r = rt();
+        const int64_t n = g->n_cols;
+        PGH_CHECK(g->items_per_tile == WG * kIPT, "graph tile table was built for a different tile size");
+        blocked = bsf64_usable(g);
+        if (blocked) PGH_TRY(bsf64_ensure(g));
+        const int64_t nv = blocked ? bsf64_length(g) : n;
+        PGH_TRY(p64.alloc(nv));
+        PGH_TRY(res64.alloc(nv));
+        PGH_TRY(t0.alloc(nv));
+        PGH_TRY(t1.alloc(nv));
+        if (blocked) PGH_TRY(xg64.alloc(nv + 1));
+        const int cgrid = residual_grid(n);
+        if (blocked) {
+            PGH_TRY(bsf64_bring(g, p->data, c1, p64.p, res64.p, xg64.p));
+        } else if (n > 0) {
+            k_f32_to_f64<<<cgrid, WG, 0, r.stream>>>(p->data, p64.p, n, 1.0);
+            k_f32_to_f64<<<cgrid, WG, 0, r.stream>>>(p->data, res64.p, n, c1);      // result_1 = c_1 * p (result_0 = 0)
+        }
+        tbuf[0] = t0.p, tbuf[1] = t1.p;
+        term = p64.p;
+        view = view_of(g);
+        grids = grids_for(g);
+        // on a caller-space f32 copy of result_1 (it decides only whether the loop stops at iteration 2)
+        DevF32 first;
+        PGH_TRY(first.alloc(n));
+        if (n > 0) k_scale_copy<<<cgrid, WG, 0, r.stream>>>(p->data, first.p, n, c1);
+        return first_delta(first.p, n, n, cfg, delta1);
+    }
+    bool closes_in_step() const { return false; }
+    bool defers() const { return defer_close_enabled() && blocked; }      // the close rides in the next term's k_bsf64_partial
+    int launch(int k, double c, const PendingClose&, int* count) {
+        Runtime& r = rt();
+        const bool cheb = cheb_recurrence && k > 2;      // abstract_filters.py:219-221 (taylor: every term is M^T of the last)
+        EpiPoly64 epi;
+        epi.a = cheb ? 2.0 : 1.0;
+        epi.b = cheb ? -1.0 : 0.0;
+        epi.c = c;
+        epi.term = term;
+        epi.term_out = tbuf[k & 1];
+        epi.r = res64.p;
+        epi.err_linf = (cfg->err_kind == PGH_ERR_LINF);
+        double* psum = r.d_partials;
+        double* pdel = r.d_partials + kMaxPartials;
+        term = tbuf[k & 1];
+        *count = grids.total();
+        if (blocked) return bsf64_step(g, epi.a, epi.b, epi.c, epi.term, epi.term_out, res64.p, xg64.p, epi.err_linf, g_state, psum, pdel, count);
+        {
+            ProfScope prof(PGH_K_SPMV);
+            k_spmv_merge<kIPT, double, EpiPoly64><<<grids.main_grid, WG, 0, r.stream>>>(view, epi, epi.term, g_state, psum, pdel);
+        }
+        {
+            ProfScope prof(PGH_K_FIXUP);
+            k_spmv_fixup<double, EpiPoly64><<<grids.fix_grid, WG, 0, r.stream>>>(view, epi, g_state, psum + grids.main_grid, pdel + grids.main_grid);
+        }
+        return 0;
+    }
+    int take() {
+        const int64_t n = g->n_cols;
+        if (blocked) PGH_TRY(bsf64_take(g, res64.p, cfg->out_scale, result->data));
+        else if (n > 0) k_f64_to_f32<<<residual_grid(n), WG, 0, rt().stream>>>(res64.p, result->data, n, cfg->out_scale);
+        return 0;
+    }
+};
+
+// ClosedFormGraphFilter's loop (abstract_filters.py:232-256) under ConvergenceManager (convergence.py:77-101).  Iteration 1 never
+// compares (the step sets result_1 = c_1 * p, term_1 = p; every reference run starts from result_0 = 0, abstract_filters.py:212-213);
+// the host mirrors iteration 2, which compares delta_1; the steps of iterations 2 .. max_iters - 1 run ahead on the device, the step
+// of iteration k producing term_{k+1} and result_k and being followed by the check of iteration k + 1.
+template <typename Stepper>
+int closed_form_run(Stepper& s, pgh_graph_t g, const double* coeffs, int32_t num_coeffs, pgh_vec_t result, const pgh_loop_cfg* cfg,
+                    pgh_loop_result* res) {
     auto coeff = [&](int it) -> double { return (it >= 1 && it <= num_coeffs) ? coeffs[it - 1] : 0.0; };
+    const int64_t n = g->n_cols;
     const int max_iters = cfg->max_iters;
     LoopTimer timer;
     PGH_TRY(timer.start());
-    int it = 1;
-    if (it >= max_iters) {
+    int it = 1;                       // ConvergenceManager.iteration
+    if (it >= max_iters) {            // convergence.py:86-89: stops before the first step
         PGH_TRY(pgh_vec_fill(result, 0.0));
         PGH_TRY(timer.stop(&res->loop_ms));
         res->iterations = it;
         res->converged = 0;
         return 0;
     }
-    PGH_CHECK(g->items_per_tile == WG * kIPT, "graph tile table was built for a different tile size");
-    // square graphs: the blocked f64 image (pgh_bsf64.hip; vectors live in its internal id space); otherwise the row-major CSR
-    const bool blocked = bsf64_usable(g);
-    if (blocked) PGH_TRY(bsf64_ensure(g));
-    const int64_t nv = blocked ? bsf64_length(g) : n;
-    DevF64 p64, res64, t0, t1, xg64;
-    PGH_TRY(p64.alloc(nv));
-    PGH_TRY(res64.alloc(nv));
-    PGH_TRY(t0.alloc(nv));
-    PGH_TRY(t1.alloc(nv));
-    if (blocked) PGH_TRY(xg64.alloc(nv + 1));
-    const int cgrid = residual_grid(n);
-    const double c1 = coeff(1);
-    if (blocked) {
-        PGH_TRY(bsf64_bring(g, p->data, c1, p64.p, res64.p, xg64.p));
-    } else if (n > 0) {
-        k_f32_to_f64<<<cgrid, WG, 0, r.stream>>>(p->data, p64.p, n, 1.0);
-        k_f32_to_f64<<<cgrid, WG, 0, r.stream>>>(p->data, res64.p, n, c1);      // result_1 = c_1 * p (result_0 = 0)
-    }
-    // delta_1 = |result_1 - 0| (decides only whether the loop stops at iteration 2)
     double err = 0.0;
-    {
-        DevF32 first;
-        PGH_TRY(first.alloc(n));
-        if (n > 0) k_scale_copy<<<cgrid, WG, 0, r.stream>>>(p->data, first.p, n, c1);
-        pgh_vec_s rv;
-        rv.data = first.p;
-        rv.n = n;
-        rv.owns = false;
-        const int kind = cfg->err_kind == PGH_ERR_ITERS ? PGH_ERR_L1 : cfg->err_kind;
-        PGH_TRY(pgh_scaled_residual(kind == PGH_ERR_MABS ? PGH_ERR_L1 : kind, &rv, 1.0, &rv, 0.0, &err));
-        if (kind == PGH_ERR_MABS && n > 0) err /= (double)n;
-    }
-    double* tbuf[2] = {t0.p, t1.p};
-    const double* term = p64.p;
+    PGH_TRY(s.bring(coeff(1), &err));
     int spmv = 0;
     bool converged = false;
-    k_state_init<<<1, 1, 0, r.stream>>>(g_state, 1.0);
-    const bool poll = g_progress_dev != nullptr;
-    const int batch = poll ? 1 : batch_for(g);
-    const int window = window_for(g);
-    static const bool defer_env64 = getenv("PGH_DEFER_CLOSE") == nullptr || atoi(getenv("PGH_DEFER_CLOSE")) != 0;
-    const bool defer64 = defer_env64 && blocked;
-    pending_close_slot().active = 0;
-    if (poll) progress_reset();
+    k_state_init<<<1, 1, 0, rt().stream>>>(g_state, 1.0);
+    RunAhead ahead(g);
     it = 2;
-    bool stop = false;
-    if (it >= max_iters) {
-        stop = true;
-    } else if (cfg->err_kind != PGH_ERR_ITERS && it % cfg->end_modulo == 0 && err <= cfg->tol) {
-        stop = true;
-        converged = true;
-    }
+    bool stop = it >= max_iters;
+    if (!stop && loop_checks_at(cfg->err_kind, it, max_iters, cfg->end_modulo) && err <= cfg->tol) stop = converged = true;
     if (!stop) {
-        const GraphView v = view_of(g);
-        const StepGrid sg = grids_for(g);
-        double* psum = r.d_partials;
-        double* pdel = r.d_partials + kMaxPartials;
-        int next_it = 2;
-        bool done = false;
-        while (!done && next_it < max_iters) {
-            if (poll) {
-                PGH_TRY(progress_wait(next_it - 2, window, &done));
-                if (done) break;
-            }
-            const int upto = (next_it + batch < max_iters) ? next_it + batch : max_iters;
-            for (; next_it < upto; ++next_it) {
-                const int k = next_it;
-                const bool cheb = cheb_recurrence && k > 2;      // abstract_filters.py:219-221 (taylor: every term is M^T of the last)
-                EpiPoly64 epi;
-                epi.a = cheb ? 2.0 : 1.0;
-                epi.b = cheb ? -1.0 : 0.0;
-                epi.c = coeff(k);
-                epi.term = term;
-                epi.term_out = tbuf[k & 1];
-                epi.r = res64.p;
-                epi.err_linf = (cfg->err_kind == PGH_ERR_LINF);
-                int count = sg.total();
-                if (blocked) {
-                    PGH_TRY(bsf64_step(g, epi.a, epi.b, epi.c, term, tbuf[k & 1], res64.p, xg64.p, epi.err_linf, g_state, psum, pdel, &count));
-                } else {
-                    {
-                        ProfScope prof(PGH_K_SPMV);
-                        k_spmv_merge<kIPT, double, EpiPoly64><<<sg.main_grid, WG, 0, r.stream>>>(v, epi, term, g_state, psum, pdel);
-                    }
-                    {
-                        ProfScope prof(PGH_K_FIXUP);
-                        k_spmv_fixup<double, EpiPoly64><<<sg.fix_grid, WG, 0, r.stream>>>(v, epi, g_state, psum + sg.main_grid, pdel + sg.main_grid);
-                    }
-                }
-                const int chk_it = k + 1;
-                const int check = (cfg->err_kind != PGH_ERR_ITERS) && (chk_it < max_iters) && (chk_it % cfg->end_modulo == 0);
-                if (defer64) {                     // blocked f64 image: the close rides in the next term's k_bsf64_partial
-                    PendingClose pc{};
-                    pc.state = g_state;
-                    pc.partial_sum = psum;
-                    pc.res_partials = pdel;
-                    pc.progress = g_progress_dev;
-                    pc.tol = cfg->tol;
-                    pc.n = (long long)n;
-                    pc.num_sum = count;
-                    pc.num_res = count;
-                    pc.check = check;
-                    pc.err_kind = cfg->err_kind;
-                    pc.active = 1;
-                    pending_close_slot() = pc;
-                } else {
-                    ProfScope prof(PGH_K_FINAL);
-                    k_step_close<<<1, WG, 0, r.stream>>>(g_state, psum, count, pdel, count, 0, check, cfg->err_kind, cfg->tol, n,
-                                                         nullptr, g_progress_dev);
-                }
-                term = tbuf[k & 1];
-            }
-            PGH_HIP(hipGetLastError());
-            if (!poll || next_it >= max_iters) PGH_TRY(flush_pending_close());
-            if (!poll) {
-                PGH_TRY(fetch_state());
-                done = g_state_host->done != 0;
-            }
-        }
+        const bool defer = s.defers();
+        auto step = [&](int j) -> int {            // the j-th step is iteration k = j + 1's
+            const int k = j + 1;
+            PendingClose pc = close_record(cfg, n, k + 1, 0, 0, 0);      // k + 1: the comparison of result_k with result_{k-1}
+            int count = 0;
+            PGH_TRY(s.launch(k, coeff(k), pc, &count));
+            if (s.closes_in_step()) return 0;
+            pc.num_sum = pc.num_res = count;
+            return close_step(pc, defer, false);
+        };
+        int enq = 0;
+        PGH_TRY(ahead.enqueue(&enq, max_iters - 2, step));
         PGH_TRY(flush_pending_close());               // a no-op once the loop has ended on the device
         PGH_TRY(fetch_state());
         spmv = g_state_host->steps;
         converged = g_state_host->converged != 0;
         err = g_state_host->steps > 0 ? g_state_host->err : err;
-        it = 2 + spmv;
+        it = 2 + spmv;                 // iteration value at loop exit
     }
     PGH_TRY(timer.stop(&res->loop_ms));           // (as in recursive_run: the way out is left running)
-    if (blocked) PGH_TRY(bsf64_take(g, res64.p, cfg->out_scale, result->data));
-    else if (n > 0) k_f64_to_f32<<<cgrid, WG, 0, r.stream>>>(res64.p, result->data, n, cfg->out_scale);
+    PGH_TRY(s.take());
     PGH_HIP(hipGetLastError());
     res->iterations = it;
     res->converged = converged ? 1 : 0;
@@ -2625,7 +2752,7 @@ int recursive_run_f64(pgh_graph_t g, int mode, pgh_vec_t p, pgh_vec_t lam, pgh_v
         // iterate's y * source scale, its quotient rides in a)
         ++spmv;
         ++it;
-        const bool check = cfg->err_kind != PGH_ERR_ITERS && it < max_iters && it % cfg->end_modulo == 0;
+        const bool check = loop_checks_at(cfg->err_kind, it, max_iters, cfg->end_modulo);
         constexpr int kAt = 8;                             // words of rt().d_scalars this loop uses: [kAt] = sum(y), [kAt + 1] = residual
         k_fold64<<<1, WG, 0, r.stream>>>(psum, count, 0, r.d_scalars + kAt);
         if (check) {
@@ -2729,15 +2856,11 @@ extern "C" int pgh_sarw_run(pgh_graph_t g, pgh_vec_t p, pgh_vec_t ranks, const p
     return rc;
 }
 
-// Closed-form filters: result_k = result_{k-1} + c_k * term_k, term_{k+1} = a * M^T term_k + b * term_k.
-// The reference accumulates first and multiplies afterwards (abstract_filters.py:254-256), which costs one
-// trailing, unused SpMV per run; here step k computes term_{k+1} AND folds it into the result, so the
-// run needs (iterations - 2) SpMVs for the identical result.
+// Closed-form filters (closed_form_run above)
 extern "C" int pgh_poly_run(pgh_graph_t g, pgh_vec_t p, const double* coeffs, int32_t num_coeffs, int32_t chebyshev,
                             pgh_vec_t result, const pgh_loop_cfg* cfg, pgh_loop_result* res) {
     PGH_CHECK(g && p && result && cfg && res && (coeffs || num_coeffs == 0), "pgh_poly_run: null argument");
     PGH_TRY(ensure_state());
-    Runtime& r = rt();
     const int64_t n = g->n_cols;
     PGH_CHECK(g->n_rows == g->n_cols && p->n == n && result->n == n, "pgh_poly_run: shape mismatch");
     PGH_CHECK(cfg->end_modulo >= 1, "end_modulo must be >= 1");
@@ -2746,183 +2869,12 @@ extern "C" int pgh_poly_run(pgh_graph_t g, pgh_vec_t p, const double* coeffs, in
     // kernels for measurements)
     // chebyshev == 2: the TAYLOR form with f64 terms and accumulator (round 6: tolerances below fp32 eps; the caller clamps cfg->tol at
     // fp64 eps like the reference's numpy backend, pygrank/core/backend/numpy.py:84-86)
-    if (chebyshev == 2) return poly_run_f64(g, p, coeffs, num_coeffs, result, cfg, res, false);
-    if (chebyshev && !(getenv("PGH_CHEB_F32") != nullptr && atoi(getenv("PGH_CHEB_F32")) != 0))
-        return poly_run_f64(g, p, coeffs, num_coeffs, result, cfg, res, true);
-    auto coeff = [&](int it) -> double { return (it >= 1 && it <= num_coeffs) ? coeffs[it - 1] : 0.0; };
-    const int max_iters = cfg->max_iters;
-    LoopTimer timer;
-    PGH_TRY(timer.start());
-    // iteration 1: has_converged never compares; the step sets result_1 = c_1 * p (term_1 = p).
-    // Every reference run starts from result_0 = 0 (abstract_filters.py:212-213).
-    int it = 1;                       // ConvergenceManager.iteration
-    if (it >= max_iters) {            // convergence.py:86-89: stops before the first step
-        PGH_TRY(pgh_vec_fill(result, 0.0));
-        PGH_TRY(timer.stop(&res->loop_ms));
-        res->iterations = it;
-        res->converged = 0;
-        return 0;
+    if (chebyshev == 2 || (chebyshev && !(getenv("PGH_CHEB_F32") != nullptr && atoi(getenv("PGH_CHEB_F32")) != 0))) {
+        PolyStepF64 s{g, p, result, cfg, chebyshev != 2};
+        return closed_form_run(s, g, coeffs, num_coeffs, result, cfg, res);
     }
-    InternalSpace sp(g);
-    const int64_t n_int = sp.n_int;
-    DevF32 p_buf, res_buf, t0, t1;
-    const float* p_int = nullptr;
-    PGH_TRY(sp.bring(p->data, p_buf, &p_int));
-    float* result_int = result->data;
-    if (sp.blocked) {
-        PGH_TRY(res_buf.alloc(n_int));
-        result_int = res_buf.p;
-    }
-    const double c1 = coeff(1);
-    if (n_int > 0) k_scale_copy<<<residual_grid(n_int), WG, 0, r.stream>>>(p_int, result_int, n_int, c1);
-    PGH_TRY(t0.alloc(n_int));
-    PGH_TRY(t1.alloc(n_int));
-    float* tbuf[2] = {t0.p, t1.p};
-    const float* term = p_int;        // term_1
-    // isolated rows (BsfFormat::iso_begin): every term after the first is a * 0 + b * previous term there, i.e. zero when the
-    // personalization is zero on them -- the finish kernel then passes over their items (the accumulator keeps c_1 * p = 0)
-    const bool watch_iso = sp.blocked && g->bsf.iso_flag != nullptr && g->bsf.pb.enabled && n_int > 0;
-    struct IsoGuard {
-        pgh_graph_t g_;
-        bool on;
-        ~IsoGuard() {
-            if (on) (void)iso_flag_release(g_);
-        }
-    } iso_guard{g, watch_iso};
-    if (watch_iso) {
-        PGH_HIP(hipMemsetAsync(g->bsf.iso_flag, 0, sizeof(int), r.stream));
-        k_iso_watch<<<residual_grid(n_int), WG, 0, r.stream>>>(p_int, n_int, iso_tail_of(g->bsf));
-        PGH_HIP(hipMemsetAsync(t0.p, 0, sizeof(float) * (size_t)n_int, r.stream));
-        PGH_HIP(hipMemsetAsync(t1.p, 0, sizeof(float) * (size_t)n_int, r.stream));
-    }
-    const bool scaled_gather = sp.blocked && g->bsf.src_scale != nullptr;
-    if (scaled_gather) PGH_TRY(bsf_to_internal(g, p->data, g->bsf.xg, true, 0.f));
-    // delta_1 = |result_1 - 0|, evaluated on the device like every other delta
-    double err = 0.0;
-    {
-        pgh_vec_s rv;
-        rv.data = result_int;
-        rv.n = n_int;
-        rv.owns = false;
-        double e = 0.0;
-        const int kind = cfg->err_kind == PGH_ERR_ITERS ? PGH_ERR_L1 : cfg->err_kind;
-        PGH_TRY(pgh_scaled_residual(kind == PGH_ERR_MABS ? PGH_ERR_L1 : kind, &rv, 1.0, &rv, 0.0, &e));
-        if (kind == PGH_ERR_MABS && n > 0) e /= (double)n;
-        err = e;
-    }
-    int spmv = 0;
-    bool converged = false;
-    k_state_init<<<1, 1, 0, r.stream>>>(g_state, 1.0);
-    const bool poll = g_progress_dev != nullptr;
-    const int batch = poll ? 1 : batch_for(g);
-    const int window = window_for(g);
-    const bool small_tail = sp.blocked && bsf_small_tail_usable(g);
-    static const bool defer_env = getenv("PGH_DEFER_CLOSE") == nullptr || atoi(getenv("PGH_DEFER_CLOSE")) != 0;
-    const bool defer = defer_env && sp.blocked && !small_tail;
-    pending_close_slot().active = 0;
-    if (poll) progress_reset();
-    // host-side mirror of the reference loop for iteration 2 (uses err of step 1), then device batches
-    it = 2;
-    bool stop = false;
-    if (it >= max_iters) {
-        stop = true;
-    } else if (cfg->err_kind != PGH_ERR_ITERS && it % cfg->end_modulo == 0 && err <= cfg->tol) {
-        stop = true;
-        converged = true;
-    }
-    if (!stop) {
-        // steps for iterations it = 2 .. max_iters-1; step at iteration `it` produces term_it and result_it
-        int next_it = 2;
-        bool done = false;
-        while (!done && next_it < max_iters) {
-            if (poll) {
-                PGH_TRY(progress_wait(next_it - 2, window, &done));
-                if (done) break;
-            }
-            const int upto = (next_it + batch < max_iters) ? next_it + batch : max_iters;
-            for (; next_it < upto; ++next_it) {
-                const int k = next_it;            // iteration index of this step
-                EpiParams ep{};
-                const bool cheb = chebyshev && k > 2;      // abstract_filters.py:219-221
-                ep.a = cheb ? 2.0 : 1.0;
-                ep.b = cheb ? -1.0 : 0.0;
-                ep.v = cheb ? term : nullptr;
-                float* tout = tbuf[k & 1];
-                ep.y = tout;
-                ep.r = result_int;
-                ep.c = coeff(k);
-                ep.err_linf = (cfg->err_kind == PGH_ERR_LINF);
-                if (scaled_gather) {
-                    ep.xg_out = g->bsf.xg;
-                    ep.src_scale = g->bsf.src_scale;
-                    ep.xg_blk = g->bsf.blk_size;
-                    ep.xg_live = g->bsf.xg_live;
-                }
-                int count = 0;
-                const int chk_it = k + 1;         // the comparison of result_k with result_{k-1}
-                const int check = (cfg->err_kind != PGH_ERR_ITERS) && (chk_it < max_iters) && (chk_it % cfg->end_modulo == 0);
-                if (small_tail) {                 // small graphs: fix-ups, epilogue and close in one one-workgroup launch (k_small_tail)
-                    PendingClose pc{};
-                    pc.state = g_state;
-                    pc.progress = g_progress_dev;
-                    pc.tol = cfg->tol;
-                    pc.n = (long long)n;
-                    pc.check = check;
-                    pc.err_kind = cfg->err_kind;
-                    PGH_TRY((bsf_launch_small<EPI_POLY>(g, ep, scaled_gather ? g->bsf.xg : term, nullptr, g_state, pc)));
-                    term = tout;
-                    continue;
-                }
-                PGH_TRY((launch_step<EPI_POLY>(g, ep, scaled_gather ? g->bsf.xg : term, g_state, &count)));
-                if (defer) {
-                    // blocked layout: the close of this term rides in the first kernel of the next one, as in the recursive loops
-                    // (PendingClose; one launch and one dependent boundary fewer per term)
-                    PendingClose pc{};
-                    pc.state = g_state;
-                    pc.partial_sum = r.d_partials;
-                    pc.res_partials = r.d_partials + kMaxPartials;
-                    pc.progress = g_progress_dev;
-                    pc.tol = cfg->tol;
-                    pc.n = (long long)n;
-                    pc.num_sum = count;
-                    pc.num_res = count;
-                    pc.check = check;
-                    pc.err_kind = cfg->err_kind;
-                    pc.active = 1;
-                    pending_close_slot() = pc;
-                } else {
-                    ProfScope prof(PGH_K_FINAL);
-                    k_step_close<<<1, WG, 0, r.stream>>>(g_state, r.d_partials, count, r.d_partials + kMaxPartials,
-                                                         count, 0, check, cfg->err_kind, cfg->tol, n, nullptr, g_progress_dev);
-                }
-                term = tout;
-            }
-            PGH_HIP(hipGetLastError());
-            if (!poll || next_it >= max_iters) PGH_TRY(flush_pending_close());
-            if (!poll) {
-                PGH_TRY(fetch_state());
-                done = g_state_host->done != 0;
-            }
-        }
-        PGH_TRY(flush_pending_close());               // a no-op once the loop has ended on the device
-        PGH_TRY(fetch_state());
-        spmv = g_state_host->steps;
-        converged = g_state_host->converged != 0;
-        err = g_state_host->steps > 0 ? g_state_host->err : err;
-        it = 2 + spmv;                 // iteration value at loop exit
-    }
-    PGH_TRY(timer.stop(&res->loop_ms));           // (as in recursive_run: the way out is left running)
-    if (sp.blocked) {
-        PGH_TRY(bsf_to_original(g, result_int, result->data, cfg->out_scale));
-    } else if (n > 0 && cfg->out_scale != 1.0) {
-        k_scale_copy<<<residual_grid(n), WG, 0, r.stream>>>(result->data, result->data, n, cfg->out_scale);
-    }
-    PGH_HIP(hipGetLastError());
-    res->iterations = it;
-    res->converged = converged ? 1 : 0;
-    res->spmv_count = spmv;
-    res->last_error = err;
-    return 0;
+    PolyStepF32 s(g, p, result, cfg, chebyshev != 0);
+    return closed_form_run(s, g, coeffs, num_coeffs, result, cfg, res);
 }
 
 PGH_WARM_KERNEL(k_state_resume)
