@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI: include/pgh.h, which every engine library exports in full, and the optional headers
-include/pgh_*.h (OPTIONAL below), one per fused entry family.
+include/pgh_*.h (TABLES below), one per fused entry family.
 
 Every symbol of SIGNATURES is bound when the library loads; a library that lacks one does not load.  The optional tables are bound
 apart, on the first ``entry(name)``: a library without them -- the host test double under oracle/ -- still loads, ``entry`` returns
@@ -325,6 +325,15 @@ POST_SIGNATURES = {
 POST_MAX_COLS = 64        # include/pgh_post.h PGH_POST_MAX_COLS
 POST_ROW_SUB, POST_ROW_SWEEP = 0, 1                                                 # include/pgh_post.h PGH_POST_ROW_*
 
+# include/pgh_gnn.h.  Unfused route: gnn.differentiable_propagate steps its recurrences one conv at a time (needs pgh_graph_transposed
+# under graph_dropout), stages its slabs through the host, and builds the transposed operator from a scipy round trip.
+GNN_SIGNATURES = {
+    "pgh_graph_transposed": (C.c_int, [c_graph, C.POINTER(c_graph)]),
+    "pgh_linear_run_batch": (C.c_int, [c_graph, c_mat, C.c_double, C.c_int32, c_f64p, c_f64p, c_f64p, c_mat, C.c_double, C.c_uint64,
+                                       C.c_int64, c_f64p]),
+    "pgh_mat_wrap": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(c_mat)]),
+}
+
 # header -> its table: every optional entry family; the names are distinct across the tables and from SIGNATURES
 OPTIONAL = {
     "pgh_batch.h": BATCH_SIGNATURES, "pgh_tune.h": TUNE_SIGNATURES, "pgh_measure.h": MEASURE_SIGNATURES,
@@ -333,7 +342,10 @@ OPTIONAL = {
     "pgh_krylov.h": KRYLOV_SIGNATURES, "pgh_link.h": LINK_SIGNATURES, "pgh_arnoldi.h": ARNOLDI_SIGNATURES,
     "pgh_post.h": POST_SIGNATURES,
 }
-_HEADER_OF = {name: header for header, table in OPTIONAL.items() for name in table}
+# ... and every header entry() serves: OPTIONAL -- the thirteen families whose number and 41 names tests/test_fused_plumbing.py pins --
+# and the headers added since, which tests of their own enumerate (include/pgh_gnn.h: tests/test_gnn_host.py)
+TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES})
+_HEADER_OF = {name: header for header, table in TABLES.items() for name in table}
 DECLINED = 2              # every optional header's PGH_*_DECLINED: nothing was written, the caller takes its unfused route
 
 _lib = None
@@ -378,7 +390,7 @@ def entry(name):
     cdll = lib()
     cache = getattr(cdll, attribute, None)
     if cache is None:
-        cache = bind_optional(cdll, OPTIONAL[header])
+        cache = bind_optional(cdll, TABLES[header])
         setattr(cdll, attribute, cache)
     return cache[name]
 

@@ -245,6 +245,7 @@ struct pgh_mat_s {
     float*  data = nullptr;
     int64_t n = 0;
     int32_t b = 0;
+    bool    owns = true;     // false: a view of somebody else's buffer (pgh_mat_wrap, include/pgh_gnn.h)
 };
 
 struct pgh_timer_s {
@@ -474,6 +475,10 @@ struct pgh_graph_s {
     int64_t  part_live_nodes = -1;   // generated partitions: ids with any edge (they sort first; -1 = unknown)
     int64_t  row_begin = 0;
     PushIndex push;                  // out-edge index of the sparse first step (pgh_push.hip), built on first use
+    // a transposed graph (pgh_graph_transposed, include/pgh_gnn.h): bsf_mm.mm_edge holds, for the entry (i, j), the index of the entry
+    // (j, i) in its mask partner's CSR(M^T) -- the multi-seed dropout launches apply the transpose of the partner's mask; the
+    // single-vector images have no such words and refuse dropout
+    bool mask_mirrored = false;
 };
 
 // ---------------------------------------------------------------- device helpers

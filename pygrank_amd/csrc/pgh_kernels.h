@@ -734,6 +734,13 @@ int bsf_ensure_edge_ids(pgh_graph_s* g);
 void bsf_set_dropout(double rate, uint64_t seed);
 void bsf_clear_dropout();
 DropView bsf_dropout_view(const int32_t* edge);
+// the multi-seed image as pgh_gnn.hip drives it (pgh_spmm.hip): slabs are [BsfFormat::n_out, ld] in the image's id space, ld = b rounded up
+// to whole float4s; mm_masked_sums is pgh_spmm's product before its output scale (BsfFormat::mm_rowop holds the row operands)
+int mm_ensure_layout(pgh_graph_s* g);
+int mm_mirror_edge_ids(pgh_graph_s* gt, const pgh_graph_s* partner);
+int mm_slab_in(pgh_graph_s* g, const float* src, int b, int ld, float* dst_int);
+int mm_slab_out(pgh_graph_s* g, const float* src_int, int b, int ld, float* dst);
+int mm_masked_sums(pgh_graph_s* g, const float* xg, int ld, int b, float* sums, double rate, uint64_t seed);
 // the partitioned loop's fused scalars (pgh_spmv.hip; driven by pgh_dist.hip)
 bool dist_can_fuse(const pgh_graph_s* g);
 // where a partitioned run keeps this rank's slice of the next gather vector: packed for the exchange (BsfFormat::lg_*), 0 = by row

@@ -1048,7 +1048,7 @@ extern "C" int pgh_mat_alloc(int64_t n, int32_t b, pgh_mat_t* out) {
 }
 extern "C" int pgh_mat_free(pgh_mat_t m) {
     if (!m) return 0;
-    pool_free(m->data);
+    if (m->owns) pool_free(m->data);
     delete m;
     return 0;
 }

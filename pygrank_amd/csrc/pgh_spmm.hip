@@ -127,7 +127,10 @@ struct MMDrop {
 
 // index in CSR(M^T) order of every entry of the multi-seed stream (built once, on the first dropout launch): the entry's
 // row is that of its segment, its source is the column word; both go back to the caller's ids and the source is looked up
-// in the row (sorted indices: binary search)
+// in the row (sorted indices: binary search).  MIRROR (a transposed graph, include/pgh_gnn.h): rowptr / col are the mask PARTNER's and the
+// swapped pair is looked up there -- the word of the entry (i, j) is the index of the partner's entry (j, i), so the mask this image
+// applies for a seed is the transpose of the one its partner applies
+template <bool MIRROR = false>
 __global__ __launch_bounds__(WG) void k_mm_edge_ids(const uint32_t* __restrict__ colf, const int4* __restrict__ tile,
                                                      const int32_t* __restrict__ seg_row, int num_tiles, const int32_t* __restrict__ perm,
                                                      const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -150,10 +153,11 @@ __global__ __launch_bounds__(WG) void k_mm_edge_ids(const uint32_t* __restrict__
             if (row_new >= 0) {
                 const int row_old = perm ? perm[row_new] : row_new;
                 const int col_old = perm ? perm[w & 0x7fffffffu] : (int)(w & 0x7fffffffu);
-                int lo = rowptr[row_old], hi = rowptr[row_old + 1];
+                const int in_row = MIRROR ? col_old : row_old, find = MIRROR ? row_old : col_old;
+                int lo = in_row >= 0 ? rowptr[in_row] : -1, hi = in_row >= 0 ? rowptr[in_row + 1] : -1;
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
-                    if (col[mid] < col_old) lo = mid + 1; else hi = mid;
+                    if (col[mid] < find) lo = mid + 1; else hi = mid;
                 }
                 out = lo;
             }
@@ -1289,10 +1293,11 @@ MMView mm_view(const BsfFormat& f) {
 int ensure_mm_edge_ids(pgh_graph_s* g) {
     BsfFormat& f = g->bsf_mm;
     if (f.mm_edge != nullptr) return 0;
+    PGH_CHECK(!g->mask_mirrored, "graph_dropout: the transposed graph has lost its mirrored index words");
     PGH_CHECK(g->rowptr != nullptr && g->col != nullptr, "graph_dropout on a batch needs the CSR image of the graph");
     PGH_HIP(pooled_malloc(&f.mm_edge, sizeof(int32_t) * (size_t)f.num_entries));
-    k_mm_edge_ids<<<blocks_for((int64_t)f.num_tiles * 64, 64), WG, 0, rt().stream>>>(f.colf, f.tile, f.seg_row, f.num_tiles, f.perm, g->rowptr,
-                                                                                      g->col, f.mm_edge);
+    k_mm_edge_ids<false><<<blocks_for((int64_t)f.num_tiles * 64, 64), WG, 0, rt().stream>>>(f.colf, f.tile, f.seg_row, f.num_tiles, f.perm, g->rowptr,
+                                                                                             g->col, f.mm_edge);
     PGH_HIP(hipGetLastError());
     PGH_HIP(hipStreamSynchronize(rt().stream));
     f.device_bytes += (int64_t)f.num_entries * 4;
@@ -2173,3 +2178,57 @@ extern "C" int pgh_poly_run_batch_mixed(pgh_graph_t g, pgh_mat_t p, const double
     for (size_t i = 0; i < (size_t)num_coeffs * p->b; ++i) PGH_CHECK(std::isfinite(coeffs[i]), "pgh_poly_run_batch_mixed: a non-finite coefficient");
     return poly_batch_impl(g, p, coeffs, num_coeffs, result, cfg, out_scales, results, true);
 }
+
+// =================================================================================================
+// What pgh_gnn.hip (include/pgh_gnn.h) drives of the multi-seed image: its way in and out, one masked product, the mirrored index words.
+// =================================================================================================
+namespace pgh {
+
+int mm_ensure_layout(pgh_graph_s* g) { return ensure_mm_layout(g); }
+
+// gt->bsf_mm.mm_edge <- for every stream entry (i, j) of gt the index of the entry (j, i) in the partner's CSR(M^T)
+int mm_mirror_edge_ids(pgh_graph_s* gt, const pgh_graph_s* partner) {
+    PGH_CHECK(partner->rowptr != nullptr && partner->col != nullptr && partner->n_rows == gt->n_rows && partner->n_cols == gt->n_cols,
+              "the mask partner needs the CSR image of a graph of the same shape");
+    PGH_TRY(ensure_mm_layout(gt));
+    BsfFormat& f = gt->bsf_mm;
+    PGH_CHECK(f.mm_edge == nullptr, "the graph has index words of its own already");
+    PGH_HIP(pooled_malloc(&f.mm_edge, sizeof(int32_t) * (size_t)f.num_entries));
+    k_mm_edge_ids<true><<<blocks_for((int64_t)f.num_tiles * 64, 64), WG, 0, rt().stream>>>(f.colf, f.tile, f.seg_row, f.num_tiles, f.perm,
+                                                                                            partner->rowptr, partner->col, f.mm_edge);
+    PGH_HIP(hipGetLastError());
+    PGH_HIP(hipStreamSynchronize(rt().stream));
+    f.device_bytes += (int64_t)f.num_entries * 4;
+    gt->mask_mirrored = true;
+    return 0;
+}
+
+// dst_int [n_int, ld] <- the caller's [n, b] slab in the image's id space (holes and the columns b .. ld - 1 zero)
+int mm_slab_in(pgh_graph_s* g, const float* src, int b, int ld, float* dst_int) {
+    const BsfFormat& f = g->bsf_mm;
+    PermuteIn q{};
+    q.src_b = src;
+    q.out_b = dst_int;
+    k_mm_permute_in<<<blocks_for((int64_t)f.n_out * lanes_per_row(ld)), WG, 0, rt().stream>>>(q, f.perm, f.n_out, g->n_rows, b, ld);
+    PGH_HIP(hipGetLastError());
+    return 0;
+}
+
+// the caller's [n, b] slab <- src_int [n_int, ld]; every caller id has exactly one row
+int mm_slab_out(pgh_graph_s* g, const float* src_int, int b, int ld, float* dst) {
+    const BsfFormat& f = g->bsf_mm;
+    k_mm_permute_out<<<blocks_for((int64_t)f.n_out * lanes_per_row(ld)), WG, 0, rt().stream>>>(src_int, f.perm, f.n_out, g->n_cols, b, ld, nullptr, dst);
+    PGH_HIP(hipGetLastError());
+    return 0;
+}
+
+// sums [n_int, ld] <- the row sums of the stream times the gather slab xg, under the mask of (rate, seed) when rate > 0; rows without
+// entries keep what they hold (the caller's zeros)
+int mm_masked_sums(pgh_graph_s* g, const float* xg, int ld, int b, float* sums, double rate, uint64_t seed) {
+    MMDrop drop_store;
+    const MMDrop* drop = nullptr;
+    PGH_TRY(make_drop(g, rate, seed, &drop_store, &drop));
+    return mm_partial(g, xg, ld, b, sums, nullptr, drop);
+}
+
+}  // namespace pgh

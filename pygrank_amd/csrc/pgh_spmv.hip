@@ -844,6 +844,7 @@ extern "C" int pgh_spmv(pgh_graph_t g, pgh_vec_t x, pgh_vec_t y) {
 extern "C" int pgh_spmv_dropout(pgh_graph_t g, pgh_vec_t x, pgh_vec_t y, double rate, uint64_t seed) {
     PGH_TRY(check_graph_vecs(g, x, y, "pgh_spmv_dropout"));
     PGH_CHECK(rate >= 0.0 && rate < 1.0, "pgh_spmv_dropout: rate must lie in [0, 1)");
+    PGH_CHECK(rate == 0.0 || !g->mask_mirrored, "pgh_spmv_dropout: a transposed graph mirrors its partner's mask in the multi-seed image only (include/pgh_gnn.h)");
     if (g->n_cols == 0) return 0;
     if (rate > 0.0 && bsf_dropout_usable(g)) {
         // the blocked layouts (round 4): the stream kernel and the cold image's phase A multiply every entry by the mask factor of
@@ -896,6 +897,7 @@ __global__ void k_dropout_degrees(const int32_t* __restrict__ col, const float* 
 extern "C" int pgh_graph_degrees_dropout(pgh_graph_t g, double rate, uint64_t seed, pgh_vec_t out) {
     PGH_CHECK(g && out && out->n == g->n_rows, "pgh_graph_degrees_dropout: length mismatch");
     PGH_CHECK(rate >= 0.0 && rate < 1.0, "pgh_graph_degrees_dropout: rate must lie in [0, 1)");
+    PGH_CHECK(rate == 0.0 || !g->mask_mirrored, "pgh_graph_degrees_dropout: a transposed graph mirrors its partner's mask in the multi-seed image only (include/pgh_gnn.h)");
     if (g->n_rows == 0) return 0;
     Runtime& r = rt();
     double* acc = nullptr;
@@ -2362,6 +2364,7 @@ extern "C" int pgh_ppr_run_dropout(pgh_graph_t g, pgh_vec_t p, pgh_vec_t ranks, 
     PGH_CHECK(g && p && ranks && cfg && res, "pgh_ppr_run_dropout: null argument");
     PGH_CHECK(p->n == g->n_cols, "pgh_ppr_run_dropout: personalization length mismatch");
     PGH_CHECK(rate >= 0.0 && rate < 1.0, "pgh_ppr_run_dropout: rate must lie in [0, 1)");
+    PGH_CHECK(rate == 0.0 || !g->mask_mirrored, "pgh_ppr_run_dropout: a transposed graph mirrors its partner's mask in the multi-seed image only (include/pgh_gnn.h)");
     EpiParams ep{};
     ep.a = cfg->alpha;
     ep.b = 1.0 - cfg->alpha;

@@ -775,6 +775,19 @@ class DeviceMatrix:
         return m
 
     @staticmethod
+    def wrap(device_ptr, n, b, keepalive=None):
+        """A view of a contiguous row-major f32 [n, b] buffer somebody else owns (include/pgh_gnn.h pgh_mat_wrap; a torch tensor's
+        data_ptr()): freeing the matrix leaves the buffer alone, `keepalive` lives as long as the view."""
+        entry = L.entry("pgh_mat_wrap")
+        if entry is None:
+            raise L.EngineError("this engine library has no pgh_mat_wrap (include/pgh_gnn.h)")
+        h = L.c_mat()
+        L.check(entry(C.c_void_p(device_ptr), int(n), int(b), C.byref(h)))
+        m = DeviceMatrix(h, n, b)
+        m._keepalive = keepalive
+        return m
+
+    @staticmethod
     def from_columns(cols):
         cols = list(cols)
         m = DeviceMatrix.empty(len(cols[0]), len(cols))
@@ -1070,6 +1083,20 @@ class DeviceGraph:
         data = np.empty(self.nnz, dtype=np.float32)
         L.check(L.lib().pgh_graph_download(self._h, _ptr(indptr), _ptr(indices), _ptr(data)))
         return sp.csr_array((data, indices, indptr), shape=(self.shape[1], self.shape[0]))
+
+    def transposed(self):
+        """The graph that stores the transpose of this one's CSR(M^T), built on the device with this graph as its mask partner
+        (include/pgh_gnn.h pgh_graph_transposed): its conv is x -> M x and its multi-seed dropout launches apply the transpose of the
+        mask this graph applies for the same seed.  None when the library lacks the entry or declines this graph."""
+        entry = L.entry("pgh_graph_transposed")
+        if entry is None or self._h is None:
+            return None
+        h = L.c_graph()
+        if not L.accepted(entry(self._h, C.byref(h))):
+            return None
+        out = DeviceGraph(h, (self.shape[1], self.shape[0]), self.nnz)
+        out.mask_mirrored = True
+        return out
 
     def conv(self, x):
         """M^T x (numpy.py:64-65); pure.  A DeviceMatrix [n, b] is propagated as one multi-seed pass (b <= 64)."""
