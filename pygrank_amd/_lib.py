@@ -14,7 +14,6 @@ There is NO CPU fallback: if the library is missing, if it reports a runtime oth
 visible when the engine is first used, an exception is raised.
 """
 import ctypes as C
-import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -393,16 +392,6 @@ def entry(name):
         cache = bind_optional(cdll, TABLES[header])
         setattr(cdll, attribute, cache)
     return cache[name]
-
-
-# The per-family names from before entry() and DECLINED.  Nothing in this tree uses them; they stay for one change, so that the tests
-# of the commit before it -- which every change is checked against -- run on this code.  The next change deletes this block.
-BATCH_DECLINED = TUNE_DECLINED = MEASURE_DECLINED = PAIR_DECLINED = FAIR_DECLINED = MIXED_DECLINED = LFPR_DECLINED = DECLINED
-OVERSAMPLE_DECLINED = RANK_DECLINED = KRYLOV_DECLINED = LINK_DECLINED = ARNOLDI_DECLINED = POST_DECLINED = DECLINED
-batch_entry = tune_entry = measure_entry = supervised_entry = fair_entry = mixed_entry = lfpr_entry = oversample_entry = entry
-rank_entry = krylov_entry = link_entry = arnoldi_entry = post_entry = entry
-(bind_batch, bind_tune, bind_measure, bind_supervised, bind_fair, bind_mixed, bind_lfpr, bind_oversample, bind_rank, bind_krylov,
- bind_link, bind_arnoldi, bind_post) = (functools.partial(bind_optional, table=_table) for _table in OPTIONAL.values())
 
 
 def load_library(path=None):

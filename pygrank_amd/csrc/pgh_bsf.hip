@@ -40,14 +40,6 @@ constexpr int kBsfHot = PGH_BSF_HOT;        // f32 entries of the gather vector 
 constexpr uint64_t kLow29 = (1ULL << 29) - 1;
 constexpr uint64_t kRowSentinel = kLow29;        // sorts after every real row of a block
 
-inline int blocks_for(int64_t n, int cap_mult = 16) {
-    int64_t b = (n + kBlock - 1) / kBlock;
-    const int64_t cap = (int64_t)rt().num_cus * cap_mult;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // ------------------------------------------------------------------------------------------------- builder kernels
 // reference count of every source (weights count as multiplicities when the format is value-free)
 __global__ void k_source_counts(const int32_t* __restrict__ col, const int32_t* __restrict__ mult, int64_t nnz,

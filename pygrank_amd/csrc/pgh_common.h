@@ -141,6 +141,42 @@ struct StreamFence {
         return hipStreamSynchronize(rt().stream);
     }
 };
+// Times a device loop on the engine's stream: start() creates the two events and records the first, stop() records the second, waits
+// for it and reads the time between them.  Every way out of the frame destroys both.
+struct LoopTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~LoopTimer() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int start() {
+        PGH_HIP(hipEventCreate(&a));
+        PGH_HIP(hipEventCreate(&b));
+        PGH_HIP(hipEventRecord(a, rt().stream));
+        return 0;
+    }
+    int stop(double* ms) {
+        PGH_HIP(hipEventRecord(b, rt().stream));
+        PGH_HIP(hipEventSynchronize(b));
+        float f = 0.f;
+        PGH_HIP(hipEventElapsedTime(&f, a, b));
+        *ms = (double)f;
+        return 0;
+    }
+};
+// an input an optional entry does not serve: nothing was enqueued, nothing was written; `status` is the header's *_DECLINED
+inline int declined(int status, const std::string& why) {
+    set_error(why);
+    return status;
+}
+// workgroups of 256 threads (WG, kBlock) for the grid-stride walk of n items: at most cap_mult per CU, at least one
+inline int blocks_for(int64_t n, int cap_mult = 16) {
+    int64_t blocks = (n + 255) / 256;
+    const int64_t cap = (int64_t)rt().num_cus * cap_mult;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
+}
 template <typename T>
 struct DevBuf {
     T* p = nullptr;

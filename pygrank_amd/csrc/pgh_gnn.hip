@@ -19,18 +19,6 @@ namespace {
 
 constexpr int kLanes = 64;
 
-int declined(const char* msg) {
-    set_error(msg);
-    return PGH_GNN_DECLINED;
-}
-
-int blocks_of(int64_t n, int cap_mult = 16) {
-    int64_t blocks = (n + WG - 1) / WG;
-    const int64_t cap = (int64_t)rt().num_cus * cap_mult;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 // ------------------------------------------------------------------------------------------------- transposition
 __global__ void k_gnn_iota(int32_t* __restrict__ v, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = (int32_t)i;
@@ -97,33 +85,15 @@ __global__ __launch_bounds__(WG) void k_gnn_close(const f32x4* __restrict__ rowo
     }
 }
 
-struct Slab {
-    void* p = nullptr;
-    ~Slab() {
-        if (p) pool_free(p);
-    }
-    int alloc(size_t bytes) { return pool_alloc(bytes > 0 ? bytes : 1, &p); }
-    float* f() { return static_cast<float*>(p); }
-    f32x4* q() { return static_cast<f32x4*>(p); }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
 }  // namespace
 
 extern "C" int pgh_graph_transposed(pgh_graph_t g, pgh_graph_t* out) {
     PGH_CHECK(g && out, "pgh_graph_transposed: null argument");
-    if (g->n_rows != g->n_cols) return declined("pgh_graph_transposed: a square matrix only");
-    if (g->part_perm != nullptr || g->row_begin != 0) return declined("pgh_graph_transposed: not on a slice of a row partition");
-    if (g->rowptr == nullptr || g->col == nullptr || g->val == nullptr) return declined("pgh_graph_transposed: the graph keeps no CSR image");
-    if (!g->bsf.enabled) return declined("pgh_graph_transposed: the graph has no blocked layout");
-    if (g->n_rows == 0) return declined("pgh_graph_transposed: an empty graph");
+    if (g->n_rows != g->n_cols) return declined(PGH_GNN_DECLINED, "pgh_graph_transposed: a square matrix only");
+    if (g->part_perm != nullptr || g->row_begin != 0) return declined(PGH_GNN_DECLINED, "pgh_graph_transposed: not on a slice of a row partition");
+    if (g->rowptr == nullptr || g->col == nullptr || g->val == nullptr) return declined(PGH_GNN_DECLINED, "pgh_graph_transposed: the graph keeps no CSR image");
+    if (!g->bsf.enabled) return declined(PGH_GNN_DECLINED, "pgh_graph_transposed: the graph has no blocked layout");
+    if (g->n_rows == 0) return declined(PGH_GNN_DECLINED, "pgh_graph_transposed: an empty graph");
     PGH_TRY(ensure_init());
     Runtime& r = rt();
     const int64_t n = g->n_rows, nnz = g->nnz;
@@ -152,13 +122,13 @@ extern "C" int pgh_graph_transposed(pgh_graph_t g, pgh_graph_t* out) {
             PGH_TRY(temp.alloc(temp_bytes));
             // one stable sort of (column, entry): the entries of a column keep the order of the stored CSR -- ascending rows, the copies of a
             // repeated entry in their order -- which is the order of the transposed CSR's rows
-            k_gnn_iota<<<blocks_of(nnz), WG, 0, r.stream>>>(entry.p, nnz);
+            k_gnn_iota<<<blocks_for(nnz), WG, 0, r.stream>>>(entry.p, nnz);
             PGH_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, temp_bytes, g->col, col_sorted.p, entry.p, entry_sorted.p, (int)nnz, 0, end_bit, r.stream));
-            k_gnn_fill<<<blocks_of(nnz), WG, 0, r.stream>>>(entry_sorted.p, nnz, g->rowptr, n, g->val, value_free ? g->keep_mult : nullptr, t->col, t->val,
+            k_gnn_fill<<<blocks_for(nnz), WG, 0, r.stream>>>(entry_sorted.p, nnz, g->rowptr, n, g->val, value_free ? g->keep_mult : nullptr, t->col, t->val,
                                                            value_free ? mult_t.p : nullptr);
         }
-        k_gnn_ptr<<<blocks_of(nnz + 1), WG, 0, r.stream>>>(col_sorted.p, nnz, n, t->rowptr);
-        k_gnn_row_sums<<<blocks_of(n * 64), WG, 0, r.stream>>>(g->rowptr, g->val, n, t->degrees);
+        k_gnn_ptr<<<blocks_for(nnz + 1), WG, 0, r.stream>>>(col_sorted.p, nnz, n, t->rowptr);
+        k_gnn_row_sums<<<blocks_for(n * 64), WG, 0, r.stream>>>(g->rowptr, g->val, n, t->degrees);
         PGH_HIP(hipGetLastError());
         PGH_HIP(hipStreamSynchronize(r.stream));
         PGH_TRY(finish_graph(t));
@@ -195,11 +165,11 @@ extern "C" int pgh_linear_run_batch(pgh_graph_t g, pgh_mat_t v, double s0, int32
     PGH_CHECK(g && v && out && c && (steps <= 0 || (a && b)), "pgh_linear_run_batch: null argument");
     PGH_CHECK(steps >= 0, "pgh_linear_run_batch: a negative number of steps");
     PGH_CHECK(rate >= 0.0 && rate < 1.0, "pgh_linear_run_batch: the rate must lie in [0, 1)");
-    if (g->n_rows != g->n_cols) return declined("pgh_linear_run_batch: a square matrix only");
-    if (!g->bsf.enabled) return declined("pgh_linear_run_batch: the graph has no blocked layout");
-    if (v->b > kLanes) return declined("pgh_linear_run_batch: at most 64 columns");
+    if (g->n_rows != g->n_cols) return declined(PGH_GNN_DECLINED, "pgh_linear_run_batch: a square matrix only");
+    if (!g->bsf.enabled) return declined(PGH_GNN_DECLINED, "pgh_linear_run_batch: the graph has no blocked layout");
+    if (v->b > kLanes) return declined(PGH_GNN_DECLINED, "pgh_linear_run_batch: at most 64 columns");
     if (rate > 0.0 && g->bsf_mm.mm_edge == nullptr && (g->rowptr == nullptr || g->col == nullptr))
-        return declined("pgh_linear_run_batch: graph_dropout needs the CSR image of the graph");
+        return declined(PGH_GNN_DECLINED, "pgh_linear_run_batch: graph_dropout needs the CSR image of the graph");
     PGH_CHECK(v->n == g->n_cols && out->n == g->n_cols && v->b == out->b && v->b >= 1, "pgh_linear_run_batch: shape mismatch");
     PGH_CHECK(v->data != out->data, "pgh_linear_run_batch: the output aliases the input");
     PGH_CHECK(std::isfinite(s0) && std::isfinite(c[0]), "pgh_linear_run_batch: a non-finite coefficient");
@@ -213,34 +183,30 @@ extern "C" int pgh_linear_run_batch(pgh_graph_t g, pgh_mat_t v, double s0, int32
     const int width = v->b, ld = (width + 3) & ~3, quads = ld / 4;
     const int64_t n_int = f.n_out;
     const size_t bytes = sizeof(float) * (size_t)n_int * ld;
-    Slab v_int, xg, sums, acc;
+    PoolBuf v_int, xg, sums, acc;
     PGH_TRY(v_int.alloc(bytes));
     PGH_TRY(xg.alloc(bytes));
     PGH_TRY(sums.alloc(bytes));
     PGH_TRY(acc.alloc(bytes));
-    Events ev;
-    PGH_HIP(hipEventCreate(&ev.a));
-    PGH_HIP(hipEventCreate(&ev.b));
     const f32x4* rowop = reinterpret_cast<const f32x4*>(f.mm_rowop);
-    const int grid = blocks_of(n_int * quads, 8);
-    PGH_HIP(hipEventRecord(ev.a, r.stream));
+    const int grid = blocks_for(n_int * quads, 8);
+    LoopTimer timer;
+    PGH_TRY(timer.start());
     PGH_HIP(hipMemsetAsync(sums.p, 0, bytes, r.stream));
-    PGH_TRY(mm_slab_in(g, v->data, width, ld, v_int.f()));
-    k_gnn_close<<<grid, WG, 0, r.stream>>>(rowop, sums.q(), v_int.q(), acc.q(), xg.q(), n_int, quads, 0.f, (float)s0, (float)c[0], 1);
+    PGH_TRY(mm_slab_in(g, v->data, width, ld, v_int.as<float>()));
+    k_gnn_close<<<grid, WG, 0, r.stream>>>(rowop, sums.as<f32x4>(), v_int.as<f32x4>(), acc.as<f32x4>(), xg.as<f32x4>(), n_int, quads, 0.f, (float)s0,
+                                           (float)c[0], 1);
     for (int k = 1; k <= steps; ++k) {
         const uint64_t seed = seed_first + (uint64_t)((int64_t)(k - 1) * seed_stride);
-        PGH_TRY(mm_masked_sums(g, xg.f(), ld, width, sums.f(), rate, seed));
-        k_gnn_close<<<grid, WG, 0, r.stream>>>(rowop, sums.q(), v_int.q(), acc.q(), xg.q(), n_int, quads, (float)a[k - 1], (float)b[k - 1], (float)c[k], 0);
+        PGH_TRY(mm_masked_sums(g, xg.as<float>(), ld, width, sums.as<float>(), rate, seed));
+        k_gnn_close<<<grid, WG, 0, r.stream>>>(rowop, sums.as<f32x4>(), v_int.as<f32x4>(), acc.as<f32x4>(), xg.as<f32x4>(), n_int, quads, (float)a[k - 1],
+                                               (float)b[k - 1], (float)c[k], 0);
     }
     PGH_HIP(hipGetLastError());
-    PGH_TRY(mm_slab_out(g, acc.f(), width, ld, out->data));
-    PGH_HIP(hipEventRecord(ev.b, r.stream));
-    PGH_HIP(hipStreamSynchronize(r.stream));
-    if (loop_ms) {
-        float ms = 0.f;
-        PGH_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-        *loop_ms = ms;
-    }
+    PGH_TRY(mm_slab_out(g, acc.as<float>(), width, ld, out->data));
+    double ms = 0.0;
+    PGH_TRY(timer.stop(&ms));                          // (waits for the loop's last launch: the caller's slab is written)
+    if (loop_ms) *loop_ms = ms;
     return 0;
 }
 

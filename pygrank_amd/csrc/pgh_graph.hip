@@ -22,14 +22,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kItemsPerTile = 256 * PGH_IPT;
 
-inline int blocks_for(int64_t n, int cap_mult = 16) {
-    int64_t b = (n + kBlock - 1) / kBlock;
-    const int64_t cap = (int64_t)rt().num_cus * cap_mult;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // row sums of M in f64 (one wavefront per row keeps hub rows parallel) -> f32 degrees
 __global__ void k_row_sums(const int64_t* __restrict__ indptr, const double* __restrict__ data, int64_t n_rows,
                            float* __restrict__ deg) {

@@ -212,14 +212,6 @@ __global__ void k_fill_i32(int32_t* p, int64_t n, int32_t v) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-inline int blocks_for(int64_t n) {
-    int64_t b = (n + kBlock - 1) / kBlock;
-    const int64_t cap = (int64_t)rt().num_cus * 16;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 namespace {

@@ -39,10 +39,7 @@ int lpr_for(int cols) {
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // a refusal: nothing was enqueued, nothing was written
-int declined(int status, const char* who, const std::string& why) {
-    set_error(who + (" declined: " + why));
-    return status;
-}
+int declined(int status, const char* who, const std::string& why) { return declined(status, who + (" declined: " + why)); }
 
 // Behind the loads of an iteration: neither the optimiser nor the scheduler moves a load below this point, so every load is in flight
 // before the first use ("Waits"; without it the compiler sinks each load to its use and waits for them in turn).

@@ -16,6 +16,7 @@
 #include "pgh_batch.h"
 #include "pgh_mixed.h"
 
+#include <functional>
 #include <type_traits>
 #include <vector>
 
@@ -1227,24 +1228,6 @@ __global__ __launch_bounds__(WG) void k_mm_permute_out(const float* __restrict__
     }
 }
 
-inline int blocks_for(int64_t n, int cap_mult = 16) {
-    int64_t blocks = (n + WG - 1) / WG;
-    const int64_t cap = (int64_t)rt().num_cus * cap_mult;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
-struct DevBytes {          // slab work buffers from the runtime's stream-ordered pool (eight 2 GB slabs per 64-seed batch)
-    void* p = nullptr;
-    ~DevBytes() {
-        if (p) pool_free(p);
-    }
-    int alloc(size_t bytes) { return pool_alloc(bytes > 0 ? bytes : 1, &p); }
-    template <typename T>
-    T* as() { return static_cast<T*>(p); }
-};
-
 int ensure_mm_layout(pgh_graph_s* g) {
     if (g->bsf_mm.enabled) return 0;
     PGH_CHECK(g->n_rows == g->n_cols, "the multi-seed path needs a square matrix");
@@ -1304,6 +1287,21 @@ int ensure_mm_edge_ids(pgh_graph_s* g) {
     return 0;
 }
 
+// one launch of the gather pass in its (DROP, SPARSE) form: which = 3 * valued + {0, 1, 2} for 16, 8, 4 lanes per row
+template <bool DROP, bool SPARSE>
+void launch_mm_partial(int which, int grid, const MMView& v, const float* xg, int ld, int b, float* sums, const BatchState* state,
+                       const MMDrop& drop, const SparseGate& sg) {
+    hipStream_t stream = rt().stream;
+    switch (which) {
+        case 0: k_mm_partial<false, 16, DROP, SPARSE><<<grid, WG, 0, stream>>>(v, xg, ld, b, sums, state, drop, sg); break;
+        case 1: k_mm_partial<false, 8, DROP, SPARSE><<<grid, WG, 0, stream>>>(v, xg, ld, b, sums, state, drop, sg); break;
+        case 2: k_mm_partial<false, 4, DROP, SPARSE><<<grid, WG, 0, stream>>>(v, xg, ld, b, sums, state, drop, sg); break;
+        case 3: k_mm_partial<true, 16, DROP, SPARSE><<<grid, WG, 0, stream>>>(v, xg, ld, b, sums, state, drop, sg); break;
+        case 4: k_mm_partial<true, 8, DROP, SPARSE><<<grid, WG, 0, stream>>>(v, xg, ld, b, sums, state, drop, sg); break;
+        default: k_mm_partial<true, 4, DROP, SPARSE><<<grid, WG, 0, stream>>>(v, xg, ld, b, sums, state, drop, sg); break;
+    }
+}
+
 int mm_partial(pgh_graph_s* g, const float* xg, int ld, int b, float* sums, const BatchState* state, const MMDrop* drop = nullptr,
                const SparseGate* gate = nullptr) {
     Runtime& r = rt();
@@ -1322,37 +1320,15 @@ int mm_partial(pgh_graph_s* g, const float* xg, int ld, int b, float* sums, cons
         if (per_cu < 1) per_cu = 1;
     }
     const int grid = r.num_cus * per_cu;
-    if (drop != nullptr) {          // graph_dropout: the same shapes with the mask word (the value-free stream gets a factor per entry)
+    {
         ProfScope prof(PGH_K_SPMM);
-        switch (which) {
-            case 0: k_mm_partial<false, 16, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, *drop); break;
-            case 1: k_mm_partial<false, 8, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, *drop); break;
-            case 2: k_mm_partial<false, 4, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, *drop); break;
-            case 3: k_mm_partial<true, 16, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, *drop); break;
-            case 4: k_mm_partial<true, 8, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, *drop); break;
-            default: k_mm_partial<true, 4, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, *drop); break;
-        }
-    } else {
-        // both forms of the pass for every step: each evaluates the gate on the device, the one it does not select returns at once
-        const SparseGate sg = gate != nullptr ? *gate : SparseGate{};
-        ProfScope prof(PGH_K_SPMM);
-        switch (which) {
-            case 0: k_mm_partial<false, 16><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-            case 1: k_mm_partial<false, 8><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-            case 2: k_mm_partial<false, 4><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-            case 3: k_mm_partial<true, 16><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-            case 4: k_mm_partial<true, 8><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-            default: k_mm_partial<true, 4><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-        }
-        if (sg.map != nullptr) {
-            switch (which) {
-                case 0: k_mm_partial<false, 16, false, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-                case 1: k_mm_partial<false, 8, false, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-                case 2: k_mm_partial<false, 4, false, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-                case 3: k_mm_partial<true, 16, false, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-                case 4: k_mm_partial<true, 8, false, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-                default: k_mm_partial<true, 4, false, true><<<grid, WG, 0, r.stream>>>(v, xg, ld, b, sums, state, MMDrop{}, sg); break;
-            }
+        if (drop != nullptr) {      // graph_dropout: the same shapes with the mask word (the value-free stream gets a factor per entry)
+            launch_mm_partial<true, false>(which, grid, v, xg, ld, b, sums, state, *drop, SparseGate{});
+        } else {
+            // both forms of the pass for every step: each evaluates the gate on the device, the one it does not select returns at once
+            const SparseGate sg = gate != nullptr ? *gate : SparseGate{};
+            launch_mm_partial<false, false>(which, grid, v, xg, ld, b, sums, state, MMDrop{}, sg);
+            if (sg.map != nullptr) launch_mm_partial<false, true>(which, grid, v, xg, ld, b, sums, state, MMDrop{}, sg);
         }
     }
     {
@@ -1364,7 +1340,6 @@ int mm_partial(pgh_graph_s* g, const float* xg, int ld, int b, float* sums, cons
 }
 
 int combine_grid() { return rt().num_cus * 8; }
-int cgrid_of() { return combine_grid(); }
 
 }  // namespace
 
@@ -1406,7 +1381,7 @@ int spmm_impl(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y, double rate, uint64_t see
     const BsfFormat& f = g->bsf_mm;
     const int b = x->b, ld = (b + 3) & ~3;
     const int64_t n_int = f.n_out;
-    DevBytes xg, sums, yint, partial;
+    PoolBuf xg, sums, yint, partial;
     PGH_TRY(xg.alloc(sizeof(float) * (size_t)n_int * ld));
     PGH_TRY(sums.alloc(sizeof(float) * (size_t)n_int * ld));
     PGH_TRY(yint.alloc(sizeof(float) * (size_t)n_int * ld));
@@ -1473,6 +1448,173 @@ int poll_ring(PollRing** out) {
     return 0;
 }
 
+// The run switches of the multi-seed loops, read once at the top of a call: not per step, and not once per process
+// (tests/test_gpu_batch_switches.py flips them inside one process).  PGH_MM_WGS, a launch shape, is mm_partial's.
+struct MMSwitches {
+    bool fused = on("PGH_MM_FUSED", true);              // the in-kernel residual of the sum rules
+    bool sparse = on("PGH_MM_SPARSE", true);            // the sparse form of the gather pass while few rows hold a non-zero
+    bool first_pred = on("PGH_MM_FIRST_PRED", true);    // step 1's quotient predicted from sums of the way in
+    bool affine = on("PGH_MM_AFFINE", false);           // StepParams::affine (diagnostic)
+    static bool on(const char* name, bool unset) {
+        const char* v = getenv(name);
+        return v != nullptr ? atoi(v) != 0 : unset;
+    }
+};
+
+// The host side of one multi-seed run ("The host drivers"): the work buffers every loop allocates, in the sizes
+// the loop names; the common start; the poll ring's protocol; the way out.  A loop supplies its argument checks, its first prediction
+// or first term, the launches of one step and its close.
+struct MMRun {
+    pgh_graph_s* const g;
+    const BsfFormat&   f;
+    const f32x4* const rowop;       // the row words of the way in, the steps and the way out
+    const bool         skip_dead;   // rows without entries and without personalization are zero in every iterate: nobody reads or writes them
+    const int          b, ld;
+    const int64_t      n, n_int;
+    const size_t       slab;        // bytes of one [n_int, ld] slab
+    const int64_t      map_len;     // bytes of a row map: whole 64-row chunks (k_mm_step reads a chunk's flags as one line), 16-byte aligned halves
+    const int          cgrid, in_grid;
+    // one more slab (the internal personalization, or the result); the two gather slabs; the plain row sums; per-workgroup partials and
+    // their folds; the BatchState; the factors of the way out; bit 0 / 1 of a row: p holds a non-zero / the row has entries; the non-zero
+    // rows of the gather slabs and their counts; the zero row.  The order is part of the speed: the pool hands equal-sized blocks out in
+    // the order they came back, so the order in which these go back decides which block serves which slab in the next call (a
+    // scale-23 call ran 1 % slower with the slabs in another order, profiles/mm_loops/README.md).
+    PoolBuf     extra, xg0, xg1, sums, partial, folded, state_mem, factors, row_flags, nz_maps, nz_counts, zero_row;
+    LoopTimer   timer;
+    PollRing*   ring = nullptr;
+    BatchState* state = nullptr;
+    float*      buf[2] = {nullptr, nullptr};
+    double*     fold = nullptr;
+    int*        in_part = nullptr;  // [2][in_grid * 4] the way in's per-wavefront counts, behind the loop's own count words
+
+    MMRun(pgh_graph_s* graph, int width, const f32x4* row_words, bool skip)
+        : g(graph), f(graph->bsf_mm), rowop(row_words), skip_dead(skip), b(width), ld((width + 3) & ~3), n(graph->n_cols), n_int(f.n_out),
+          slab(sizeof(float) * (size_t)n_int * ld), map_len((n_int + 63) / 64 * 64 + 64), cgrid(combine_grid()),
+          in_grid(blocks_for(n_int * lanes_per_row(ld))) {}
+
+    // maps: row maps of the gather slabs; own_counts: count words of the loop in front of the way in's; partial_rows x cgrid x 64
+    // doubles of workgroup partials; fold_rows x 64 folded doubles
+    int alloc(int maps, int own_counts, int partial_rows, int fold_rows) {
+        PGH_TRY(zero_row.alloc(sizeof(float) * (size_t)(ld + 4)));
+        PGH_TRY(row_flags.alloc((size_t)map_len));
+        PGH_TRY(nz_maps.alloc((size_t)maps * map_len));
+        PGH_TRY(nz_counts.alloc(sizeof(int) * (size_t)(own_counts + 2 * in_grid * (WG / 64))));
+        PGH_TRY(extra.alloc(slab));
+        PGH_TRY(xg0.alloc(slab));
+        PGH_TRY(xg1.alloc(slab));
+        PGH_TRY(sums.alloc(slab));
+        PGH_TRY(partial.alloc(sizeof(double) * (size_t)partial_rows * cgrid * kLanes));
+        PGH_TRY(folded.alloc(sizeof(double) * (size_t)fold_rows * kLanes));
+        PGH_TRY(state_mem.alloc(sizeof(BatchState)));
+        PGH_TRY(factors.alloc(sizeof(double) * kLanes));
+        PGH_TRY(poll_ring(&ring));
+        state = state_mem.as<BatchState>();
+        buf[0] = xg0.as<float>();
+        buf[1] = xg1.as<float>();
+        fold = folded.as<double>();
+        in_part = nz_counts.as<int>() + own_counts;
+        return 0;
+    }
+    // the zero row, the clock, and the structural zeros of the rows without entries when every row is processed
+    int open() {
+        PGH_HIP(hipMemsetAsync(zero_row.p, 0, sizeof(float) * (size_t)(ld + 4), rt().stream));
+        PGH_TRY(timer.start());
+        if (!skip_dead) PGH_HIP(hipMemsetAsync(sums.p, 0, slab, rt().stream));
+        return 0;
+    }
+    void init_state() { k_mm_state_init<<<1, kLanes, 0, rt().stream>>>(state, b); }
+    // The way in: src_p -> the extra slab, src_x -> both gather slabs (in gather form), the row flags, the first map and the counts.
+    // pred_part (or null): per-workgroup partials of the sums the first prediction is made of.
+    void way_in(const float* src_p, const float* src_x, double* pred_part) {
+        PermuteIn2 q{};
+        q.nz_map = nz_maps.as<uint8_t>();
+        q.nz_rows = in_part;
+        q.live_rows = in_part + in_grid * (WG / 64);
+        q.src_p = src_p;
+        q.src_x = src_x;
+        q.out_p = extra.as<float>();
+        q.out_xg0 = buf[0];
+        q.out_xg1 = buf[1];
+        q.rowop = rowop;
+        q.row_flags = row_flags.as<uint8_t>();
+        q.row_has = skip_dead ? f.mm_row_has : nullptr;                       // null: every row counts as holding entries
+        q.pred_part = pred_part;
+        k_mm_permute_in2<<<in_grid, WG, 0, rt().stream>>>(q, f.perm, n_int, n, b, ld);
+    }
+    // behind the close of step k: its outcome into slot k of the ring
+    int publish_poll(int k) {
+        PGH_HIP(hipMemcpyAsync(&ring->host[k % kPollRing], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, rt().stream));
+        PGH_HIP(hipEventRecord(ring->ev[k % kPollRing], rt().stream));
+        return 0;
+    }
+    // The host keeps up to three steps enqueued beyond the last one whose outcome it has seen; launches behind a stop or a pause are
+    // no-ops.  enqueue_step(k) ends in publish_poll(k).  A step that reports a pause ran but for its close, and the steps enqueued behind
+    // it did nothing: on_pause(k) closes it, its outcome comes through slot 0 and the run goes on behind it.  Slot 0 is also the slot
+    // of every step that is a multiple of 8: the wait for the stream, before anything new is enqueued, is what makes that safe.
+    // (on_pause empty: a loop whose kernels never pause.)
+    int run_ahead(int max_steps, const std::function<int(int)>& enqueue_step, const std::function<int(int)>& on_pause = nullptr) {
+        int enq = 0, seen = 0;
+        bool stop = false;
+        while (!stop) {
+            while (enq < max_steps && enq - seen < 3) {
+                PGH_TRY(enqueue_step(enq + 1));
+                ++enq;
+            }
+            if (seen == enq) break;
+            const int k = seen + 1;
+            PGH_HIP(hipEventSynchronize(ring->ev[k % kPollRing]));
+            const BatchPoll poll = ring->host[k % kPollRing];
+            ++seen;
+            if (poll.paused && on_pause) {
+                PGH_TRY(on_pause(k));
+                PGH_HIP(hipMemcpyAsync(&ring->host[0], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, rt().stream));
+                PGH_HIP(hipStreamSynchronize(rt().stream));
+                enq = seen;
+                stop = ring->host[0].all_done != 0;
+            } else if (poll.all_done) {
+                stop = true;
+            }
+        }
+        return 0;
+    }
+    // The way out.  The factors are the columns' output scales, times the state's quotient when state_scale.  result: the slab that
+    // leaves (k_mm_permute_out), or null: the iterate of the last executed step does, out of its gather form (k_mm_permute_out2) -- the
+    // slab row of a column that stopped early was copied forward unchanged by every later executed step.  A column reports
+    // first_iterations + its steps.
+    int finish(bool state_scale, const float* result, const pgh_loop_cfg* cfg, const double* out_scales, float* dst, int first_iterations,
+               int flags, pgh_loop_result* results) {
+        hipStream_t stream = rt().stream;
+        BatchState host_state;
+        PGH_HIP(hipMemcpyAsync(&host_state, state, sizeof(BatchState), hipMemcpyDeviceToHost, stream));
+        PGH_HIP(hipStreamSynchronize(stream));
+        double h_factors[kLanes];
+        for (int j = 0; j < kLanes; ++j)
+            h_factors[j] = j < b ? (state_scale ? host_state.scale[j] : 1.0) * (out_scales ? out_scales[j] : cfg->out_scale) : 1.0;
+        PGH_HIP(hipMemcpyAsync(factors.p, h_factors, sizeof(h_factors), hipMemcpyHostToDevice, stream));
+        const int out_grid = blocks_for(n_int * lanes_per_row(ld));
+        if (result != nullptr) {
+            k_mm_permute_out<<<out_grid, WG, 0, stream>>>(result, f.perm, n_int, n, b, ld, factors.as<double>(), dst);
+        } else {
+            const int executed = host_state.executed;              // steps that ran before every column had stopped
+            k_mm_permute_out2<<<out_grid, WG, 0, stream>>>(buf[executed & 1], rowop, f.perm, n_int, n, b, ld, factors.as<double>(), dst,
+                                                           row_flags.as<uint8_t>());
+        }
+        PGH_HIP(hipGetLastError());
+        double ms = 0.0;
+        PGH_TRY(timer.stop(&ms));
+        for (int j = 0; j < b; ++j) {
+            memset(&results[j], 0, sizeof(pgh_loop_result));
+            results[j].iterations = first_iterations + host_state.steps[j];
+            results[j].converged = host_state.converged[j];
+            results[j].spmv_count = host_state.steps[j];
+            results[j].last_error = host_state.err[j];
+            results[j].loop_ms = ms;
+            results[j].flags = flags;
+        }
+        return 0;
+    }
+};
+
 // walk_rowop (null for PageRank): the row words of an absorbing walk (k_mm_walk_rowops); the step is then k_mm_step<., true> with
 // a = the quotient alone, and the residual comes from the separate kernel (the in-kernel prediction is PageRank's column sums)
 // col_alphas (null for the uniform loops): [b] host, one alpha per column (pgh_ppr_run_batch_mixed): the MIXED forms of the step, its close
@@ -1484,89 +1626,54 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     PGH_CHECK(p->b >= 1 && p->b <= kLanes, std::string(who) + ": the batch width must be in [1, 64]");
     PGH_CHECK(cfg->end_modulo >= 1, "end_modulo must be >= 1");
     PGH_TRY(ensure_mm_layout(g));
+    const MMSwitches sw;
     Runtime& r = rt();
     const BsfFormat& f = g->bsf_mm;
-    const int b = p->b, ld = (b + 3) & ~3;
-    const int64_t n = g->n_cols, n_int = f.n_out;
-    const size_t slab = sizeof(float) * (size_t)n_int * ld;
     const bool walk = walk_rowop != nullptr;
     const f32x4* rowop = walk ? walk_rowop : reinterpret_cast<const f32x4*>(f.mm_rowop);
     const double alpha = walk ? 1.0 : cfg->alpha;                   // a walk's step: a = its quotient
     const bool mixed = col_alphas != nullptr;
     ColAlphas mixed_alphas{};                                       // (lanes beyond b: 0, their columns are frozen from the start)
-    for (int j = 0; mixed && j < b; ++j) mixed_alphas.v[j] = col_alphas[j];
-    DevBytes pint, xg0, xg1, sums, partial, folded, state_mem, factors, row_flags, nz_maps, nz_counts, zero_row;
-    PGH_TRY(zero_row.alloc(sizeof(float) * (size_t)(ld + 4)));
-    PGH_HIP(hipMemsetAsync(zero_row.p, 0, sizeof(float) * (size_t)(ld + 4), r.stream));
-    PGH_TRY(row_flags.alloc((size_t)((n_int + 63) / 64 * 64 + 64)));      // whole 64-row chunks (k_mm_step reads a chunk's flags as one line)
-    // non-zero rows of the two gather slabs (k_mm_partial<SPARSE>): a byte per row, and {rows that hold a non-zero [2], rows in the run}
-    const int64_t map_len = (n_int + 63) / 64 * 64 + 64;         // whole passes of 16 rows, 16-byte aligned halves
-    PGH_TRY(nz_maps.alloc(2 * (size_t)map_len));
-    const int in_grid = blocks_for(n_int * lanes_per_row(ld));
-    PGH_TRY(nz_counts.alloc(sizeof(int) * (size_t)(4 + cgrid_of() + 2 * in_grid * (WG / 64))));
-    uint8_t* nz_map[2] = {nz_maps.as<uint8_t>(), nz_maps.as<uint8_t>() + map_len};
-    int* nz_cnt = nz_counts.as<int>();
-    const bool sparse_gate = rate == 0.0 && !(getenv("PGH_MM_SPARSE") != nullptr && atoi(getenv("PGH_MM_SPARSE")) == 0);
+    for (int j = 0; mixed && j < p->b; ++j) mixed_alphas.v[j] = col_alphas[j];
     // rows without entries and without personalization are zero in every iterate when the loop starts from p (they are then
     // zero in the start iterate too): nobody reads or writes them after the way in
-    const bool skip_dead = cfg->start_from_p != 0 && f.mm_row_has != nullptr;
-    PGH_TRY(pint.alloc(slab));
-    PGH_TRY(xg0.alloc(slab));
-    PGH_TRY(xg1.alloc(slab));
-    PGH_TRY(sums.alloc(slab));
-    const int cgrid = combine_grid();
-    PGH_TRY(partial.alloc(sizeof(double) * 4 * (size_t)cgrid * kLanes));
-    PGH_TRY(folded.alloc(sizeof(double) * 7 * kLanes));                  // S, T, R', D of the step + the separate kernel's residual + the way in's {T0, sum p}
-    PGH_TRY(state_mem.alloc(sizeof(BatchState)));
-    PGH_TRY(factors.alloc(sizeof(double) * kLanes));
-    BatchState* state = state_mem.as<BatchState>();
-    PollRing* ring = nullptr;
-    PGH_TRY(poll_ring(&ring));
-    hipEvent_t ev_a, ev_b;
-    PGH_HIP(hipEventCreate(&ev_a));
-    PGH_HIP(hipEventCreate(&ev_b));
-    PGH_HIP(hipEventRecord(ev_a, r.stream));
-    if (!skip_dead) PGH_HIP(hipMemsetAsync(sums.p, 0, slab, r.stream));      // structural zeros of the rows without entries (every row is processed)
-    // the in-kernel residual: sum rules, the plain matrix (a dropped matrix has other column sums every step), PGH_MM_FUSED=0 turns it off
-    const bool fused_first = (cfg->err_kind == PGH_ERR_L1 || cfg->err_kind == PGH_ERR_MABS) && rate == 0.0 && !walk &&
-                             !(getenv("PGH_MM_FUSED") != nullptr && atoi(getenv("PGH_MM_FUSED")) == 0);
-    bool step1_predicted = false;                // the way in's sums give step 1 its predicted quotient (PGH_MM_FIRST_PRED=0: the separate kernel)
-    k_mm_state_init<<<1, kLanes, 0, r.stream>>>(state, b);
-    PGH_HIP(hipMemsetAsync(nz_maps.p, 0, 2 * (size_t)map_len, r.stream));       // rows nobody ever writes hold zeros: their bytes stay 0
-    PGH_HIP(hipMemsetAsync(nz_counts.p, 0, sizeof(int) * 4, r.stream));
+    MMRun run(g, p->b, rowop, cfg->start_from_p != 0 && f.mm_row_has != nullptr);
+    const int b = run.b, ld = run.ld, cgrid = run.cgrid, in_grid = run.in_grid;
+    const int64_t n = run.n, n_int = run.n_int;
+    // two row maps (k_mm_partial<SPARSE>: a byte per row of either gather slab); count words {rows that hold a non-zero [2], rows in
+    // the run, -} and k_mm_step's per-workgroup counts; S, T, R', D of the step; 7 folds: those four + the separate kernel's residual +
+    // the way in's {T0, sum p}
+    PGH_TRY(run.alloc(2, 4 + cgrid, 4, 7));
+    uint8_t* nz_map[2] = {run.nz_maps.as<uint8_t>(), run.nz_maps.as<uint8_t>() + run.map_len};
+    int* nz_cnt = run.nz_counts.as<int>();
     int* nz_part = nz_cnt + 4;                                           // [cgrid] k_mm_step's per-workgroup counts
-    int* in_part = nz_part + cgrid_of();                                 // [2][in_grid * 4] the way in's per-wavefront counts
-    {
-        PermuteIn2 q{};
-        q.nz_map = nz_map[0];
-        q.nz_rows = in_part;
-        q.live_rows = in_part + in_grid * (WG / 64);
-        q.src_p = p->data;
-        q.src_x = cfg->start_from_p ? p->data : ranks->data;                  // abstract_filters.py:56 without / with warm_start
-        q.out_p = pint.as<float>();
-        q.out_xg0 = xg0.as<float>();
-        q.out_xg1 = xg1.as<float>();
-        q.rowop = rowop;
-        q.row_flags = row_flags.as<uint8_t>();
-        q.row_has = skip_dead ? f.mm_row_has : nullptr;                       // null: every row counts as holding entries
-        // the first step's quotient is predicted from sums of the way in (no separate residual pass for step 1): its per-workgroup
-        // partials borrow the step partials' buffer (2 x in_grid x 64 doubles <= 4 x cgrid x 64 as long as in_grid <= 2 cgrid)
-        const bool first_pred = fused_first && in_grid <= 2 * cgrid && !(getenv("PGH_MM_FIRST_PRED") != nullptr && atoi(getenv("PGH_MM_FIRST_PRED")) == 0);
-        q.pred_part = first_pred ? partial.as<double>() : nullptr;
-        k_mm_permute_in2<<<in_grid, WG, 0, r.stream>>>(q, f.perm, n_int, n, b, ld);
-        k_mm_count_fold<<<1, WG, 0, r.stream>>>(q.nz_rows, q.live_rows, in_grid * (WG / 64), nz_cnt + 0, nz_cnt + 2);
-        if (first_pred) {
-            double* fold0 = folded.as<double>();
-            k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), in_grid, 0, state, fold0 + 5 * kLanes, 0);
-            k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>() + (int64_t)in_grid * kLanes, in_grid, 0, state, fold0 + 6 * kLanes, 0);
-            if (mixed) k_mm_first_pred_mixed<<<1, kLanes, 0, r.stream>>>(state, fold0 + 5 * kLanes, fold0 + 6 * kLanes, mixed_alphas, cfg->use_quotient);
-            else
-            k_mm_first_pred<<<1, kLanes, 0, r.stream>>>(state, fold0 + 5 * kLanes, fold0 + 6 * kLanes, cfg->alpha, cfg->use_quotient);
-        }
-        step1_predicted = first_pred;
+    float* const* buf = run.buf;
+    float* sums = run.sums.as<float>();
+    float* pint = run.extra.as<float>();                                // the personalization in the internal id space
+    double* partial = run.partial.as<double>();
+    double* fold = run.fold;
+    uint8_t* row_flags = run.row_flags.as<uint8_t>();
+    BatchState* state = run.state;
+    const bool sparse_gate = rate == 0.0 && sw.sparse;
+    // the in-kernel residual: sum rules, the plain matrix (a dropped matrix has other column sums every step), PGH_MM_FUSED=0 turns it off
+    const bool fused_first = (cfg->err_kind == PGH_ERR_L1 || cfg->err_kind == PGH_ERR_MABS) && rate == 0.0 && !walk && sw.fused;
+    // the first step's quotient is predicted from sums of the way in (no separate residual pass for step 1; PGH_MM_FIRST_PRED=0: the
+    // separate kernel): its per-workgroup partials borrow the step partials' buffer (2 x in_grid x 64 doubles <= 4 x cgrid x 64 as long
+    // as in_grid <= 2 cgrid)
+    const bool step1_predicted = fused_first && in_grid <= 2 * cgrid && sw.first_pred;
+    PGH_TRY(run.open());
+    run.init_state();
+    PGH_HIP(hipMemsetAsync(run.nz_maps.p, 0, 2 * (size_t)run.map_len, r.stream));    // rows nobody ever writes hold zeros: their bytes stay 0
+    PGH_HIP(hipMemsetAsync(run.nz_counts.p, 0, sizeof(int) * 4, r.stream));
+    run.way_in(p->data, cfg->start_from_p ? p->data : ranks->data, step1_predicted ? partial : nullptr);    // abstract_filters.py:56 without / with warm_start
+    k_mm_count_fold<<<1, WG, 0, r.stream>>>(run.in_part, run.in_part + in_grid * (WG / 64), in_grid * (WG / 64), nz_cnt + 0, nz_cnt + 2);
+    if (step1_predicted) {
+        k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial, in_grid, 0, state, fold + 5 * kLanes, 0);
+        k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial + (int64_t)in_grid * kLanes, in_grid, 0, state, fold + 6 * kLanes, 0);
+        if (mixed) k_mm_first_pred_mixed<<<1, kLanes, 0, r.stream>>>(state, fold + 5 * kLanes, fold + 6 * kLanes, mixed_alphas, cfg->use_quotient);
+        else
+        k_mm_first_pred<<<1, kLanes, 0, r.stream>>>(state, fold + 5 * kLanes, fold + 6 * kLanes, cfg->alpha, cfg->use_quotient);
     }
-    float* buf[2] = {xg0.as<float>(), xg1.as<float>()};
-    double* fold = folded.as<double>();
     const int linf = cfg->err_kind == PGH_ERR_LINF;
     const int max_steps = cfg->max_iters - 1 > 0 ? cfg->max_iters - 1 : 0;
     bool fused = fused_first;
@@ -1577,8 +1684,15 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     cp.n_orig = n;
     cp.use_quotient = cfg->use_quotient;
     cp.err_kind = cfg->err_kind;
-    // the close of a step: the uniform form, or the MIXED one with the columns' alphas behind the same arguments
-    auto launch_close = [&](const CloseParams& c2) {
+    // the close of step k: the uniform form, or the MIXED one with the columns' alphas behind the same arguments
+    auto launch_close = [&](int k, int check, int mode, int resume) {
+        CloseParams c2 = cp;
+        c2.check = check;
+        c2.mode = mode;
+        c2.resume = resume;
+        c2.nz_part = sparse_gate ? nz_part : nullptr;
+        c2.nz_parts = cgrid;
+        c2.nz_total = nz_cnt + (k & 1);
         if (mixed) {
             CloseParamsMixed cm{};
             static_cast<CloseParams&>(cm) = c2;
@@ -1588,24 +1702,17 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
             k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
         }
     };
-    auto check_of = [&](int k) { return loop_checks_at(cfg->err_kind, k + 1, cfg->max_iters, cfg->end_modulo); };
+    auto check_of = [&](int k) { return loop_checks_at(cfg->err_kind, k + 1, cfg->max_iters, cfg->end_modulo) ? 1 : 0; };
     // the separate residual of step k + its close (first step, max rule, dropout, a paused step)
     auto close_plain = [&](int k, int mode, int resume) -> int {
-        const int check = check_of(k) ? 1 : 0;
+        const int check = check_of(k);
         if (check) {
             ProfScope prof(PGH_K_RESIDUAL);
-            k_mm_residual2<<<cgrid, WG, 0, r.stream>>>(buf[k & 1], buf[(k - 1) & 1], rowop, n_int, ld, b, cfg->use_quotient, linf, state, fold,
-                                                       partial.as<double>(), row_flags.as<uint8_t>(), resume);
-            k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, resume);
+            k_mm_residual2<<<cgrid, WG, 0, r.stream>>>(buf[k & 1], buf[(k - 1) & 1], rowop, n_int, ld, b, cfg->use_quotient, linf, state, fold, partial,
+                                                       row_flags, resume);
+            k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial, cgrid, linf, state, fold + 4 * kLanes, resume);
         }
-        CloseParams c2 = cp;
-        c2.check = check;
-        c2.mode = mode;
-        c2.resume = resume;
-        c2.nz_part = sparse_gate ? nz_part : nullptr;
-        c2.nz_parts = cgrid;
-        c2.nz_total = nz_cnt + (k & 1);
-        launch_close(c2);
+        launch_close(k, check, mode, resume);
         PGH_HIP(hipGetLastError());
         return 0;
     };
@@ -1619,13 +1726,13 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
             gate.nz_rows = nz_cnt + ((k - 1) & 1);
             gate.live_rows = nz_cnt + 2;
         }
-        PGH_TRY(mm_partial(g, buf[(k - 1) & 1], ld, b, sums.as<float>(), state, drop, sparse_gate ? &gate : nullptr));
+        PGH_TRY(mm_partial(g, buf[(k - 1) & 1], ld, b, sums, state, drop, sparse_gate ? &gate : nullptr));
         const int mode = (k == 1 && !(fused && step1_predicted)) ? 2 : (fused ? 1 : 0);
         StepParams c{};
-        c.sums = sums.as<float>();
+        c.sums = sums;
         c.rowop = rowop;
-        c.p = pint.as<float>();
-        c.row_flags = row_flags.as<uint8_t>();
+        c.p = pint;
+        c.row_flags = row_flags;
         c.xg_old = buf[(k - 1) & 1];
         c.xg_new = buf[k & 1];
         c.alpha = alpha;
@@ -1634,95 +1741,38 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         c.nz_part = sparse_gate ? nz_part : nullptr;
         c.nz_prev = nz_cnt + ((k - 1) & 1);
         c.live_rows = nz_cnt + 2;
-        c.affine = getenv("PGH_MM_AFFINE") != nullptr && atoi(getenv("PGH_MM_AFFINE")) != 0;
-        c.zero = zero_row.as<float>();
+        c.affine = sw.affine;
+        c.zero = run.zero_row.as<float>();
         {
             ProfScope prof(PGH_K_COMBINE);
             if (mixed) {
                 StepParamsMixed cm{};
                 static_cast<StepParams&>(cm) = c;
                 memcpy(cm.col_alpha, mixed_alphas.v, sizeof(cm.col_alpha));
-                k_mm_step<false, false, true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial.as<double>());
-                if (sparse_gate) k_mm_step<true, false, true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial.as<double>());
+                k_mm_step<false, false, true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial);
+                if (sparse_gate) k_mm_step<true, false, true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial);
             } else if (walk) {
-                k_mm_step<false, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
-                if (sparse_gate) k_mm_step<true, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+                k_mm_step<false, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial);
+                if (sparse_gate) k_mm_step<true, true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial);
             } else {
-                k_mm_step<false><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
-                if (sparse_gate) k_mm_step<true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+                k_mm_step<false><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial);
+                if (sparse_gate) k_mm_step<true><<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial);
             }
         }
-        k_mm_fold4<<<dim3(kLanes, 4), WG, 0, r.stream>>>(partial.as<double>(), cgrid, state, fold);
-        if (mode == 1) {
-            CloseParams c2 = cp;
-            c2.check = check_of(k) ? 1 : 0;
-            c2.mode = 1;
-            c2.nz_part = sparse_gate ? nz_part : nullptr;
-            c2.nz_parts = cgrid;
-            c2.nz_total = nz_cnt + (k & 1);
-            launch_close(c2);
-        } else {
-            PGH_TRY(close_plain(k, mode, 0));
-        }
+        k_mm_fold4<<<dim3(kLanes, 4), WG, 0, r.stream>>>(partial, cgrid, state, fold);
+        if (mode == 1) launch_close(k, check_of(k), 1, 0);
+        else PGH_TRY(close_plain(k, mode, 0));
         PGH_HIP(hipGetLastError());
-        PGH_HIP(hipMemcpyAsync(&ring->host[k % kPollRing], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
-        PGH_HIP(hipEventRecord(ring->ev[k % kPollRing], r.stream));
-        return 0;
+        return run.publish_poll(k);
     };
-    // the host keeps up to three steps enqueued beyond the last one whose outcome it has seen; launches behind a stop or a pause are no-ops
-    int enq = 0, seen = 0;
-    bool stop = false;
-    while (!stop) {
-        while (enq < max_steps && enq - seen < 3) {
-            PGH_TRY(enqueue_step(enq + 1));
-            ++enq;
-        }
-        if (seen == enq) break;
-        const int k = seen + 1;
-        PGH_HIP(hipEventSynchronize(ring->ev[k % kPollRing]));
-        const BatchPoll poll = ring->host[k % kPollRing];
-        ++seen;
-        if (poll.paused) {
-            // step k ran but for its close; the steps enqueued behind it saw the pause and did nothing.  The separate kernel decides, the
-            // run goes on without the fusion (a negative or non-finite value would pause every step)
-            flags |= 1;
-            fused = false;
-            PGH_TRY(close_plain(k, 0, 1));
-            PGH_HIP(hipMemcpyAsync(&ring->host[0], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
-            PGH_HIP(hipStreamSynchronize(r.stream));
-            enq = seen;
-            stop = ring->host[0].all_done != 0;
-        } else if (poll.all_done) {
-            stop = true;
-        }
-    }
-    BatchState host_state;
-    PGH_HIP(hipMemcpyAsync(&host_state, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
-    PGH_HIP(hipStreamSynchronize(r.stream));
-    // the slab row of a column that stopped early was copied forward unchanged by every later executed step
-    double h_factors[kLanes];
-    for (int j = 0; j < kLanes; ++j) h_factors[j] = j < b ? host_state.scale[j] * (out_scales ? out_scales[j] : cfg->out_scale) : 1.0;
-    PGH_HIP(hipMemcpyAsync(factors.p, h_factors, sizeof(h_factors), hipMemcpyHostToDevice, r.stream));
-    const int executed = host_state.executed;              // steps that ran before every column had stopped
-    k_mm_permute_out2<<<blocks_for(n_int * lanes_per_row(ld)), WG, 0, r.stream>>>(buf[executed & 1], rowop, f.perm, n_int, n, b, ld, factors.as<double>(),
-                                                                                    ranks->data, row_flags.as<uint8_t>());
-    PGH_HIP(hipGetLastError());
-    PGH_HIP(hipEventRecord(ev_b, r.stream));
-    PGH_HIP(hipEventSynchronize(ev_b));
-    float ms = 0.f;
-    PGH_HIP(hipEventElapsedTime(&ms, ev_a, ev_b));
-    (void)hipEventDestroy(ev_a);
-    (void)hipEventDestroy(ev_b);
-    for (int j = 0; j < b; ++j) {
-        memset(&results[j], 0, sizeof(pgh_loop_result));
-        results[j].iterations = host_state.steps[j] + 1;
-        results[j].converged = host_state.converged[j];
-        results[j].spmv_count = host_state.steps[j];
-        results[j].last_error = host_state.err[j];
-        results[j].loop_ms = (double)ms;
-        results[j].flags = flags;
-    }
-    return 0;
+    // a paused step: the separate kernel decides, and the run goes on without the fusion (a negative or non-finite value would pause
+    // every step)
+    PGH_TRY(run.run_ahead(max_steps, enqueue_step, [&](int k) -> int {
+        flags |= 1;
+        fused = false;
+        return close_plain(k, 0, 1);
+    }));
+    return run.finish(true, nullptr, cfg, out_scales, ranks->data, 1, flags, results);
 }
 }  // namespace
 
@@ -1731,12 +1781,6 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
 // They reuse the multi-seed layout, the gather pass (mm_partial), the permutes, BatchState and the poll ring of the PageRank batch.
 // =================================================================================================
 namespace {
-
-// an input these loops do not serve: nothing was written, the caller runs the columns one by one
-int declined(const char* msg) {
-    set_error(msg);
-    return PGH_BATCH_DECLINED;
-}
 
 // the row words of an absorbing walk in the multi-seed id space: {u * dst scale, s'', 1 / s'', v} with y = a * u * (M^T x) + v * p,
 // u = deg / (lam + deg), v = lam / (lam + deg).  lam == null: the symmetric walk, lam = (1 + sqrt(1 + 4 deg)) / 2 and the source factor
@@ -1934,8 +1978,8 @@ __global__ __launch_bounds__(WG) void k_mm_poly_step(PolyStepArgs<MIXED> c, int6
 
 int check_batch_shapes(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop_cfg* cfg, const char* who) {
     PGH_CHECK(g && p && out && cfg, std::string(who) + ": null argument");
-    if (g->n_rows != g->n_cols) return declined("the multi-seed loops need a square matrix");
-    if (!g->bsf.enabled) return declined("the multi-seed loops need a graph with the blocked layout");
+    if (g->n_rows != g->n_cols) return declined(PGH_BATCH_DECLINED, "the multi-seed loops need a square matrix");
+    if (!g->bsf.enabled) return declined(PGH_BATCH_DECLINED, "the multi-seed loops need a graph with the blocked layout");
     PGH_CHECK(p->n == g->n_cols && out->n == g->n_cols && p->b == out->b, std::string(who) + ": shape mismatch");
     PGH_CHECK(p->b >= 1 && p->b <= kLanes, std::string(who) + ": the batch width must be in [1, 64]");
     PGH_CHECK(cfg->end_modulo >= 1, "end_modulo must be >= 1");
@@ -1948,7 +1992,7 @@ int walk_batch(pgh_graph_t g, pgh_mat_t p, const float* lam, pgh_mat_t ranks, co
     PGH_TRY(ensure_mm_layout(g));
     const BsfFormat& f = g->bsf_mm;
     const int64_t n_int = f.n_out;
-    DevBytes rowop, bad;
+    PoolBuf rowop, bad;
     PGH_TRY(rowop.alloc(sizeof(f32x4) * (size_t)(n_int > 0 ? n_int : 1)));
     PGH_TRY(bad.alloc(sizeof(int)));
     Runtime& r = rt();
@@ -1959,7 +2003,7 @@ int walk_batch(pgh_graph_t g, pgh_mat_t p, const float* lam, pgh_mat_t ranks, co
     int h_bad = 0;
     PGH_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, r.stream));
     PGH_HIP(hipStreamSynchronize(r.stream));
-    if (h_bad) return declined("a row with absorption + degree == 0 (or a non-finite absorption): the single-vector loop's NaN");
+    if (h_bad) return declined(PGH_BATCH_DECLINED, "a row with absorption + degree == 0 (or a non-finite absorption): the single-vector loop's NaN");
     pgh_loop_cfg from_p = *cfg;
     from_p.start_from_p = 1;                               // ranks are output only
     return batch_impl(g, p, ranks, &from_p, out_scales, 0.0, 0, results, rowop.as<f32x4>());
@@ -2008,63 +2052,32 @@ int poly_batch_impl(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t nu
     }
     PGH_TRY(ensure_mm_layout(g));
     const BsfFormat& f = g->bsf_mm;
-    const int64_t n_int = f.n_out;
-    const size_t slab = sizeof(float) * (size_t)n_int * ld;
     const f32x4* rowop = reinterpret_cast<const f32x4*>(f.mm_rowop);
-    DevBytes res_slab, xg0, xg1, sums, partial, folded, state_mem, factors, row_flags, nz_map, nz_counts, zero_row;
-    PGH_TRY(zero_row.alloc(sizeof(float) * (size_t)(ld + 4)));
-    PGH_HIP(hipMemsetAsync(zero_row.p, 0, sizeof(float) * (size_t)(ld + 4), r.stream));
-    PGH_TRY(row_flags.alloc((size_t)((n_int + 63) / 64 * 64 + 64)));
-    PGH_TRY(nz_map.alloc((size_t)((n_int + 63) / 64 * 64 + 64)));          // (written by the way in; the loop keeps the dense pass)
-    const int in_grid = blocks_for(n_int * lanes_per_row(ld));
-    PGH_TRY(nz_counts.alloc(sizeof(int) * (size_t)(2 * in_grid * (WG / 64))));
-    const bool skip_dead = f.mm_row_has != nullptr;       // every run starts from p: rows without entries and without p stay zero
-    PGH_TRY(res_slab.alloc(slab));
-    PGH_TRY(xg0.alloc(slab));
-    PGH_TRY(xg1.alloc(slab));
-    PGH_TRY(sums.alloc(slab));
-    const int cgrid = combine_grid();
-    PGH_TRY(partial.alloc(sizeof(double) * (size_t)cgrid * kLanes));
-    PGH_TRY(folded.alloc(sizeof(double) * 5 * kLanes));                  // S, T, R', D (zeros: no quotient) + the folded change
-    PGH_TRY(state_mem.alloc(sizeof(BatchState)));
-    PGH_TRY(factors.alloc(sizeof(double) * kLanes));
-    BatchState* state = state_mem.as<BatchState>();
-    double* fold = folded.as<double>();
-    PollRing* ring = nullptr;
-    PGH_TRY(poll_ring(&ring));
-    hipEvent_t ev_a, ev_b;
-    PGH_HIP(hipEventCreate(&ev_a));
-    PGH_HIP(hipEventCreate(&ev_b));
-    PGH_HIP(hipEventRecord(ev_a, r.stream));
-    if (!skip_dead) PGH_HIP(hipMemsetAsync(sums.p, 0, slab, r.stream));
-    PGH_HIP(hipMemsetAsync(folded.p, 0, sizeof(double) * 5 * kLanes, r.stream));
-    k_mm_state_init<<<1, kLanes, 0, r.stream>>>(state, b);
-    {
-        PermuteIn2 q{};
-        q.nz_map = nz_map.as<uint8_t>();
-        q.nz_rows = nz_counts.as<int>();
-        q.live_rows = nz_counts.as<int>() + in_grid * (WG / 64);
-        q.src_p = p->data;
-        q.src_x = p->data;                                 // term_1 = p: the first gather slab
-        q.out_p = res_slab.as<float>();                    // p, turned into result_1 = c_1 p in place below
-        q.out_xg0 = xg0.as<float>();
-        q.out_xg1 = xg1.as<float>();
-        q.rowop = rowop;
-        q.row_flags = row_flags.as<uint8_t>();
-        q.row_has = skip_dead ? f.mm_row_has : nullptr;
-        k_mm_permute_in2<<<in_grid, WG, 0, r.stream>>>(q, f.perm, n_int, n, b, ld);
-    }
+    MMRun run(g, b, rowop, f.mm_row_has != nullptr);       // every run starts from p: rows without entries and without p stay zero
+    const int cgrid = run.cgrid;
+    const int64_t n_int = run.n_int;
+    // one row map (written by the way in; the loop keeps the dense pass), no count words of its own, one row of partials (the change);
+    // 5 folds: S, T, R', D (zeros: no quotient) + the folded change
+    PGH_TRY(run.alloc(1, 0, 1, 5));
+    float* const* buf = run.buf;
+    float* sums = run.sums.as<float>();
+    float* res_slab = run.extra.as<float>();               // p from the way in, turned into result_1 = c_1 p in place below
+    double* partial = run.partial.as<double>();
+    double* fold = run.fold;
+    uint8_t* row_flags = run.row_flags.as<uint8_t>();
+    BatchState* state = run.state;
+    PGH_TRY(run.open());
+    PGH_HIP(hipMemsetAsync(run.folded.p, 0, sizeof(double) * 5 * kLanes, r.stream));
+    run.init_state();
+    run.way_in(p->data, p->data, nullptr);                 // term_1 = p: the first gather slab
     const int linf = cfg->err_kind == PGH_ERR_LINF;
-    if (mixed) k_mm_poly_init<ColCoefs><<<cgrid, WG, 0, r.stream>>>(res_slab.as<float>(), row_flags.as<uint8_t>(), n_int, ld, col_coeffs(1), linf,
-                                                                    partial.as<double>());
+    if (mixed) k_mm_poly_init<ColCoefs><<<cgrid, WG, 0, r.stream>>>(res_slab, row_flags, n_int, ld, col_coeffs(1), linf, partial);
     else
-    k_mm_poly_init<<<cgrid, WG, 0, r.stream>>>(res_slab.as<float>(), row_flags.as<uint8_t>(), n_int, ld, (float)coeff(1), linf,
-                                               partial.as<double>());
-    k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, 0);
+    k_mm_poly_init<<<cgrid, WG, 0, r.stream>>>(res_slab, row_flags, n_int, ld, (float)coeff(1), linf, partial);
+    k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial, cgrid, linf, state, fold + 4 * kLanes, 0);
     const int check2 = loop_checks_at(cfg->err_kind, 2, cfg->max_iters, cfg->end_modulo);
     k_mm_poly_first<<<1, kLanes, 0, r.stream>>>(state, fold + 4 * kLanes, check2, cfg->err_kind, cfg->tol, (long long)n);
     PGH_HIP(hipGetLastError());
-    float* buf[2] = {xg0.as<float>(), xg1.as<float>()};
     const int max_steps = cfg->max_iters - 2 > 0 ? cfg->max_iters - 2 : 0;
     CloseParams cp{};
     cp.tol = cfg->tol;
@@ -2074,14 +2087,14 @@ int poly_batch_impl(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t nu
     cp.mode = 0;
     // step k runs iteration k + 1; its check is the one of iteration k + 2
     auto enqueue_step = [&](int k) -> int {
-        PGH_TRY(mm_partial(g, buf[(k - 1) & 1], ld, b, sums.as<float>(), state));
+        PGH_TRY(mm_partial(g, buf[(k - 1) & 1], ld, b, sums, state));
         PolyStepParams c{};
-        c.sums = sums.as<float>();
+        c.sums = sums;
         c.rowop = rowop;
-        c.row_flags = row_flags.as<uint8_t>();
-        c.result = res_slab.as<float>();
+        c.row_flags = row_flags;
+        c.result = res_slab;
         c.xg_new = buf[k & 1];
-        c.zero = zero_row.as<float>();
+        c.zero = run.zero_row.as<float>();
         c.c = mixed ? 0.f : (float)coeff(k + 1);
         c.linf = linf;
         {
@@ -2091,56 +2104,19 @@ int poly_batch_impl(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t nu
                 static_cast<PolyStepParams&>(cm) = c;
                 const ColCoefs cc = col_coeffs(k + 1);
                 memcpy(cm.col_c, cc.v, sizeof(cm.col_c));
-                k_mm_poly_step<true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial.as<double>());
+                k_mm_poly_step<true><<<cgrid, WG, 0, r.stream>>>(cm, n_int, ld, b, state, partial);
             } else
-            k_mm_poly_step<<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial.as<double>());
+            k_mm_poly_step<<<cgrid, WG, 0, r.stream>>>(c, n_int, ld, b, state, partial);
         }
-        const int it = k + 2;
         CloseParams c2 = cp;
-        c2.check = loop_checks_at(cfg->err_kind, it, cfg->max_iters, cfg->end_modulo);
-        if (c2.check) k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial.as<double>(), cgrid, linf, state, fold + 4 * kLanes, 0);
+        c2.check = loop_checks_at(cfg->err_kind, k + 2, cfg->max_iters, cfg->end_modulo);
+        if (c2.check) k_mm_fold1<<<kLanes, WG, 0, r.stream>>>(partial, cgrid, linf, state, fold + 4 * kLanes, 0);
         k_mm_close2<<<1, kLanes, 0, r.stream>>>(state, fold, fold + 4 * kLanes, c2);
         PGH_HIP(hipGetLastError());
-        PGH_HIP(hipMemcpyAsync(&ring->host[k % kPollRing], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
-        PGH_HIP(hipEventRecord(ring->ev[k % kPollRing], r.stream));
-        return 0;
+        return run.publish_poll(k);
     };
-    // up to three steps enqueued beyond the last one whose outcome the host has seen (launches behind the stop are no-ops)
-    int enq = 0, seen = 0;
-    for (;;) {
-        while (enq < max_steps && enq - seen < 3) {
-            PGH_TRY(enqueue_step(enq + 1));
-            ++enq;
-        }
-        if (seen == enq) break;
-        const int k = seen + 1;
-        PGH_HIP(hipEventSynchronize(ring->ev[k % kPollRing]));
-        ++seen;
-        if (ring->host[k % kPollRing].all_done) break;
-    }
-    BatchState host_state;
-    PGH_HIP(hipMemcpyAsync(&host_state, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
-    PGH_HIP(hipStreamSynchronize(r.stream));
-    double h_factors[kLanes];
-    for (int j = 0; j < kLanes; ++j) h_factors[j] = j < b ? (out_scales ? out_scales[j] : cfg->out_scale) : 1.0;
-    PGH_HIP(hipMemcpyAsync(factors.p, h_factors, sizeof(h_factors), hipMemcpyHostToDevice, r.stream));
-    k_mm_permute_out<<<blocks_for(n_int * lanes_per_row(ld)), WG, 0, r.stream>>>(res_slab.as<float>(), f.perm, n_int, n, b, ld,
-                                                                                 factors.as<double>(), result->data);
-    PGH_HIP(hipGetLastError());
-    PGH_HIP(hipEventRecord(ev_b, r.stream));
-    PGH_HIP(hipEventSynchronize(ev_b));
-    float ms = 0.f;
-    PGH_HIP(hipEventElapsedTime(&ms, ev_a, ev_b));
-    (void)hipEventDestroy(ev_a);
-    (void)hipEventDestroy(ev_b);
-    for (int j = 0; j < b; ++j) {
-        results[j].iterations = 2 + host_state.steps[j];
-        results[j].converged = host_state.converged[j];
-        results[j].spmv_count = host_state.steps[j];
-        results[j].last_error = host_state.err[j];
-        results[j].loop_ms = (double)ms;
-    }
-    return 0;
+    PGH_TRY(run.run_ahead(max_steps, enqueue_step));        // (these kernels never pause)
+    return run.finish(false, res_slab, cfg, out_scales, result->data, 2, 0, results);
 }
 }  // namespace
 

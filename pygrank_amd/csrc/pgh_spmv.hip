@@ -1886,28 +1886,6 @@ int close_step(const PendingClose& pc, bool defer, bool as_record = true) {
     return 0;
 }
 
-struct LoopTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~LoopTimer() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    int start() {
-        PGH_HIP(hipEventCreate(&a));
-        PGH_HIP(hipEventCreate(&b));
-        PGH_HIP(hipEventRecord(a, rt().stream));
-        return 0;
-    }
-    int stop(double* ms) {
-        PGH_HIP(hipEventRecord(b, rt().stream));
-        PGH_HIP(hipEventSynchronize(b));
-        float f = 0.f;
-        PGH_HIP(hipEventElapsedTime(&f, a, b));
-        *ms = (double)f;
-        return 0;
-    }
-};
-
 // Vectors of a loop in the graph's internal id space.  Row-major graphs: internal == caller space (no copies).
 // Blocked graphs: relabelled + padded; `bring` copies a caller vector in, `take_back` writes the result out.
 struct InternalSpace {
