@@ -27,8 +27,9 @@ from pygrank_amd.measures import (AM, AUC, GM, L1, L2, MSQ, MSQRT, NDCG, Accurac
                                   MaxDifference, MeasureCombination, MKLDivergence, Modularity, Parity, PearsonCorrelation, PPV, RMabs,
                                   SpearmanCorrelation, Supervised, TNR, TPR, Unsupervised, pRule, split)
 from pygrank_amd.convergence import ConvergenceManager
-from pygrank_amd.postprocess import (LinearSweep, Normalize, Ordinals, Postprocessor, Sweep, Tautology, Threshold, Top,
-                                     Transformer)
+from pygrank_amd.postprocess import (LinearSweep, MabsMaintain, Normalize, Ordinals, Postprocessor, SeparateNormalization, Sequential,
+                                     Sweep, Tautology, Threshold, Top, Transformer)
+from pygrank_amd.subgraph import Subgraph, Supergraph
 from pygrank_amd.filters import (AbsorbingWalks, ClosedFormGraphFilter, GenericGraphFilter, GraphFilter, HeatKernel,
                                  ImpulseGraphFilter, LFPR, LowPassRecursiveGraphFilter, PageRank, PageRankClosed,
                                  RecursiveGraphFilter, SymmetricAbsorbingRandomWalks)

@@ -333,6 +333,21 @@ GNN_SIGNATURES = {
     "pgh_mat_wrap": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(c_mat)]),
 }
 
+# include/pgh_select.h.  Unfused route: top / nonzero / Subgraph / Supergraph work with numpy on the downloaded values, MabsMaintain and
+# SeparateNormalization transform the columns of the inner ranker's batch one by one.
+SELECT_SIGNATURES = {
+    "pgh_vec_select": (C.c_int, [c_vec, C.c_int32, C.c_double, C.c_int64, c_i32p, c_vec, c_i64p]),
+    "pgh_vec_gather": (C.c_int, [c_vec, c_i32p, C.c_int64, c_vec]),
+    "pgh_vec_scatter": (C.c_int, [c_vec, c_i32p, C.c_int64, c_vec]),
+    "pgh_mat_topk": (C.c_int, [c_mat, C.c_int64, c_i32p, c_f64p]),
+    "pgh_mat_col_scale": (C.c_int, [c_mat, c_f64p, c_mat]),
+    "pgh_mat_split_sums": (C.c_int, [c_mat, c_vec, c_f64p]),
+    "pgh_mat_split_blend": (C.c_int, [c_mat, c_vec, c_f64p, c_f64p, c_mat]),
+}
+SELECT_NONZERO, SELECT_GT, SELECT_GE = 0, 1, 2                                     # include/pgh_select.h PGH_SELECT_*
+TOPK_MAX_K = 4096         # include/pgh_select.h PGH_TOPK_MAX_K
+SELECT_MAX_COLS = 64      # include/pgh_select.h PGH_SELECT_MAX_COLS
+
 # header -> its table: every optional entry family; the names are distinct across the tables and from SIGNATURES
 OPTIONAL = {
     "pgh_batch.h": BATCH_SIGNATURES, "pgh_tune.h": TUNE_SIGNATURES, "pgh_measure.h": MEASURE_SIGNATURES,
@@ -342,8 +357,9 @@ OPTIONAL = {
     "pgh_post.h": POST_SIGNATURES,
 }
 # ... and every header entry() serves: OPTIONAL -- the thirteen families whose number and 41 names tests/test_fused_plumbing.py pins --
-# and the headers added since, which tests of their own enumerate (include/pgh_gnn.h: tests/test_gnn_host.py)
-TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES})
+# and the headers added since, which tests of their own enumerate (include/pgh_gnn.h: tests/test_gnn_host.py; include/pgh_select.h:
+# tests/test_subgraph_host.py)
+TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES, "pgh_select.h": SELECT_SIGNATURES})
 _HEADER_OF = {name: header for header, table in TABLES.items() for name in table}
 DECLINED = 2              # every optional header's PGH_*_DECLINED: nothing was written, the caller takes its unfused route
 

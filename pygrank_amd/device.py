@@ -288,6 +288,47 @@ class DeviceVector:
         L.check(L.lib().pgh_filter_out(self._h, exclude._h, staging._h, C.byref(count)))
         return staging[0:count.value] if count.value != self._n else staging
 
+    # ------------------------------------------------------------------ selections as lists (include/pgh_select.h).  Each returns None
+    # when the loaded library lacks the entry: the caller works on the downloaded values.
+    def select(self, mode=L.SELECT_NONZERO, cut=0.0, capacity=None):
+        """(positions int32 ascending, their values as a DeviceVector) of the entries that are non-zero (SELECT_NONZERO), > cut
+        (SELECT_GT) or >= cut (SELECT_GE): pgh_vec_select.  Only the positions cross to the host.  A list longer than `capacity`
+        (65536 to begin with) costs a second call."""
+        entry = L.entry("pgh_vec_select")
+        if entry is None:
+            return None
+        capacity = min(self._n, 1 << 16) if capacity is None else min(int(capacity), self._n)
+        count = C.c_int64()
+        while True:
+            positions = np.empty(max(capacity, 1), dtype=np.int32)
+            values = DeviceVector.empty(capacity)
+            L.check(entry(self._h, int(mode), float(cut), capacity, positions.ctypes.data_as(L.c_i32p), values._h, C.byref(count)))
+            if count.value <= capacity:
+                break
+            capacity = count.value
+        found = count.value
+        return positions[:found].copy(), (values if found == capacity else values[0:found])
+
+    def gather(self, positions):
+        """self[positions] for strictly ascending int32 positions, as a DeviceVector (pgh_vec_gather)."""
+        entry = L.entry("pgh_vec_gather")
+        if entry is None:
+            return None
+        positions = np.ascontiguousarray(positions, dtype=np.int32)
+        out = DeviceVector.empty(len(positions))
+        L.check(entry(self._h, positions.ctypes.data_as(L.c_i32p), len(positions), out._h))
+        return out
+
+    def scatter(self, positions, source):
+        """self[positions[t]] = source[t] for strictly ascending int32 positions, in place (pgh_vec_scatter); False without the entry."""
+        entry = L.entry("pgh_vec_scatter")
+        if entry is None:
+            return False
+        positions = np.ascontiguousarray(positions, dtype=np.int32)
+        self._before_write()
+        L.check(entry(self._h, positions.ctypes.data_as(L.c_i32p), len(positions), source._h))
+        return True
+
     def axpby(self, a, other, b):
         """a * self + b * other in one pass."""
         out = DeviceVector.empty(self._n)
@@ -752,6 +793,18 @@ def _all_ones(data):
     return True
 
 
+def host_top(values, k):
+    """(rows int32 [k, b], values [k, b]) of a host array [n, b]: every column's k largest entries, value descending, ties (-0.0 and
+    +0.0 among them) by ascending row -- numpy's restatement of pgh_mat_topk."""
+    values = np.asarray(values)
+    n, b = values.shape
+    rows = np.empty((k, b), dtype=np.int32)
+    places = np.arange(n)
+    for j in range(b):
+        rows[:, j] = np.lexsort((places, -values[:, j]))[:k]
+    return rows, np.take_along_axis(values, rows.astype(np.int64), axis=0)
+
+
 class DeviceMatrix:
     """Row-major f32 [n, b] slab in HBM: the multi-seed batch layout (a gathered row is b*4 contiguous bytes)."""
 
@@ -903,6 +956,50 @@ class DeviceMatrix:
         """DeviceVector.ordinals of every column."""
         out = DeviceMatrix.empty(self.n, self.b)
         return out if self._post("pgh_post_ordinals", out._h) else None
+
+    # ---- include/pgh_select.h: the k best rows of every column, and the slab passes of MabsMaintain and SeparateNormalization (None when
+    # the library lacks the entry or the entry declines)
+    def top(self, k):
+        """(rows int32 [k, b], values f64 [k, b]): the k largest entries of every column, value descending, ties by ascending row.
+        pgh_mat_topk for k <= 4096 (wider slabs in chunks of 64 columns): only the 2 k b results cross to the host.  A larger k, a
+        declined call or a library without the entry downloads the slab and sorts with numpy."""
+        k = int(k)
+        if not 1 <= k <= self.n:
+            raise L.EngineError(f"top: k = {k} lies outside [1, {self.n}]")
+        entry = L.entry("pgh_mat_topk")
+        if entry is not None and k <= L.TOPK_MAX_K:
+            rows, values = np.empty((k, self.b), dtype=np.int32), np.empty((k, self.b), dtype=np.float64)
+            for first, part in self.chunks(L.SELECT_MAX_COLS):
+                r, v = np.empty((k, part.b), dtype=np.int32), np.empty((k, part.b), dtype=np.float64)
+                if not L.accepted(entry(part._h, k, r.ctypes.data_as(L.c_i32p), v.ctypes.data_as(L.c_f64p))):
+                    break
+                rows[:, first:first + part.b], values[:, first:first + part.b] = r, v
+            else:
+                return rows, values
+        return host_top(self.numpy(), k)
+
+    def col_scale(self, factors):
+        """self[:, j] * factors[j] (pgh_mat_col_scale)."""
+        entry = L.entry("pgh_mat_col_scale")
+        factors = np.ascontiguousarray(factors, dtype=np.float64)
+        out = DeviceMatrix.empty(self.n, self.b)
+        return out if entry is not None and L.accepted(entry(self._h, factors.ctypes.data_as(L.c_f64p), out._h)) else None
+
+    def split_sums(self, separator):
+        """[b, 2]: every column's sum of self * separator and of self * (1 - separator), the f32 products added in f64
+        (pgh_mat_split_sums)."""
+        entry = L.entry("pgh_mat_split_sums")
+        out = np.empty((self.b, 2), dtype=np.float64)
+        return out if entry is not None and L.accepted(entry(self._h, separator._h, out.ctypes.data_as(L.c_f64p))) else None
+
+    def split_blend(self, separator, first, second):
+        """self * separator * first[j] + self * (1 - separator) * second[j] (pgh_mat_split_blend)."""
+        entry = L.entry("pgh_mat_split_blend")
+        first, second = np.ascontiguousarray(first, dtype=np.float64), np.ascontiguousarray(second, dtype=np.float64)
+        out = DeviceMatrix.empty(self.n, self.b)
+        done = entry is not None and L.accepted(entry(self._h, separator._h, first.ctypes.data_as(L.c_f64p),
+                                                      second.ctypes.data_as(L.c_f64p), out._h))
+        return out if done else None
 
     def flat(self):
         """The slab's storage as one vector of n * b entries (a view: it keeps the slab alive)."""

@@ -8,8 +8,9 @@ reference's per-node Python dictionaries.  Behaviour follows pygrank/algorithms/
 353-450.  ``propagate`` keeps the inner ranker's batch: the inner ``propagate`` runs once and its [n, b] slab goes through the
 passes of include/pgh_post.h (a multi-column radix select for ``Top``, one slab pass each for the others), so a
 chain such as ``PageRank() >> Sweep() >> Normalize() >> Top(10)`` stays on the device between the multi-seed loop and the measures'
-``evaluate_many``.  The fairness postprocessors are in pygrank_amd/fairness.py, the seed oversampling ones in pygrank_amd/oversampling.py;
-subgraph extraction stays out of scope."""
+``evaluate_many``.  ``MabsMaintain`` / ``Sequential`` / ``SeparateNormalization`` follow postprocess.py:83-103,461-503; the first and the
+last have slab forms on the passes of include/pgh_select.h.  The fairness postprocessors are in
+pygrank_amd/fairness.py, the seed oversampling ones in pygrank_amd/oversampling.py, ``Subgraph`` / ``Supergraph`` in pygrank_amd/subgraph.py."""
 from pygrank_amd import _lib as L
 from pygrank_amd import backend
 from pygrank_amd.device import DeviceMatrix, DeviceVector
@@ -53,6 +54,7 @@ class Postprocessor(NodeRanking):
     batch = True
     fused = True
     _slab = None        # (self, graph, chunk, calls) -> the transformed [n, b <= 64] slab, or None when the engine does not serve it
+    _needs = tuple(L.POST_SIGNATURES)      # the optional entries the slab form calls
 
     def __init__(self, ranker=None):
         self.ranker = ranker
@@ -76,7 +78,7 @@ class Postprocessor(NodeRanking):
         plain = graph.graph if isinstance(graph, GraphSignal) else graph
         # (a keyword that _transform has a parameter for would reach it through _apply: the columns route lets it)
         reaching = len(leftover) - len(remove_used_args(self._transform, leftover))
-        served = all(L.entry(name) is not None for name in L.POST_SIGNATURES)      # (a library has all of the header or none)
+        served = all(L.entry(name) is not None for name in self._needs)          # (a library has all of a header or none)
         if self.fused and served and isinstance(inner, DeviceMatrix) and inner.n > 0 and not reaching:
             widths = [min(CHUNK, inner.b - first) for first in range(0, inner.b, CHUNK)]
             out = DeviceMatrix.empty(inner.n, inner.b) if inner.b > CHUNK else None
@@ -367,3 +369,119 @@ class LinearSweep(_UniformBaseline):
 
     def _slab(self, graph, chunk, calls):
         return self._row_slab(graph, chunk, calls, L.POST_ROW_SUB)
+
+
+class MabsMaintain(Postprocessor):
+    """Rescales the ranks so that the sum of their absolute values is that of the personalization (postprocess.py:83-103); a zero
+    personalization leaves them as they are.
+
+    ``propagate`` runs the inner ``propagate`` once, takes every column's sum |features| and sum |ranks| (pgh_mat_col_abssum) and rescales
+    the slab in one pass (pgh_mat_col_scale, include/pgh_select.h): route "slab".  ``fused = False``, a library without the entry or a
+    column whose ranks sum to zero rescales the inner batch's columns one by one ("columns"); ``batch = False`` is one ``rank()`` per
+    column ("ranks")."""
+
+    _needs = ("pgh_mat_col_scale",)
+
+    def __init__(self, ranker=None):
+        super().__init__(Tautology() if ranker is None else ranker)
+
+    def rank(self, graph=None, personalization=None, *args, **kwargs):
+        personalization = to_signal(graph, personalization)
+        norm = backend.sum(backend.abs(personalization.np))
+        ranks = self.ranker(graph, personalization, *args, **kwargs)
+        if norm != 0:
+            ranks.np = ranks.np * norm / backend.sum(backend.abs(ranks.np))
+        return ranks
+
+    def _slab(self, norms, chunk, calls):
+        """chunk * (norm / sum |chunk|) per column: the one f32 product ``ranks * norm / total`` stores."""
+        totals = chunk.col_abssum()
+        calls.add("pgh_mat_col_abssum")
+        if any(total == 0 and norm != 0 for norm, total in zip(norms, totals)):
+            return None
+        out = chunk.col_scale([norm * (1.0 / total) if norm != 0 else 1.0 for norm, total in zip(norms, totals)])
+        if out is not None:
+            calls.add("pgh_mat_col_scale")
+        return out
+
+    def propagate(self, graph, features, *args, **kwargs):
+        calls = _Calls()
+        self.last_propagate = dict(route="ranks", chunks=[], calls=calls)
+        if not self.batch or not self._has_slab_form():
+            return NodeRanking.propagate(self, graph, features, *args, **kwargs)
+        F = _as_slab(features)
+        inner = self.ranker.propagate(graph, F, *args, **kwargs)
+        norms = F.col_abssum()
+        served = all(L.entry(name) is not None for name in self._needs)
+        if self.fused and served and isinstance(inner, DeviceMatrix) and inner.n > 0:
+            calls.add("pgh_mat_col_abssum")
+            widths = [min(CHUNK, inner.b - first) for first in range(0, inner.b, CHUNK)]
+            out = DeviceMatrix.empty(inner.n, inner.b) if inner.b > CHUNK else None
+            for first, chunk in inner.chunks(CHUNK):
+                done = self._slab(norms[first:first + chunk.b], chunk, calls)
+                if done is None:
+                    break
+                if out is None:
+                    out = done
+                else:
+                    out.set_cols(first, done)
+            else:
+                self.last_propagate.update(route="slab", chunks=widths)
+                return out
+            calls.clear()
+        self.last_propagate.update(route="columns", chunks=[inner.b] if isinstance(inner, DeviceMatrix) else [])
+        columns = [column * norm / backend.sum(backend.abs(column)) if norm != 0 else column
+                   for norm, column in zip(norms, backend.separate_cols(inner))]
+        return backend.combine_cols(columns)
+
+    def _reference(self):
+        return "mabs preservation"
+
+
+class Sequential(Postprocessor):
+    """Passes the outcome of its first ranker through the others, each called on the signal as it stands (postprocess.py:461-472).  There
+    is no slab form: ``propagate`` is one ``rank()`` per column."""
+
+    def __init__(self, *rankers):
+        super().__init__(rankers[0] if rankers else None)
+        self.rankers = list(rankers)
+
+    def _transform(self, ranks, **kwargs):
+        for ranker in self.rankers:
+            if ranker is not self.ranker:
+                ranks = ranker(ranks)
+        return ranks
+
+
+class SeparateNormalization(Postprocessor):
+    """Normalises two groups of nodes apart: with a separator s in [0, 1] the ranks become r s / sum(r s) + r (1 - s) / sum(r (1 - s))
+    (postprocess.py:475-503; a zero sum leaves its part zero).  ``SeparateNormalization(ranker, separator)`` is accepted too.
+
+    The slab form takes every column's two sums from pgh_mat_split_sums and blends in one pass (pgh_mat_split_blend,
+    include/pgh_select.h)."""
+
+    _needs = ("pgh_mat_split_sums", "pgh_mat_split_blend")
+
+    def __init__(self, separator=None, ranker=None):
+        if isinstance(separator, NodeRanking):
+            separator, ranker = ranker, separator
+        super().__init__(Tautology() if ranker is None else ranker)
+        self.separator = separator
+
+    def _transform(self, ranks, **kwargs):
+        separator = to_signal(ranks, self.separator)
+        first = ranks * separator
+        second = ranks * (1 - separator)
+        return first * backend.safe_div(1., backend.sum(first.np)) + second * backend.safe_div(1., backend.sum(second.np))
+
+    def _slab(self, graph, chunk, calls):
+        separator = _device(to_signal(graph, self.separator))
+        sums = chunk.split_sums(separator)
+        if sums is None:
+            return None
+        calls.add("pgh_mat_split_sums")
+        out = chunk.split_blend(separator, [backend.safe_div(1., float(s)) for s in sums[:, 0]],
+                                [backend.safe_div(1., float(s)) for s in sums[:, 1]])
+        if out is not None:
+            calls.add("pgh_mat_split_blend")
+        return out

@@ -59,6 +59,17 @@ class AdjacencyWrapper:
     def __iter__(self):
         yield from range(self.num_nodes)
 
+    def subgraph(self, positions):
+        """The induced subgraph ``adj[positions][:, positions]`` as an AdjacencyWrapper with the same ``directed``: its nodes are
+        0 .. m - 1 in ascending original order and ``original_nodes`` (int32, ascending) says which node of this graph each one was."""
+        positions = np.unique(np.asarray(positions, dtype=np.int64))
+        if len(positions) and not 0 <= positions[0] <= positions[-1] < self.num_nodes:
+            raise Exception("subgraph: a node lies outside the graph")
+        adj = self.adj if sp.issparse(self.adj) and self.adj.format == "csr" else sp.csr_array(self.adj)
+        sub = AdjacencyWrapper(adj[positions][:, positions], directed=self.directed)
+        sub.original_nodes = positions.astype(np.int32)
+        return sub
+
 
 def _row_sums(M):                                           # numpy.py:76-77
     return np.asarray(M.sum(axis=1)).ravel()

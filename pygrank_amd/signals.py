@@ -77,6 +77,41 @@ class GraphSignal(MutableMapping):
     def __rshift__(self, other):
         return other(self)
 
+    # ---- selections that leave the device as lists (include/pgh_select.h): no download of all n values on the engine route
+    def _nodes_at(self, positions):
+        """The nodes at `positions`, in that order."""
+        if isinstance(self.node2id, _IdentityMap):
+            return [int(position) for position in positions]
+        nodes = [None] * len(self.node2id)
+        for node, position in self.node2id.items():
+            nodes[position] = node
+        return [nodes[int(position)] for position in positions]
+
+    def nonzero(self, fused=True):
+        """(positions int32 ascending, values) of the non-zero scores (a NaN is one, -0.0 is none).  On the engine route `values` is a
+        DeviceVector and only the positions cross to the host; `fused=False`, or a library without pgh_vec_select, takes the host mirror
+        and returns the values as f64."""
+        found = self._np.select() if fused and isinstance(self._np, DeviceVector) else None
+        if found is not None:
+            return found
+        values = self._mirror()
+        positions = np.flatnonzero(values != 0).astype(np.int32)
+        return positions, values[positions]
+
+    def top(self, k, fused=True):
+        """[(node, score)] of the k highest scores, score descending, ties in node order; k is clipped to the number of nodes.  Up to
+        k = 4096 the engine selects and sorts on the device (pgh_mat_topk) and k pairs cross to the host."""
+        from pygrank_amd.device import DeviceMatrix, host_top
+        k = min(int(k), len(self))
+        if k < 1:
+            return []
+        values = self._np
+        if fused and isinstance(values, DeviceVector):
+            rows, scores = DeviceMatrix.from_columns([values]).top(k)
+        else:
+            rows, scores = host_top(self._mirror().reshape(-1, 1), k)
+        return list(zip(self._nodes_at(rows[:, 0]), (float(score) for score in scores[:, 0])))
+
     # ---- mapping protocol
     def _mirror(self):
         if self._host is None:
