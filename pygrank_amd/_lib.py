@@ -348,6 +348,49 @@ SELECT_NONZERO, SELECT_GT, SELECT_GE = 0, 1, 2                                  
 TOPK_MAX_K = 4096         # include/pgh_select.h PGH_TOPK_MAX_K
 SELECT_MAX_COLS = 64      # include/pgh_select.h PGH_SELECT_MAX_COLS
 
+# include/pgh_retire.h.  Unfused route: propagate (and AlgorithmSelection's mixed PageRank group) takes the plain multi-seed entry.
+RETIRE_MAX_STAGES = 8     # include/pgh_retire.h PGH_RETIRE_MAX_STAGES
+RETIRE_NARROWED = 32      # include/pgh_retire.h PGH_RETIRE_NARROWED (a bit of pgh_loop_result::flags)
+
+
+class RetireReport(C.Structure):
+    _fields_ = [("num_stages", C.c_int32), ("reserved", C.c_int32), ("ld", C.c_int32 * RETIRE_MAX_STAGES),
+                ("live", C.c_int32 * RETIRE_MAX_STAGES), ("first_step", C.c_int32 * RETIRE_MAX_STAGES), ("column_steps", C.c_int64)]
+
+
+_RETIRE_TAIL = [c_i32p, C.c_int32, C.POINTER(RetireReport)]      # levels, num_levels, report: behind the plain sibling's arguments
+RETIRE_SIGNATURES = {
+    "pgh_ppr_run_batch_retire": (C.c_int, [c_graph, c_mat, c_mat, C.POINTER(LoopCfg), C.c_void_p, C.POINTER(LoopResult)] + _RETIRE_TAIL),
+    "pgh_ppr_run_batch_mixed_retire": (C.c_int, [c_graph, c_mat, c_mat, C.POINTER(LoopCfg), C.c_void_p, C.c_void_p, C.POINTER(LoopResult)]
+                                       + _RETIRE_TAIL),
+    "pgh_absorb_run_batch_retire": (C.c_int, [c_graph, c_mat, c_vec, c_mat, C.POINTER(LoopCfg), C.c_void_p, C.POINTER(LoopResult)]
+                                    + _RETIRE_TAIL),
+    "pgh_sarw_run_batch_retire": (C.c_int, [c_graph, c_mat, c_mat, C.POINTER(LoopCfg), C.c_void_p, C.POINTER(LoopResult)] + _RETIRE_TAIL),
+}
+
+
+def retire_on(retire):
+    """Whether a ranker's ``retire`` asks for the retiring loops: True or a list of levels (an empty one included: a run that never
+    narrows); False and None do not."""
+    return retire is True or isinstance(retire, (list, tuple))
+
+
+def retire_levels(retire):
+    """(levels, num_levels) of an include/pgh_retire.h call for a ranker's ``retire``: True -> the engine's default levels, a list ->
+    those live-column counts (the engine checks them)."""
+    if retire is True:
+        return None, -1
+    levels = [int(level) for level in retire]
+    return (C.c_int32 * max(len(levels), 1))(*levels), len(levels)
+
+
+def retire_stages(report):
+    """An engine report as the dict ``last_batches`` and ``mixed_calls`` carry under "stages"."""
+    count = report.num_stages
+    return dict(ld=list(report.ld[:count]), live=list(report.live[:count]), first_step=list(report.first_step[:count]),
+                column_steps=int(report.column_steps))
+
+
 # header -> its table: every optional entry family; the names are distinct across the tables and from SIGNATURES
 OPTIONAL = {
     "pgh_batch.h": BATCH_SIGNATURES, "pgh_tune.h": TUNE_SIGNATURES, "pgh_measure.h": MEASURE_SIGNATURES,
@@ -358,8 +401,8 @@ OPTIONAL = {
 }
 # ... and every header entry() serves: OPTIONAL -- the thirteen families whose number and 41 names tests/test_fused_plumbing.py pins --
 # and the headers added since, which tests of their own enumerate (include/pgh_gnn.h: tests/test_gnn_host.py; include/pgh_select.h:
-# tests/test_subgraph_host.py)
-TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES, "pgh_select.h": SELECT_SIGNATURES})
+# tests/test_subgraph_host.py; include/pgh_retire.h: tests/test_retire_host.py)
+TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES, "pgh_select.h": SELECT_SIGNATURES, "pgh_retire.h": RETIRE_SIGNATURES})
 _HEADER_OF = {name: header for header, table in TABLES.items() for name in table}
 DECLINED = 2              # every optional header's PGH_*_DECLINED: nothing was written, the caller takes its unfused route
 

@@ -665,6 +665,10 @@ class AlgorithmSelection(Tuner):
         without the entries, a graph the entries decline -- is ranked exactly as ``batch=False`` ranks everything: one ``rank()`` per
         ranker and split.  The columns of one split are scored together by the measure's ``evaluate_many`` where it has one.
     min_batch_width: the least number of columns (rankers x splits) a group is batched at; None (default): ``MIN_BATCH_WIDTH``.
+    retire: False (default), True or a list of levels, as ``PageRank(retire=)``: the mixed PageRank group retires its converged columns
+        inside the loop (pgh_ppr_run_batch_mixed_retire, include/pgh_retire.h; its columns stop at different steps, one alpha each) and
+        the call's record in ``mixed_calls`` carries the run's report under "stages".  The plain entry where the library lacks that one or
+        it declines.
 
     After a run ``last_selection`` holds ``rankers`` (per ranker: ``values`` per split and the ``route`` taken: "mixed_ppr",
     "mixed_poly" or "single"), ``mixed_calls`` (per engine call: ``kind``, ``width``, the per-column ``iterations`` and the loop's
@@ -677,7 +681,7 @@ class AlgorithmSelection(Tuner):
     MIN_BATCH_WIDTH = 8
 
     def __init__(self, rankers=None, measure=AUC, fraction_of_training=0.9, combined_prediction=True, tuning_backend=None, batch=True,
-                 min_batch_width=None):
+                 min_batch_width=None, retire=False):
         if tuning_backend not in (None, "hip"):
             raise Exception("tuning_backend is None or 'hip': this package drives one engine")
         if rankers is None:
@@ -690,6 +694,7 @@ class AlgorithmSelection(Tuner):
         self.tuning_backend = tuning_backend
         self.batch = batch
         self.min_batch_width = min_batch_width
+        self.retire = retire
         self.last_selection = None
 
     # ---- the batch route -----------------------------------------------------------------------------------------------------------
@@ -722,6 +727,7 @@ class AlgorithmSelection(Tuner):
         """Ranks the (ranker, split) pairs of one group as mixed batches.  columns_of[split] gains (ranker index, ranks vector) pairs;
         returns False (nothing gained) when the entry is missing or declines."""
         from pygrank_amd.device import DeviceMatrix
+        from pygrank_amd.filters import _batch_call
         entry = L.entry("pgh_ppr_run_batch_mixed" if kind == "mixed_ppr" else "pgh_poly_run_batch_mixed")
         if entry is None:
             return False
@@ -743,8 +749,10 @@ class AlgorithmSelection(Tuner):
                 cfg = first._loop_cfg(0.0, bool(first.use_quotient), 1.0)
                 cfg.start_from_p = 1
                 alphas = (C.c_double * slab.b)(*[float(rankers[r].alpha) for r, _ in chunk])
-                status = entry(g._h, P._h, R._h, C.byref(cfg), alphas, scales, results)
+                status, stages = _batch_call(self, entry, "pgh_ppr_run_batch_mixed_retire",
+                                             (g._h, P._h, R._h, C.byref(cfg), alphas, scales, results))
             else:
+                stages = None
                 cfg = first._loop_cfg(0.0, False, 1.0)
                 cfg.start_from_p = 1
                 terms = max(int(first.convergence.max_iters) - 1, 0)
@@ -754,7 +762,8 @@ class AlgorithmSelection(Tuner):
             if status == L.DECLINED and not gained:
                 return False
             L.check(status)
-            calls.append(dict(kind=kind, width=slab.b, iterations=[res.iterations for res in results], loop_ms=results[0].loop_ms))
+            calls.append(dict(kind=kind, width=slab.b, iterations=[res.iterations for res in results], loop_ms=results[0].loop_ms,
+                              **({} if stages is None else dict(stages=stages))))
             for j, ((r, s), res, nrm) in enumerate(zip(chunk, results, norms)):
                 if nrm != 0:
                     rankers[r].convergence.start()

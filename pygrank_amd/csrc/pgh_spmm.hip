@@ -15,6 +15,7 @@
 #include "pgh_kernels.h"
 #include "pgh_batch.h"
 #include "pgh_mixed.h"
+#include "pgh_retire.h"
 
 #include <functional>
 #include <type_traits>
@@ -43,6 +44,7 @@ struct BatchState {
     int    converged[kLanes];
     // the four words the host polls after every step (copied to a pinned ring): every column has stopped / the in-kernel residual
     // of step `steps` could not vouch for its verdict on some column and the step waits for the separate kernel / executed steps
+    // (paused == 2: the step is committed and the run waits to be narrowed, CloseParams::narrow_at)
     int    all_done;
     int    paused;
     int    executed;
@@ -859,6 +861,8 @@ struct CloseParams {
     const int* nz_part;      // [nz_parts] per-workgroup counts of k_mm_step (or null)
     int* nz_total;           // <- their sum
     int nz_parts;
+    int narrow_at;           // a run that retires columns (include/pgh_retire.h): with this many live columns or fewer behind a committed
+                             // close the steps enqueued behind it do nothing (state->paused = 2) and the host narrows the run; 0: never
 };
 struct CloseParamsMixed : CloseParams {                     // pgh_ppr_run_batch_mixed: the lane's own alpha forms its prediction
     double col_alpha[kLanes];
@@ -923,7 +927,7 @@ __global__ void k_mm_close2(BatchState* __restrict__ state, const double* __rest
     const unsigned long long all = __ballot(done != 0);
     if (lane == 0) {
         state->all_done = (all == ~0ULL) ? 1 : 0;
-        state->paused = 0;
+        state->paused = (all != ~0ULL && 64 - __popcll(all) <= cp.narrow_at) ? 2 : 0;
         state->executed += 1;
     }
     if (cp.nz_part != nullptr) {                           // non-zero rows of the slab this step wrote: the gate of the next gather pass
@@ -1138,6 +1142,124 @@ __global__ __launch_bounds__(WG) void k_mm_permute_out2(const float* __restrict_
             for (int k = 0; k < 4; ++k)
                 if (c4 + k < b) dst[o * b + c4 + k] = v[k];
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// A run that retires its converged columns (include/pgh_retire.h).  Between two steps: the stopped columns leave
+// (k_mm_retire_out), the live ones move into a narrower workspace (k_mm_repack) and the loop state follows them (k_mm_state_narrow).
+//
+// k_mm_permute_out2 for SOME columns of the slab, each to a column of the caller's [n, dst_b] slab: lane j of the slab goes to column
+// cols.dst[j] (-1: stays) times cols.factor[j].  The arithmetic per value is k_mm_permute_out2's.
+struct RetireCols {
+    int   dst[kLanes];
+    float factor[kLanes];
+};
+__global__ __launch_bounds__(WG) void k_mm_retire_out(const float* __restrict__ xg, const f32x4* __restrict__ rowop, const int32_t* __restrict__ perm,
+                                                       int64_t n_int, int64_t n_valid, int ld, RetireCols cols, float* __restrict__ dst, int dst_b,
+                                                       const uint8_t* __restrict__ row_flags) {
+    const int lpr = lanes_per_row(ld), rows_per_wave = 64 / lpr;
+    const int lane = threadIdx.x & 63, l = lane & (lpr - 1), c4 = 4 * l;
+    if (c4 >= ld) return;
+    int to[4];
+    f32x4 factor;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        to[k] = cols.dst[c4 + k];
+        factor[k] = cols.factor[c4 + k];
+        any = any || to[k] >= 0;
+    }
+    if (!any) return;
+    const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + (threadIdx.x >> 6)) * rows_per_wave + lane / lpr;
+    const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
+    for (int64_t r = first; r < n_int; r += stride) {
+        const int64_t o = perm ? perm[r] : (r < n_valid ? r : -1);
+        if (o < 0) continue;
+        const f32x4 v = row_flags[r] == 0 ? f32x4{0.f, 0.f, 0.f, 0.f}
+                                          : (__builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xg + r * ld + c4)) * rowop[r][2]) * factor;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (to[k] >= 0) dst[o * dst_b + to[k]] = v[k];
+    }
+}
+
+// The live columns of a wide workspace into a narrow one: lane i of the narrow slabs is lane src[i] of the wide ones (-1: a padding
+// lane, zeros).  A group of lanes_per_row(ld_w) lanes loads one wide row as float4s, the values change lanes through ds_bpermute and
+// the first ld_n / 4 lanes of the group store the narrow row as float4s.  What the narrow run reads and no step writes is written here,
+// as the way in writes it: every row of the current gather slab; zeros in the rows of the OTHER gather slab whose flags are 0 (no step
+// writes them, every gather may fetch them); the rows of the personalization whose flag says that p holds a non-zero there (the flags
+// stay those of the wide run: a superset).
+struct Repack {
+    const float* p_w;        // [n_int, ld_w] personalization (rows with bit 0 of the flags only)
+    const float* x_w;        // [n_int, ld_w] the gather slab of the last executed step
+    float*       p_n;        // [n_int, ld_n]
+    float*       x_n;        // [n_int, ld_n] the same slab of the narrow pair
+    float*       other_n;    // [n_int, ld_n] the other one
+    const uint8_t* row_flags;
+    int          src[kLanes];
+};
+__global__ __launch_bounds__(WG) void k_mm_repack(Repack q, int64_t n_int, int ld_w, int ld_n) {
+    const int lpr = lanes_per_row(ld_w), rows_per_wave = 64 / lpr;
+    const int lane = threadIdx.x & 63, l = lane & (lpr - 1), c4 = 4 * l;
+    const bool reads = c4 < ld_w, writes = c4 < ld_n;
+    int from[4], part[4];                                  // per value of this lane's narrow float4: the lane that holds it and which of its four
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int s = writes ? q.src[c4 + k] : -1;
+        from[k] = s >= 0 ? (lane & ~(lpr - 1)) + (s >> 2) : lane;
+        part[k] = s >= 0 ? (s & 3) : -1;
+    }
+    // (wave-uniform trip count: every lane of the wavefront takes part in the exchange)
+    const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + (threadIdx.x >> 6)) * rows_per_wave;
+    const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
+    for (int64_t r0 = first; r0 < n_int; r0 += stride) {
+        const int64_t r = r0 + lane / lpr;
+        const bool ok = r < n_int;
+        const int fl = ok ? (int)q.row_flags[r] : 0;
+        const int64_t at = (ok ? r : 0) * ld_w + (reads ? c4 : 0);
+        const f32x4 xv = (ok && reads) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q.x_w + at)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 pv = (ok && reads && (fl & 1)) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q.p_w + at)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 xo, po;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float x0 = __shfl(xv.x, from[k], 64), x1 = __shfl(xv.y, from[k], 64), x2 = __shfl(xv.z, from[k], 64), x3 = __shfl(xv.w, from[k], 64);
+            const float p0 = __shfl(pv.x, from[k], 64), p1 = __shfl(pv.y, from[k], 64), p2 = __shfl(pv.z, from[k], 64), p3 = __shfl(pv.w, from[k], 64);
+            xo[k] = part[k] == 0 ? x0 : (part[k] == 1 ? x1 : (part[k] == 2 ? x2 : (part[k] == 3 ? x3 : 0.f)));
+            po[k] = part[k] == 0 ? p0 : (part[k] == 1 ? p1 : (part[k] == 2 ? p2 : (part[k] == 3 ? p3 : 0.f)));
+        }
+        if (!ok || !writes) continue;
+        const int64_t to = r * ld_n + c4;
+        *reinterpret_cast<f32x4*>(q.x_n + to) = xo;
+        if (fl & 1) *reinterpret_cast<f32x4*>(q.p_n + to) = po;
+        if (fl == 0) *reinterpret_cast<f32x4*>(q.other_n + to) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// the lanes of the loop state follow their columns: lane i <- lane src.v[i] for i < b_new, the lanes beyond are done from the start (as
+// k_mm_state_init leaves them); the word that voided the enqueued steps is cleared
+struct ColMap {
+    int v[kLanes];
+};
+__global__ void k_mm_state_narrow(BatchState* state, ColMap src, int b_new) {
+    const int lane = threadIdx.x;
+    const int s = lane < b_new ? src.v[lane] : -1;
+    const double scale = s >= 0 ? state->scale[s] : 1.0, err = s >= 0 ? state->err[s] : 0.0, sum = s >= 0 ? state->sum[s] : 0.0;
+    const double pred_inv = s >= 0 ? state->pred_inv[s] : 1.0, pred_raw = s >= 0 ? state->pred_raw[s] : 0.0, sum_p = s >= 0 ? state->sum_p[s] : 0.0;
+    const int done = s >= 0 ? state->done[s] : 1, steps = s >= 0 ? state->steps[s] : 0, converged = s >= 0 ? state->converged[s] : 0;
+    __syncthreads();                                       // every lane has read before any lane writes
+    state->scale[lane] = scale;
+    state->err[lane] = err;
+    state->sum[lane] = sum;
+    state->pred_inv[lane] = pred_inv;
+    state->pred_raw[lane] = pred_raw;
+    state->sum_p[lane] = sum_p;
+    state->done[lane] = done;
+    state->steps[lane] = steps;
+    state->converged[lane] = converged;
+    if (lane == 0) {
+        state->paused = 0;
+        state->b = b_new;
     }
 }
 
@@ -1361,9 +1483,10 @@ int make_drop(pgh_graph_s* g, double rate, uint64_t seed, MMDrop* out, const MMD
     return 0;
 }
 int spmm_impl(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y, double rate, uint64_t seed);
+struct RetirePlan;
 int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, double rate, uint64_t seed0,
                pgh_loop_result* results, const f32x4* walk_rowop = nullptr, const double* col_alphas = nullptr,
-               const char* who = "pgh_ppr_run_batch");
+               const char* who = "pgh_ppr_run_batch", RetirePlan* retire = nullptr);
 }  // namespace
 
 extern "C" int pgh_spmm(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y) { return spmm_impl(g, x, y, 0.0, 0); }
@@ -1552,7 +1675,11 @@ struct MMRun {
     // it did nothing: on_pause(k) closes it, its outcome comes through slot 0 and the run goes on behind it.  Slot 0 is also the slot
     // of every step that is a multiple of 8: the wait for the stream, before anything new is enqueued, is what makes that safe.
     // (on_pause empty: a loop whose kernels never pause.)
-    int run_ahead(int max_steps, const std::function<int(int)>& enqueue_step, const std::function<int(int)>& on_pause = nullptr) {
+    // A step that reports the narrowing word (paused == 2, CloseParams::narrow_at) is committed and the steps enqueued behind it did
+    // nothing either: on_narrow(k) moves the run into its narrower workspace, waits for the stream and clears the word, and the run goes
+    // on behind step k.  The close that answers a pause may raise the word as well: a narrowing follows a committed close only.
+    int run_ahead(int max_steps, const std::function<int(int)>& enqueue_step, const std::function<int(int)>& on_pause = nullptr,
+                  const std::function<int(int)>& on_narrow = nullptr) {
         int enq = 0, seen = 0;
         bool stop = false;
         while (!stop) {
@@ -1565,12 +1692,16 @@ struct MMRun {
             PGH_HIP(hipEventSynchronize(ring->ev[k % kPollRing]));
             const BatchPoll poll = ring->host[k % kPollRing];
             ++seen;
-            if (poll.paused && on_pause) {
+            if (poll.paused == 2 && on_narrow) {
+                PGH_TRY(on_narrow(k));
+                enq = seen;
+            } else if (poll.paused && on_pause) {
                 PGH_TRY(on_pause(k));
                 PGH_HIP(hipMemcpyAsync(&ring->host[0], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, rt().stream));
                 PGH_HIP(hipStreamSynchronize(rt().stream));
                 enq = seen;
                 stop = ring->host[0].all_done != 0;
+                if (!stop && ring->host[0].paused == 2 && on_narrow) PGH_TRY(on_narrow(k));
             } else if (poll.all_done) {
                 stop = true;
             }
@@ -1615,12 +1746,51 @@ struct MMRun {
     }
 };
 
+// The host's record of a run that retires its columns (include/pgh_retire.h): the levels, and the report as it grows.
+struct RetirePlan {
+    std::vector<int>  levels;        // strictly descending
+    pgh_retire_report report{};
+    // the live count at or below which a slab of width ld narrows (0: never): the greatest level below ld, and a narrower slab results
+    int trigger(int ld, int stages) const {
+        if (stages >= PGH_RETIRE_MAX_STAGES) return 0;
+        for (int level : levels)
+            if (level < ld) return level < ld - 4 ? level : ld - 4;
+        return 0;
+    }
+    void stage(int ld, int live, int first_step) {
+        const int s = report.num_stages;
+        if (s > 0) report.column_steps += (int64_t)report.ld[s - 1] * (first_step - report.first_step[s - 1]);
+        report.ld[s] = ld;
+        report.live[s] = live;
+        report.first_step[s] = first_step;
+        report.num_stages = s + 1;
+    }
+    void close(int executed) {
+        const int s = report.num_stages - 1;
+        report.column_steps += (int64_t)report.ld[s] * (executed + 1 - report.first_step[s]);
+    }
+};
+// null levels (num_levels != 0): {32, 16, 8, 4}
+int make_retire_plan(const int32_t* levels, int32_t num_levels, const char* who, RetirePlan* plan) {
+    if (levels == nullptr && num_levels != 0) {
+        plan->levels = {32, 16, 8, 4};
+        return 0;
+    }
+    PGH_CHECK(num_levels >= 0 && num_levels < kLanes, std::string(who) + ": the number of levels must be in [0, 63]");
+    for (int i = 0; i < num_levels; ++i) {
+        PGH_CHECK(levels[i] >= 1 && levels[i] < kLanes && (i == 0 || levels[i] < levels[i - 1]),
+                  std::string(who) + ": the levels must be strictly descending live-column counts in [1, 63]");
+        plan->levels.push_back(levels[i]);
+    }
+    return 0;
+}
+
 // walk_rowop (null for PageRank): the row words of an absorbing walk (k_mm_walk_rowops); the step is then k_mm_step<., true> with
 // a = the quotient alone, and the residual comes from the separate kernel (the in-kernel prediction is PageRank's column sums)
 // col_alphas (null for the uniform loops): [b] host, one alpha per column (pgh_ppr_run_batch_mixed): the MIXED forms of the step, its close
 // and the first prediction run instead of the uniform ones, everything else is shared
 int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, double rate, uint64_t seed0,
-               pgh_loop_result* results, const f32x4* walk_rowop, const double* col_alphas, const char* who) {
+               pgh_loop_result* results, const f32x4* walk_rowop, const double* col_alphas, const char* who, RetirePlan* retire) {
     PGH_CHECK(g && p && ranks && cfg && results, std::string(who) + ": null argument");
     PGH_CHECK(g->n_rows == g->n_cols && p->n == g->n_cols && ranks->n == g->n_cols && p->b == ranks->b, std::string(who) + ": shape mismatch");
     PGH_CHECK(p->b >= 1 && p->b <= kLanes, std::string(who) + ": the batch width must be in [1, 64]");
@@ -1638,7 +1808,8 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     // rows without entries and without personalization are zero in every iterate when the loop starts from p (they are then
     // zero in the start iterate too): nobody reads or writes them after the way in
     MMRun run(g, p->b, rowop, cfg->start_from_p != 0 && f.mm_row_has != nullptr);
-    const int b = run.b, ld = run.ld, cgrid = run.cgrid, in_grid = run.in_grid;
+    int b = run.b, ld = run.ld;                                     // (a run that retires columns narrows them, see `narrow` below)
+    const int cgrid = run.cgrid, in_grid = run.in_grid;
     const int64_t n = run.n, n_int = run.n_int;
     // two row maps (k_mm_partial<SPARSE>: a byte per row of either gather slab); count words {rows that hold a non-zero [2], rows in
     // the run, -} and k_mm_step's per-workgroup counts; S, T, R', D of the step; 7 folds: those four + the separate kernel's residual +
@@ -1654,6 +1825,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     double* fold = run.fold;
     uint8_t* row_flags = run.row_flags.as<uint8_t>();
     BatchState* state = run.state;
+    int narrow_at = retire != nullptr ? retire->trigger(ld, 1) : 0;     // CloseParams::narrow_at of the stage
     const bool sparse_gate = rate == 0.0 && sw.sparse;
     // the in-kernel residual: sum rules, the plain matrix (a dropped matrix has other column sums every step), PGH_MM_FUSED=0 turns it off
     const bool fused_first = (cfg->err_kind == PGH_ERR_L1 || cfg->err_kind == PGH_ERR_MABS) && rate == 0.0 && !walk && sw.fused;
@@ -1693,6 +1865,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         c2.nz_part = sparse_gate ? nz_part : nullptr;
         c2.nz_parts = cgrid;
         c2.nz_total = nz_cnt + (k & 1);
+        c2.narrow_at = narrow_at;
         if (mixed) {
             CloseParamsMixed cm{};
             static_cast<CloseParams&>(cm) = c2;
@@ -1767,12 +1940,116 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     };
     // a paused step: the separate kernel decides, and the run goes on without the fusion (a negative or non-finite value would pause
     // every step)
-    PGH_TRY(run.run_ahead(max_steps, enqueue_step, [&](int k) -> int {
+    auto on_pause = [&](int k) -> int {
         flags |= 1;
         fused = false;
         return close_plain(k, 0, 1);
-    }));
-    return run.finish(true, nullptr, cfg, out_scales, ranks->data, 1, flags, results);
+    };
+    if (retire == nullptr) {
+        PGH_TRY(run.run_ahead(max_steps, enqueue_step, on_pause));
+        return run.finish(true, nullptr, cfg, out_scales, ranks->data, 1, flags, results);
+    }
+    // A run that retires its columns (include/pgh_retire.h).  col_of[i]: the caller's column in lane i of the current slabs.  A column
+    // leaves once, at the narrowing that follows its stop or at the end, and its part of the loop state is kept for results[].
+    const int width = b;                                             // the caller's row length
+    int col_of[kLanes];
+    for (int j = 0; j < kLanes; ++j) col_of[j] = j < b ? j : -1;
+    BatchState kept{};                                               // lanes indexed by the caller's column
+    PoolBuf wide[4];                                                 // what a narrowing hands back to the pool when this frame ends
+    auto retire_lanes = [&](const BatchState& hs, bool all) {        // the lanes that have stopped (all: every lane) leave from the last iterate
+        RetireCols cols;
+        for (int j = 0; j < kLanes; ++j) {
+            cols.dst[j] = -1;
+            cols.factor[j] = 1.f;
+            if (j >= b || !(all || hs.done[j])) continue;
+            const int c = col_of[j];
+            cols.dst[j] = c;
+            cols.factor[j] = (float)(hs.scale[j] * (out_scales ? out_scales[c] : cfg->out_scale));
+            kept.steps[c] = hs.steps[j];
+            kept.converged[c] = hs.converged[j];
+            kept.err[c] = hs.err[j];
+        }
+        k_mm_retire_out<<<blocks_for(n_int * lanes_per_row(ld)), WG, 0, r.stream>>>(buf[hs.executed & 1], rowop, f.perm, n_int, n, ld, cols,
+                                                                                  ranks->data, width, row_flags);
+    };
+    auto narrow = [&](int k) -> int {
+        BatchState hs;
+        PGH_HIP(hipMemcpyAsync(&hs, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
+        PGH_HIP(hipStreamSynchronize(r.stream));
+        retire_lanes(hs, false);
+        Repack q{};
+        ColMap map{};
+        int nb = 0;
+        for (int j = 0; j < kLanes; ++j) q.src[j] = map.v[j] = -1;
+        for (int j = 0; j < b; ++j)
+            if (!hs.done[j]) q.src[nb] = map.v[nb] = j, ++nb;
+        const int nld = (nb + 3) & ~3;
+        PGH_CHECK(nb >= 1 && nld < ld && hs.executed == k, std::string(who) + ": the loop state does not ask for a narrowing");
+        // the narrow workspace comes from the pool; the wide one goes back with this frame (the stream is still reading it)
+        const size_t slab = sizeof(float) * (size_t)n_int * nld;
+        PoolBuf* mine[4] = {&run.extra, &run.xg0, &run.xg1, &run.sums};
+        for (int i = 0; i < 4; ++i) {
+            if (wide[i].p != nullptr) pool_free(wide[i].p);          // (the stage before: the wait above was behind its last reader)
+            wide[i].p = mine[i]->p;
+            mine[i]->p = nullptr;
+            PGH_TRY(mine[i]->alloc(slab));
+        }
+        float* nbuf[2] = {run.xg0.as<float>(), run.xg1.as<float>()};
+        q.p_w = pint;
+        q.x_w = buf[hs.executed & 1];
+        q.p_n = run.extra.as<float>();
+        q.x_n = nbuf[hs.executed & 1];
+        q.other_n = nbuf[(hs.executed + 1) & 1];
+        q.row_flags = row_flags;
+        k_mm_repack<<<blocks_for(n_int * lanes_per_row(ld)), WG, 0, r.stream>>>(q, n_int, ld, nld);
+        // (every row counts as holding entries without skip_dead: the rows that hold none keep their structural zeros in the sums)
+        if (!run.skip_dead) PGH_HIP(hipMemsetAsync(run.sums.p, 0, slab, r.stream));
+        k_mm_state_narrow<<<1, kLanes, 0, r.stream>>>(state, map, nb);
+        PGH_HIP(hipGetLastError());
+        ColAlphas alphas_now = mixed_alphas;
+        int cols_now[kLanes];
+        memcpy(cols_now, col_of, sizeof(cols_now));
+        for (int j = 0; j < kLanes; ++j) {
+            col_of[j] = j < nb ? cols_now[map.v[j]] : -1;
+            mixed_alphas.v[j] = (mixed && j < nb) ? alphas_now.v[map.v[j]] : 0.0;
+        }
+        retire->stage(nld, nb, k + 1);
+        run.buf[0] = nbuf[0];
+        run.buf[1] = nbuf[1];
+        pint = run.extra.as<float>();
+        sums = run.sums.as<float>();
+        b = nb;
+        ld = nld;
+        narrow_at = retire->trigger(ld, retire->report.num_stages);
+        return 0;
+    };
+    retire->stage(ld, b, 1);
+    PGH_TRY(run.run_ahead(max_steps, enqueue_step, on_pause, narrow));
+    if (retire->report.num_stages == 1) {                            // never narrowed: the plain way out
+        PGH_TRY(run.finish(true, nullptr, cfg, out_scales, ranks->data, 1, flags, results));
+        int executed = 0;
+        for (int j = 0; j < b; ++j) executed = results[j].spmv_count > executed ? results[j].spmv_count : executed;
+        retire->close(executed);
+        return 0;
+    }
+    BatchState hs;
+    PGH_HIP(hipMemcpyAsync(&hs, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
+    PGH_HIP(hipStreamSynchronize(r.stream));
+    retire_lanes(hs, true);
+    PGH_HIP(hipGetLastError());
+    double ms = 0.0;
+    PGH_TRY(run.timer.stop(&ms));
+    retire->close(hs.executed);
+    for (int j = 0; j < width; ++j) {
+        memset(&results[j], 0, sizeof(pgh_loop_result));
+        results[j].iterations = 1 + kept.steps[j];
+        results[j].converged = kept.converged[j];
+        results[j].spmv_count = kept.steps[j];
+        results[j].last_error = kept.err[j];
+        results[j].loop_ms = ms;
+        results[j].flags = flags | PGH_RETIRE_NARROWED;
+    }
+    return 0;
 }
 }  // namespace
 
@@ -1987,7 +2264,7 @@ int check_batch_shapes(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop
 }
 
 int walk_batch(pgh_graph_t g, pgh_mat_t p, const float* lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
-               pgh_loop_result* results) {
+               pgh_loop_result* results, const char* who = "pgh_ppr_run_batch", RetirePlan* retire = nullptr) {
     PGH_CHECK(g->degrees != nullptr, "the absorbing walks need the graph's degrees");
     PGH_TRY(ensure_mm_layout(g));
     const BsfFormat& f = g->bsf_mm;
@@ -2006,7 +2283,7 @@ int walk_batch(pgh_graph_t g, pgh_mat_t p, const float* lam, pgh_mat_t ranks, co
     if (h_bad) return declined(PGH_BATCH_DECLINED, "a row with absorption + degree == 0 (or a non-finite absorption): the single-vector loop's NaN");
     pgh_loop_cfg from_p = *cfg;
     from_p.start_from_p = 1;                               // ranks are output only
-    return batch_impl(g, p, ranks, &from_p, out_scales, 0.0, 0, results, rowop.as<f32x4>());
+    return batch_impl(g, p, ranks, &from_p, out_scales, 0.0, 0, results, rowop.as<f32x4>(), nullptr, who, retire);
 }
 
 }  // namespace
@@ -2153,6 +2430,60 @@ extern "C" int pgh_poly_run_batch_mixed(pgh_graph_t g, pgh_mat_t p, const double
     PGH_TRY(check_mixed(g, p, result, cfg, num_coeffs == 0 ? (const void*)cfg : (const void*)coeffs, results, "pgh_poly_run_batch_mixed"));
     for (size_t i = 0; i < (size_t)num_coeffs * p->b; ++i) PGH_CHECK(std::isfinite(coeffs[i]), "pgh_poly_run_batch_mixed: a non-finite coefficient");
     return poly_batch_impl(g, p, coeffs, num_coeffs, result, cfg, out_scales, results, true);
+}
+
+// =================================================================================================
+// The loops of batch_impl in the mode that retires converged columns (include/pgh_retire.h): the plain sibling's checks, the levels,
+// and the report once the run has ended.  What the sibling declines or does not serve is declined here with nothing written.
+// =================================================================================================
+namespace {
+int retire_report_out(int status, const RetirePlan& plan, pgh_retire_report* report) {
+    if (status == 0 && report != nullptr) *report = plan.report;
+    return status;
+}
+}  // namespace
+
+extern "C" int pgh_ppr_run_batch_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                                        pgh_loop_result* results, const int32_t* levels, int32_t num_levels, pgh_retire_report* report) {
+    const char* who = "pgh_ppr_run_batch_retire";
+    PGH_CHECK(results, std::string(who) + ": null argument");
+    RetirePlan plan;
+    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
+    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
+    return retire_report_out(batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, nullptr, who, &plan), plan, report);
+}
+
+extern "C" int pgh_ppr_run_batch_mixed_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* alphas,
+                                              const double* out_scales, pgh_loop_result* results, const int32_t* levels, int32_t num_levels,
+                                              pgh_retire_report* report) {
+    const char* who = "pgh_ppr_run_batch_mixed_retire";
+    RetirePlan plan;
+    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
+    PGH_TRY(check_mixed(g, p, ranks, cfg, alphas, results, who));
+    for (int j = 0; j < p->b; ++j) PGH_CHECK(std::isfinite(alphas[j]), std::string(who) + ": a non-finite alpha");
+    return retire_report_out(batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, alphas, who, &plan), plan, report);
+}
+
+extern "C" int pgh_absorb_run_batch_retire(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
+                                           const double* out_scales, pgh_loop_result* results, const int32_t* levels, int32_t num_levels,
+                                           pgh_retire_report* report) {
+    const char* who = "pgh_absorb_run_batch_retire";
+    PGH_CHECK(results && lam, std::string(who) + ": null argument");
+    RetirePlan plan;
+    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
+    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
+    PGH_CHECK(lam->n == g->n_cols, std::string(who) + ": absorption length mismatch");
+    return retire_report_out(walk_batch(g, p, lam->data, ranks, cfg, out_scales, results, who, &plan), plan, report);
+}
+
+extern "C" int pgh_sarw_run_batch_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                                         pgh_loop_result* results, const int32_t* levels, int32_t num_levels, pgh_retire_report* report) {
+    const char* who = "pgh_sarw_run_batch_retire";
+    PGH_CHECK(results, std::string(who) + ": null argument");
+    RetirePlan plan;
+    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
+    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
+    return retire_report_out(walk_batch(g, p, nullptr, ranks, cfg, out_scales, results, who, &plan), plan, report);
 }
 
 // =================================================================================================

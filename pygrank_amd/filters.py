@@ -39,11 +39,33 @@ def _f64_image_usable(g):
     return g is not None and g.shape[0] == g.shape[1] and g.shape[0] > 0 and g.nnz > 0 and "row-major" not in g.format()
 
 
+def _batch_call(ranker, plain, retiring, args):
+    """One multi-seed call of propagate: through `plain(*args)`, or -- when ``ranker.retire`` asks for it -- through the entry
+    `retiring` of include/pgh_retire.h, which takes the same arguments with the levels and a report behind them and retires converged
+    columns inside the loop.  A library without that entry takes the plain call, and so does a call the entry DECLINED.  Returns
+    (status, the report as ``_lib.retire_stages`` gives it, or None after a plain call)."""
+    entry = L.entry(retiring) if L.retire_on(getattr(ranker, "retire", False)) else None
+    if entry is not None:
+        levels, count = L.retire_levels(ranker.retire)
+        report = L.RetireReport()
+        status = entry(*args, levels, count, C.byref(report))
+        if status != L.DECLINED:
+            return status, (L.retire_stages(report) if status == 0 else None)
+    return plain(*args), None
+
+
+def _batch_info(results, stages):
+    """The per-column records of one chunk in ``last_batches``; a run of include/pgh_retire.h adds its report under "stages"."""
+    extra = {} if stages is None else dict(stages=stages)
+    return [dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms, flags=r.flags, **extra)
+            for r in results]
+
+
 def _propagate_in_batches(ranker, features, cfg, run):
     """signals.py:225-226 (one rank() per feature column) as multi-seed device loops of up to 64 columns with the prologue of
     PageRank.propagate: per-column L1 norms (abstract_filters.py:52-55; zero columns stay zero), preserve_norm factors, the loop
-    started from p (:56), ConvergenceManager's verdict per non-zero column.  run(P, R, cfg_ref, scales, results) -> status of one
-    include/pgh_batch.h call.  Returns the [n, B] ranks, or None when the engine declined the first chunk (nothing was run)."""
+    started from p (:56), ConvergenceManager's verdict per non-zero column.  run(P, R, cfg_ref, scales, results) -> what _batch_call
+    returns for one include/pgh_batch.h call.  Returns the [n, B] ranks, or None when the engine declined the first chunk (nothing was run)."""
     from pygrank_amd.device import DeviceMatrix
     F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
     if not isinstance(F, DeviceMatrix):
@@ -58,13 +80,11 @@ def _propagate_in_batches(ranker, features, cfg, run):
         results = (L.LoopResult * chunk.b)()
         scales = (C.c_double * chunk.b)(*[(float(nrm) if ranker.preserve_norm else 1.0) for nrm in norms])
         ranker.convergence.start()
-        status = run(P, R, C.byref(cfg), scales, results)
+        status, stages = run(P, R, C.byref(cfg), scales, results)
         if status == L.DECLINED and not batches:
             return None
         L.check(status)
-        batches.append([dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms,
-                             flags=r.flags)
-                        for r in results])
+        batches.append(_batch_info(results, stages))
         ranker.last_batches = batches
         for r, nrm in zip(results, norms):
             if nrm != 0:
@@ -330,12 +350,17 @@ class RecursiveGraphFilter(GraphFilter):
 class PageRank(RecursiveGraphFilter):
     """adhoc.py:9-46: r <- alpha * M^T r + (1 - alpha) * p."""
 
-    def __init__(self, alpha=0.85, *args, dtype=None, **kwargs):
-        """dtype="float64" (an extension of this backend): the loop keeps its iterates, sums, quotient and residual in f64 on the engine's
+    def __init__(self, alpha=0.85, *args, dtype=None, retire=False, **kwargs):
+        """retire (an extension of this backend; also an attribute): True, or a list of strictly descending live-column counts below 64
+        (True: 32, 16, 8, 4) -- propagate's multi-seed runs retire their converged columns inside the loop (include/pgh_retire.h) and
+        ``last_batches`` carries the run's report under "stages".  A column of such a run may differ from the plain batch's in its last
+        bits.  graph_dropout takes the plain loop.
+        dtype="float64" (an extension of this backend): the loop keeps its iterates, sums, quotient and residual in f64 on the engine's
         f64 image (pgh_ppr_run_f64) and the tolerance is clamped at fp64 eps like the reference's numpy backend
         (pygrank/core/backend/numpy.py:84-86) instead of fp32 eps -- e.g. tol=1e-9 as in the reference's tests/test_filters.py:189,194.
         An exactness mode (one host look per step); personalization and ranks stay f32 vectors."""
         self.alpha = alpha
+        self.retire = retire
         super().__init__(*args, dtype=dtype, **kwargs)
 
     def _reference(self):
@@ -435,6 +460,7 @@ class PageRank(RecursiveGraphFilter):
             scales = (C.c_double * chunk.b)(*[(float(nrm) if self.preserve_norm else 1.0) for nrm in norms])
             cfg.start_from_p = 1                                                  # ranks start as a copy of p (:56)
             self.convergence.start()
+            stages = None
             if dropout > 0:
                 # graph_dropout(M, rate) of every step (abstract_filters.py:59-62) inside the batch kernel: one mask per step,
                 # seeds reserved up front (the loop stops on the device)
@@ -442,11 +468,10 @@ class PageRank(RecursiveGraphFilter):
                 seed0 = _hip.take_dropout_seeds(max(int(cfg.max_iters), 1))
                 L.check(L.lib().pgh_ppr_run_batch_dropout(g._h, P._h, R._h, C.byref(cfg), scales, dropout, seed0, results))
             else:
-                L.check(L.lib().pgh_ppr_run_batch(g._h, P._h, R._h, C.byref(cfg), scales, results))
-            info = [dict(iterations=r.iterations, converged=bool(r.converged), spmv=r.spmv_count, loop_ms=r.loop_ms,
-                         flags=r.flags)
-                    for r in results]
-            self.last_batches.append(info)
+                status, stages = _batch_call(self, L.lib().pgh_ppr_run_batch, "pgh_ppr_run_batch_retire",
+                                             (g._h, P._h, R._h, C.byref(cfg), scales, results))
+                L.check(status)
+            self.last_batches.append(_batch_info(results, stages))
             for r, nrm in zip(results, norms):
                 if nrm != 0:
                     self.convergence.finish_device_loop(r.iterations, r.converged)   # raises like the per-column run would
@@ -459,9 +484,11 @@ class PageRank(RecursiveGraphFilter):
 class AbsorbingWalks(RecursiveGraphFilter):
     """adhoc.py:125-174: partially absorbing random walks."""
 
-    def __init__(self, alpha=1 - 1.E-6, *args, **kwargs):
+    def __init__(self, alpha=1 - 1.E-6, *args, retire=False, **kwargs):
+        """retire: as PageRank's (propagate's multi-seed runs retire their converged columns inside the loop)."""
         super().__init__(*args, **kwargs)
         self.alpha = alpha
+        self.retire = retire
 
     def _reference(self):
         return f"partially absorbing random walks (absorption scale {(1 - self.alpha) / self.alpha:.3g})"
@@ -504,8 +531,8 @@ class AbsorbingWalks(RecursiveGraphFilter):
             lam = (to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np
             if isinstance(lam, DeviceVector) and len(lam) == g.shape[0]:
                 cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
-                out = _propagate_in_batches(self, features, cfg,
-                                            lambda P, R, cfg_ref, scales, res: entry(g._h, P._h, lam._h, R._h, cfg_ref, scales, res))
+                out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: _batch_call(
+                    self, entry, "pgh_absorb_run_batch_retire", (g._h, P._h, lam._h, R._h, cfg_ref, scales, res)))
                 if out is not None:
                     return out
         return super().propagate(graph, features, *args, **kwargs)
@@ -766,9 +793,11 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
     a = (1 + sqrt(1 + 4 d)) / 2 a step is ``conv(ranks / a, M) * d / (a + d) + personalization * a / (a + d)``
     (``alpha`` is accepted for signature compatibility and, as in the reference, does not enter the formula)."""
 
-    def __init__(self, alpha=0.5, *args, **kwargs):
+    def __init__(self, alpha=0.5, *args, retire=False, **kwargs):
+        """retire: as PageRank's (propagate's multi-seed runs retire their converged columns inside the loop)."""
         super().__init__(*args, **kwargs)
         self.alpha = alpha
+        self.retire = retire
 
     def _reference(self):
         return "symmetric partially absorbing random walks"
@@ -807,8 +836,8 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
         entry = L.entry("pgh_sarw_run_batch") if g is not None else None
         if entry is not None:
             cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
-            out = _propagate_in_batches(self, features, cfg,
-                                        lambda P, R, cfg_ref, scales, res: entry(g._h, P._h, R._h, cfg_ref, scales, res))
+            out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: _batch_call(
+                self, entry, "pgh_sarw_run_batch_retire", (g._h, P._h, R._h, cfg_ref, scales, res)))
             if out is not None:
                 return out
         return super().propagate(graph, features, *args, **kwargs)
@@ -1336,8 +1365,8 @@ class ClosedFormGraphFilter(GraphFilter):
         if entry is not None:
             cfg = self._loop_cfg(0.0, False, 1.0)
             coeffs = np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64)
-            out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: entry(
-                g._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res))
+            out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: (entry(
+                g._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res), None))
             if out is not None:
                 return out
         return super().propagate(graph, features, *args, **kwargs)

@@ -13,7 +13,7 @@ Every figure is the median of --reps (9) runs timed with pgh_timer_* (events on 
 included) in ONE process, the routes alternating, after a warm-up run of each; min..max is the spread.  Needs an MI355X: there is no
 fallback.
 
-    python tools/oversample_bench.py --scale 23 --columns 64 [--objective naive] [--source original] [--out profiles/oversampling/...log]
+    python tools/oversample_bench.py --scale 23 --columns 64 [--objective naive] [--source original] [--retire] [--out profiles/oversampling/...log]
 """
 import argparse
 import json
@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--objective", default="partial", choices=["partial", "naive"])
     ap.add_argument("--source", default="previous", choices=["previous", "original"])
+    ap.add_argument("--retire", action="store_true", help="the inner ranker retires its converged columns (PageRank(retire=True))")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -63,7 +64,7 @@ def main():
     del columns
 
     def boosted(**kwargs):
-        ranker = pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000)
+        ranker = pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000, retire=args.retire)
         return pg.BoostedSeedOversampling(ranker, args.objective, args.source, **kwargs)
 
     def run(**kwargs):
@@ -88,7 +89,7 @@ def main():
     propagate = {name: summary(got) for name, got in samples.items()}
 
     # what a round spends most of its time in: the inner ranker on the seed sets, as one multi-seed run and as a single rank()
-    ranker = pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000)
+    ranker = pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000, retire=args.retire)
     first = pg.to_signal(adj, F.column(0))
     inner_samples = dict(propagate=[], rank=[])
     for rep in range(args.reps + 1):
@@ -126,7 +127,7 @@ def main():
     per_round = {name: {what: summary(got) for what, got in both.items()} for name, both in pass_samples.items()}
 
     out = dict(tool="oversample_bench", scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz), columns=args.columns,
-               seeds=args.seeds, objective=args.objective, source=args.source, reps=args.reps,
+               seeds=args.seeds, objective=args.objective, source=args.source, reps=args.reps, retire=args.retire,
                rounds=dict(min=min(rounds["batch"]), max=max(rounds["batch"]), total=sum(rounds["batch"])), batch_widths=batch_widths,
                ms_per_propagate=propagate,
                batch_over_one_by_one=round(propagate["batch"]["median_ms"] / propagate["one_by_one"]["median_ms"], 4),

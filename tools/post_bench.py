@@ -16,7 +16,7 @@ with pgh_timer_* (events on the engine's stream, host work between the launches 
 after a warm-up run of each; min..max is the spread.  A route counts as faster only when the two min..max intervals are disjoint.
 Needs an MI355X: there is no fallback.
 
-    python tools/post_bench.py --scale 23 --columns 64 --chain top [--k 10] [--out-dir profiles/post]
+    python tools/post_bench.py --scale 23 --columns 64 --chain top [--k 10] [--retire] [--out-dir profiles/post]
 """
 import argparse
 import json
@@ -44,6 +44,7 @@ def main():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--seeds", type=int, default=20)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--retire", action="store_true", help="the inner ranker retires its converged columns (PageRank(retire=True))")
     ap.add_argument("--out-dir", default=None)
     args = ap.parse_args()
     chains = args.chain.split(",")
@@ -67,7 +68,7 @@ def main():
     nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
 
     def ranker():
-        return pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000)
+        return pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000, retire=args.retire)
 
     def make(chain, **switches):
         post = dict(top=lambda: pg.Top(ranker(), args.k), normalize=lambda: pg.Normalize(ranker(), "sum"),
@@ -133,7 +134,7 @@ def main():
             propagate = {name: summary(got) for name, got in samples.items()}
 
             out = dict(tool="post_bench", scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz), columns=width,
-                       chain=chain, k=args.k if chain == "top" else None, seeds=args.seeds, reps=args.reps,
+                       chain=chain, k=args.k if chain == "top" else None, seeds=args.seeds, reps=args.reps, retire=args.retire,
                        slab_calls=dict(posts["slab"].last_propagate["calls"]),
                        ms_per_transform=transform, ms_per_propagate=propagate,
                        transform_slab_over_columns=round(transform["slab"]["median_ms"] / transform["columns"]["median_ms"], 4),
@@ -149,7 +150,7 @@ def main():
             print(line, flush=True)
             if args.out_dir:
                 os.makedirs(args.out_dir, exist_ok=True)
-                with open(os.path.join(args.out_dir, f"post_bench_scale{args.scale}_b{width}_{chain}.log"), "w") as f:
+                with open(os.path.join(args.out_dir, f"post_bench_scale{args.scale}_b{width}_{chain}{'_retire' if args.retire else ''}.log"), "w") as f:
                     f.write(line + "\n")
 
 
