@@ -391,6 +391,17 @@ def retire_stages(report):
                 column_steps=int(report.column_steps))
 
 
+# include/pgh_batch64.h.  Unfused route: a filter whose run wants f64 iterates propagates column by column (the single-vector f64 loops).
+_BATCH64_TAIL = [C.c_void_p, C.POINTER(LoopResult)]              # out_scales, results
+BATCH64_SIGNATURES = {
+    "pgh_spmm_f64": (C.c_int, [c_graph, C.c_void_p, C.c_int32, C.c_void_p]),
+    "pgh_ppr_run_batch_f64": (C.c_int, [c_graph, c_mat, c_mat, C.POINTER(LoopCfg)] + _BATCH64_TAIL + [C.c_void_p]),
+    "pgh_absorb_run_batch_f64": (C.c_int, [c_graph, c_mat, c_vec, c_mat, C.POINTER(LoopCfg)] + _BATCH64_TAIL + [C.c_void_p]),
+    "pgh_sarw_run_batch_f64": (C.c_int, [c_graph, c_mat, c_mat, C.POINTER(LoopCfg)] + _BATCH64_TAIL + [C.c_void_p]),
+    "pgh_poly_run_batch_f64": (C.c_int, [c_graph, c_mat, C.c_void_p, C.c_int32, c_mat, C.POINTER(LoopCfg)] + _BATCH64_TAIL),
+}
+
+
 # header -> its table: every optional entry family; the names are distinct across the tables and from SIGNATURES
 OPTIONAL = {
     "pgh_batch.h": BATCH_SIGNATURES, "pgh_tune.h": TUNE_SIGNATURES, "pgh_measure.h": MEASURE_SIGNATURES,
@@ -401,8 +412,9 @@ OPTIONAL = {
 }
 # ... and every header entry() serves: OPTIONAL -- the thirteen families whose number and 41 names tests/test_fused_plumbing.py pins --
 # and the headers added since, which tests of their own enumerate (include/pgh_gnn.h: tests/test_gnn_host.py; include/pgh_select.h:
-# tests/test_subgraph_host.py; include/pgh_retire.h: tests/test_retire_host.py)
-TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES, "pgh_select.h": SELECT_SIGNATURES, "pgh_retire.h": RETIRE_SIGNATURES})
+# tests/test_subgraph_host.py; include/pgh_retire.h: tests/test_retire_host.py; include/pgh_batch64.h: tests/test_batch64_host.py)
+TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES, "pgh_select.h": SELECT_SIGNATURES, "pgh_retire.h": RETIRE_SIGNATURES,
+                           "pgh_batch64.h": BATCH64_SIGNATURES})
 _HEADER_OF = {name: header for header, table in TABLES.items() for name in table}
 DECLINED = 2              # every optional header's PGH_*_DECLINED: nothing was written, the caller takes its unfused route
 

@@ -16,6 +16,7 @@
 #include "pgh_batch.h"
 #include "pgh_mixed.h"
 #include "pgh_retire.h"
+#include "pgh_mm_run.h"       // BatchState, the poll ring and the run-ahead driver (shared with pgh_spmm64.hip)
 
 #include <functional>
 #include <type_traits>
@@ -28,28 +29,8 @@ namespace {
 #ifndef PGH_MM_UNROLL
 #define PGH_MM_UNROLL 8
 #endif
-constexpr int kLanes = 64;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTileMM = 64 * PGH_BSF_IPT;        // same tile table as the single-vector layout
-
-struct BatchState {
-    double scale[kLanes];        // quotient of the current iterate (1 / sum(y_k); 1 without the quotient)
-    double err[kLanes];
-    double sum[kLanes];
-    double pred_inv[kLanes];     // PREDICTED quotient of the step being written (in-kernel residual, see k_mm_step)
-    double pred_raw[kLanes];     // the uncorrected prediction it came from
-    double sum_p[kLanes];        // sum of the column's personalization (measured by the first step)
-    int    done[kLanes];
-    int    steps[kLanes];
-    int    converged[kLanes];
-    // the four words the host polls after every step (copied to a pinned ring): every column has stopped / the in-kernel residual
-    // of step `steps` could not vouch for its verdict on some column and the step waits for the separate kernel / executed steps
-    // (paused == 2: the step is committed and the run waits to be narrowed, CloseParams::narrow_at)
-    int    all_done;
-    int    paused;
-    int    executed;
-    int    b;
-};
 
 #ifndef PGH_MM_RES_U
 #define PGH_MM_RES_U 8
@@ -1552,25 +1533,6 @@ extern "C" int pgh_ppr_run_batch_dropout(pgh_graph_t g, pgh_mat_t p, pgh_mat_t r
 }
 
 namespace {
-// what the host polls after every step: the tail of BatchState, copied to a pinned ring by the stream (no queue drain per look)
-struct BatchPoll {
-    int all_done, paused, executed, b;
-};
-constexpr int kPollRing = 8;
-struct PollRing {
-    BatchPoll* host = nullptr;       // pinned [kPollRing]
-    hipEvent_t ev[kPollRing] = {nullptr};
-};
-int poll_ring(PollRing** out) {
-    static PollRing ring;
-    if (ring.host == nullptr) {
-        PGH_HIP(hipHostMalloc(reinterpret_cast<void**>(&ring.host), sizeof(BatchPoll) * kPollRing, hipHostMallocDefault));
-        for (int i = 0; i < kPollRing; ++i) PGH_HIP(hipEventCreateWithFlags(&ring.ev[i], hipEventDisableTiming));
-    }
-    *out = &ring;
-    return 0;
-}
-
 // The run switches of the multi-seed loops, read once at the top of a call: not per step, and not once per process
 // (tests/test_gpu_batch_switches.py flips them inside one process).  PGH_MM_WGS, a launch shape, is mm_partial's.
 struct MMSwitches {
@@ -1586,8 +1548,8 @@ struct MMSwitches {
 
 // The host side of one multi-seed run ("The host drivers"): the work buffers every loop allocates, in the sizes
 // the loop names; the common start; the poll ring's protocol; the way out.  A loop supplies its argument checks, its first prediction
-// or first term, the launches of one step and its close.
-struct MMRun {
+// or first term, the launches of one step and its close.  (The protocol itself -- publish_poll, run_ahead -- is MMRunAhead's, pgh_mm_run.h.)
+struct MMRun : MMRunAhead {
     pgh_graph_s* const g;
     const BsfFormat&   f;
     const f32x4* const rowop;       // the row words of the way in, the steps and the way out
@@ -1604,8 +1566,6 @@ struct MMRun {
     // scale-23 call ran 1 % slower with the slabs in another order, profiles/mm_loops/README.md).
     PoolBuf     extra, xg0, xg1, sums, partial, folded, state_mem, factors, row_flags, nz_maps, nz_counts, zero_row;
     LoopTimer   timer;
-    PollRing*   ring = nullptr;
-    BatchState* state = nullptr;
     float*      buf[2] = {nullptr, nullptr};
     double*     fold = nullptr;
     int*        in_part = nullptr;  // [2][in_grid * 4] the way in's per-wavefront counts, behind the loop's own count words
@@ -1663,50 +1623,6 @@ struct MMRun {
         q.row_has = skip_dead ? f.mm_row_has : nullptr;                       // null: every row counts as holding entries
         q.pred_part = pred_part;
         k_mm_permute_in2<<<in_grid, WG, 0, rt().stream>>>(q, f.perm, n_int, n, b, ld);
-    }
-    // behind the close of step k: its outcome into slot k of the ring
-    int publish_poll(int k) {
-        PGH_HIP(hipMemcpyAsync(&ring->host[k % kPollRing], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, rt().stream));
-        PGH_HIP(hipEventRecord(ring->ev[k % kPollRing], rt().stream));
-        return 0;
-    }
-    // The host keeps up to three steps enqueued beyond the last one whose outcome it has seen; launches behind a stop or a pause are
-    // no-ops.  enqueue_step(k) ends in publish_poll(k).  A step that reports a pause ran but for its close, and the steps enqueued behind
-    // it did nothing: on_pause(k) closes it, its outcome comes through slot 0 and the run goes on behind it.  Slot 0 is also the slot
-    // of every step that is a multiple of 8: the wait for the stream, before anything new is enqueued, is what makes that safe.
-    // (on_pause empty: a loop whose kernels never pause.)
-    // A step that reports the narrowing word (paused == 2, CloseParams::narrow_at) is committed and the steps enqueued behind it did
-    // nothing either: on_narrow(k) moves the run into its narrower workspace, waits for the stream and clears the word, and the run goes
-    // on behind step k.  The close that answers a pause may raise the word as well: a narrowing follows a committed close only.
-    int run_ahead(int max_steps, const std::function<int(int)>& enqueue_step, const std::function<int(int)>& on_pause = nullptr,
-                  const std::function<int(int)>& on_narrow = nullptr) {
-        int enq = 0, seen = 0;
-        bool stop = false;
-        while (!stop) {
-            while (enq < max_steps && enq - seen < 3) {
-                PGH_TRY(enqueue_step(enq + 1));
-                ++enq;
-            }
-            if (seen == enq) break;
-            const int k = seen + 1;
-            PGH_HIP(hipEventSynchronize(ring->ev[k % kPollRing]));
-            const BatchPoll poll = ring->host[k % kPollRing];
-            ++seen;
-            if (poll.paused == 2 && on_narrow) {
-                PGH_TRY(on_narrow(k));
-                enq = seen;
-            } else if (poll.paused && on_pause) {
-                PGH_TRY(on_pause(k));
-                PGH_HIP(hipMemcpyAsync(&ring->host[0], &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, rt().stream));
-                PGH_HIP(hipStreamSynchronize(rt().stream));
-                enq = seen;
-                stop = ring->host[0].all_done != 0;
-                if (!stop && ring->host[0].paused == 2 && on_narrow) PGH_TRY(on_narrow(k));
-            } else if (poll.all_done) {
-                stop = true;
-            }
-        }
-        return 0;
     }
     // The way out.  The factors are the columns' output scales, times the state's quotient when state_scale.  result: the slab that
     // leaves (k_mm_permute_out), or null: the iterate of the last executed step does, out of its gather form (k_mm_permute_out2) -- the

@@ -95,6 +95,50 @@ def _propagate_in_batches(ranker, features, cfg, run):
     return out
 
 
+def _propagate_in_batches64(ranker, features, cfg, run, raw):
+    """_propagate_in_batches through an entry of include/pgh_batch64.h (``GraphFilter(f64_batch=True)``): the loop keeps its iterates,
+    sums, quotients and residuals in f64 and the tolerance is clamped at fp64 eps (_f64_cfg).  raw: the chunk goes in UN-normalised
+    with its column norms beside it, as _f64_operands hands a single vector to the f64 route (the recursive filters); otherwise
+    L1-normalised in f32, as the closed-form filters' single rank() does.  run(P, R, cfg_ref, scales, results, norms) -> status.
+    Every record of ``last_batches`` carries "f64": True.  Returns the [n, B] ranks, or None when the engine declined the first chunk
+    (nothing was run)."""
+    from pygrank_amd.device import DeviceMatrix
+    F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
+    if not isinstance(F, DeviceMatrix):
+        F = DeviceMatrix.from_columns([F])
+    cfg = ranker._f64_cfg(cfg)
+    cfg.start_from_p = 1
+    batches = []
+    out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
+    for start, chunk in F.chunks():
+        norms = chunk.col_abssum()
+        P = chunk
+        if not raw:
+            # p * f32(1 / |p|), the bits a single rank() hands its loop (device.py _scalar_factor: a division by a scalar is a
+            # multiplication); a library without the slab form divides (a last bit of p may then differ from the single run's)
+            P = chunk.col_scale([1.0 / nrm if nrm != 0 else 1.0 for nrm in norms])
+            if P is None:
+                P = chunk.div_cols(norms)
+        R = DeviceMatrix.empty(chunk.n, chunk.b)
+        results = (L.LoopResult * chunk.b)()
+        scales = (C.c_double * chunk.b)(*[(float(nrm) if ranker.preserve_norm else 1.0) for nrm in norms])
+        in_norms = (C.c_double * chunk.b)(*[float(nrm) for nrm in norms])
+        ranker.convergence.start()
+        status = run(P, R, C.byref(cfg), scales, results, in_norms)
+        if status == L.DECLINED and not batches:
+            return None
+        L.check(status)
+        batches.append([dict(record, f64=True) for record in _batch_info(results, None)])
+        ranker.last_batches = batches
+        for r, nrm in zip(results, norms):
+            if nrm != 0:
+                ranker.convergence.finish_device_loop(r.iterations, r.converged)   # raises like the per-column run would
+        if out is None:
+            return R
+        out.set_cols(start, R)
+    return out
+
+
 class GraphFilter(NodeRanking):
     """abstract_filters.py:11-106."""
 
@@ -102,14 +146,21 @@ class GraphFilter(NodeRanking):
     _BUILT_FROM_KWARGS = (("preprocessor", default_preprocessor), ("convergence", ConvergenceManager))
 
     def __init__(self, preprocessor=None, convergence=None, personalization_transform=None, preserve_norm=True,
-                 dtype=None, **kwargs):
+                 dtype=None, f64_batch=False, **kwargs):
         """dtype (an extension of this backend; the reference's numpy engine is fp64 throughout, pygrank/core/backend/numpy.py:84-86):
         None -- the engine's f32 loop, and f64 iterates / sums / quotient / residual on the engine's f64 image whenever the tolerance lies
         below fp32 eps (where an f32 loop, clamped at fp32 eps by convergence.py:101, stops early: the reference's AbsorbingWalks default
-        alpha = 1 - 1e-6 with tol = 1e-9 takes 21 iterations, an f32 loop 12); "float32" -- always the f32 loop; "float64" -- always f64."""
+        alpha = 1 - 1e-6 with tol = 1e-9 takes 21 iterations, an f32 loop 12); "float32" -- always the f32 loop; "float64" -- always f64.
+        f64_batch (an extension; also an attribute; off by default): where a run wants f64 iterates and ``propagate`` would otherwise
+        take its f32 multi-seed route, PageRank, AbsorbingWalks, SymmetricAbsorbingRandomWalks and the taylor form of the closed-form
+        filters run chunks of up to 64 columns through the f64 multi-seed loops of include/pgh_batch64.h instead of one f64 loop per
+        column; ``last_batches`` records carry "f64": True.  A column may differ from the column loop's in its last bits (the row sums
+        are grouped differently).  Not served -- today's route: graph_dropout, the "chebyshev" form, warm starts, AlgorithmSelection's
+        mixed groups, LFPR; ``retire=`` is ignored by the f64 batch (a later piece of work)."""
         if dtype not in (None, "float32", "float64"):
             raise Exception("dtype is None (f32, f64 below fp32 eps), 'float32' or 'float64'")
         self.dtype = dtype
+        self.f64_batch = f64_batch
         given = dict(preprocessor=preprocessor, convergence=convergence)
         for attribute, factory in self._BUILT_FROM_KWARGS:
             setattr(self, attribute, given[attribute] if given[attribute] is not None else call(factory, kwargs))
@@ -222,13 +273,15 @@ class GraphFilter(NodeRanking):
     def _prepare_graph(self, graph, *args, **kwargs):
         return graph
 
-    def _batch_graph(self, graph, args, kwargs, allowed=()):
+    def _batch_graph(self, graph, args, kwargs, allowed=(), f64=False):
         """The device graph of a multi-seed loop (include/pgh_batch.h) for propagate(graph, ..., *args, **kwargs), or None where a single
         rank() would not run the f32 fused loop: extra arguments, graph_dropout, f64 iterates (dtype or a tolerance below fp32 eps), a
-        personalization transform, a stopping rule the engine cannot evaluate, a non-square / row-major / empty or non-device graph."""
+        personalization transform, a stopping rule the engine cannot evaluate, a non-square / row-major / empty or non-device graph.
+        f64: the same question for the f64 multi-seed loops (include/pgh_batch64.h) -- the run must WANT f64 iterates and the filter
+        must have been built with f64_batch=True; everything else is judged alike."""
         if args or any(k not in allowed and not (k == "graph_dropout" and not kwargs[k]) for k in kwargs):
             return None
-        if self._loop_cfg() is None or self._f64_wanted():
+        if self._loop_cfg() is None or self._f64_wanted() != f64 or (f64 and not getattr(self, "f64_batch", False)):
             return None
         transform = self.personalization_transform
         if not (isinstance(transform, Tautology) and transform.ranker is None) or type(self)._prepare_graph is not GraphFilter._prepare_graph:
@@ -320,12 +373,12 @@ class RecursiveGraphFilter(GraphFilter):
         return (self.use_quotient is None or isinstance(self.use_quotient, (bool, int))) \
             and not self.converge_to_eigenvectors
 
-    def _walk_batch_graph(self, cls, graph, args, kwargs, allowed=()):
+    def _walk_batch_graph(self, cls, graph, args, kwargs, allowed=(), f64=False):
         """_batch_graph for the walks of class `cls`: also the plain quotient and the class's own formula, step and start."""
         if not self._plain_quotient() or type(self)._formula is not cls._formula or type(self)._step is not RecursiveGraphFilter._step \
                 or type(self)._start is not cls._start:
             return None
-        return self._batch_graph(graph, args, kwargs, allowed)
+        return self._batch_graph(graph, args, kwargs, allowed, f64)
 
     def _run_recursive(self, entry, g, cfg, ranks, *vectors):
         if cfg is None or g is None or g.shape[0] != g.shape[1]:
@@ -431,8 +484,18 @@ class PageRank(RecursiveGraphFilter):
     def propagate(self, graph, features, *args, **kwargs):
         """signals.py:225-226 semantics (one rank() per feature column), run as multi-seed batches of up to 64 columns
         through pgh_ppr_run_batch: the adjacency is streamed once per iteration for the whole batch and every column
-        keeps its own quotient, residual and stopping iteration."""
+        keeps its own quotient, residual and stopping iteration.  With f64_batch=True a run that wants f64 iterates goes through
+        pgh_ppr_run_batch_f64 (include/pgh_batch64.h) the same way; graph_dropout, a library without that entry and a declined call
+        take the route below."""
         from pygrank_amd.device import DeviceMatrix
+        g64 = self._walk_batch_graph(PageRank, graph, args, kwargs, f64=True)
+        entry64 = L.entry("pgh_ppr_run_batch_f64") if g64 is not None else None
+        if entry64 is not None:
+            out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
+                                          lambda P, R, cfg_ref, scales, res, norms: entry64(g64._h, P._h, R._h, cfg_ref, scales, res, norms),
+                                          raw=True)
+            if out is not None:
+                return out
         cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
         dropout = float(kwargs.get("graph_dropout", 0) or 0)
         only_dropout = not kwargs or (set(kwargs) == {"graph_dropout"} and 0 <= dropout < 1)
@@ -524,7 +587,18 @@ class AbsorbingWalks(RecursiveGraphFilter):
     def propagate(self, graph, features, *args, **kwargs):
         """signals.py:225-226 (one rank() per feature column, each with the same `absorption=`) as multi-seed batches of up to 64
         columns through pgh_absorb_run_batch (include/pgh_batch.h) wherever a single rank() would run the f32 loop of pgh_absorb_run;
-        every column keeps its own quotient, residual and stopping iteration.  The column loop otherwise."""
+        every column keeps its own quotient, residual and stopping iteration.  With f64_batch=True a run that wants f64 iterates goes
+        through pgh_absorb_run_batch_f64 (include/pgh_batch64.h) the same way.  The column loop otherwise."""
+        g64 = self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",), f64=True)
+        entry64 = L.entry("pgh_absorb_run_batch_f64") if g64 is not None else None
+        if entry64 is not None:
+            lam = (to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np
+            if isinstance(lam, DeviceVector) and len(lam) == g64.shape[0]:
+                out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
+                                              lambda P, R, cfg_ref, scales, res, norms: entry64(g64._h, P._h, lam._h, R._h, cfg_ref, scales, res,
+                                                                                                norms), raw=True)
+                if out is not None:
+                    return out
         g = self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",))
         entry = L.entry("pgh_absorb_run_batch") if g is not None else None
         if entry is not None:
@@ -831,7 +905,16 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
 
     def propagate(self, graph, features, *args, **kwargs):
         """signals.py:225-226 as multi-seed batches of up to 64 columns through pgh_sarw_run_batch (include/pgh_batch.h) wherever a
-        single rank() would run the f32 loop of pgh_sarw_run; the column loop otherwise."""
+        single rank() would run the f32 loop of pgh_sarw_run; with f64_batch=True a run that wants f64 iterates goes through
+        pgh_sarw_run_batch_f64 (include/pgh_batch64.h) the same way; the column loop otherwise."""
+        g64 = self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs, f64=True)
+        entry64 = L.entry("pgh_sarw_run_batch_f64") if g64 is not None else None
+        if entry64 is not None:
+            out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
+                                          lambda P, R, cfg_ref, scales, res, norms: entry64(g64._h, P._h, R._h, cfg_ref, scales, res, norms),
+                                          raw=True)
+            if out is not None:
+                return out
         g = self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs)
         entry = L.entry("pgh_sarw_run_batch") if g is not None else None
         if entry is not None:
@@ -1354,13 +1437,23 @@ class ClosedFormGraphFilter(GraphFilter):
         """signals.py:225-226 (one rank() per feature column) as multi-seed batches of up to 64 columns through pgh_poly_run_batch
         (include/pgh_batch.h) wherever a single rank() would run the f32 taylor loop of pgh_poly_run: the adjacency is streamed once
         per term for the whole batch and every column stops at its own iteration.  The column loop otherwise (the "chebyshev" form,
-        an optimisation dict, overridden hooks, f64 iterates ...)."""
+        an optimisation dict, overridden hooks, f64 iterates ...).  With f64_batch=True a taylor run that wants f64 iterates goes
+        through pgh_poly_run_batch_f64 (include/pgh_batch64.h) the same way, its personalizations L1-normalised in f32 as a single
+        rank() normalises them."""
         own = ClosedFormGraphFilter
-        g = None
+        g = g64 = None
         if self.coefficient_type == "taylor" and self.optimization_dict is None and self.krylov_dims is None and type(self)._step is own._step \
                 and type(self)._recursion is own._recursion and type(self)._start is own._start \
                 and type(self)._retrieve_power is own._retrieve_power and type(self)._prepare is own._prepare:
-            g = self._batch_graph(graph, args, kwargs)
+            g64 = self._batch_graph(graph, args, kwargs, f64=True)
+            g = self._batch_graph(graph, args, kwargs) if g64 is None else None
+        entry64 = L.entry("pgh_poly_run_batch_f64") if g64 is not None else None
+        if entry64 is not None:
+            coeffs = np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64)
+            out = _propagate_in_batches64(self, features, self._loop_cfg(0.0, False, 1.0), lambda P, R, cfg_ref, scales, res, norms: entry64(
+                g64._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res), raw=False)
+            if out is not None:
+                return out
         entry = L.entry("pgh_poly_run_batch") if g is not None else None
         if entry is not None:
             cfg = self._loop_cfg(0.0, False, 1.0)
