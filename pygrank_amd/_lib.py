@@ -401,6 +401,15 @@ BATCH64_SIGNATURES = {
     "pgh_poly_run_batch_f64": (C.c_int, [c_graph, c_mat, C.c_void_p, C.c_int32, c_mat, C.POINTER(LoopCfg)] + _BATCH64_TAIL),
 }
 
+# include/pgh_retire64.h.  Unfused route: an f64 batch takes the plain entry of include/pgh_batch64.h.  Each loop: its plain f64
+# sibling's arguments, then levels, num_levels, report.
+RETIRE64_SIGNATURES = {
+    "pgh_ppr_run_batch_f64_retire": (C.c_int, BATCH64_SIGNATURES["pgh_ppr_run_batch_f64"][1] + _RETIRE_TAIL),
+    "pgh_absorb_run_batch_f64_retire": (C.c_int, BATCH64_SIGNATURES["pgh_absorb_run_batch_f64"][1] + _RETIRE_TAIL),
+    "pgh_sarw_run_batch_f64_retire": (C.c_int, BATCH64_SIGNATURES["pgh_sarw_run_batch_f64"][1] + _RETIRE_TAIL),
+    "pgh_spmm_f64_pair": BATCH64_SIGNATURES["pgh_spmm_f64"],
+}
+
 
 # header -> its table: every optional entry family; the names are distinct across the tables and from SIGNATURES
 OPTIONAL = {
@@ -412,9 +421,10 @@ OPTIONAL = {
 }
 # ... and every header entry() serves: OPTIONAL -- the thirteen families whose number and 41 names tests/test_fused_plumbing.py pins --
 # and the headers added since, which tests of their own enumerate (include/pgh_gnn.h: tests/test_gnn_host.py; include/pgh_select.h:
-# tests/test_subgraph_host.py; include/pgh_retire.h: tests/test_retire_host.py; include/pgh_batch64.h: tests/test_batch64_host.py)
+# tests/test_subgraph_host.py; include/pgh_retire.h: tests/test_retire_host.py; include/pgh_batch64.h: tests/test_batch64_host.py;
+# include/pgh_retire64.h: tests/test_retire64_host.py)
 TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES, "pgh_select.h": SELECT_SIGNATURES, "pgh_retire.h": RETIRE_SIGNATURES,
-                           "pgh_batch64.h": BATCH64_SIGNATURES})
+                           "pgh_batch64.h": BATCH64_SIGNATURES, "pgh_retire64.h": RETIRE64_SIGNATURES})
 _HEADER_OF = {name: header for header, table in TABLES.items() for name in table}
 DECLINED = 2              # every optional header's PGH_*_DECLINED: nothing was written, the caller takes its unfused route
 

@@ -66,8 +66,8 @@ struct MMRunAhead {
     // of every step that is a multiple of 8: the wait for the stream, before anything new is enqueued, is what makes that safe.
     // (on_pause empty: a loop whose kernels never pause.)
     // A step that reports the narrowing word (paused == 2, CloseParams::narrow_at) is committed and the steps enqueued behind it did
-    // nothing either: on_narrow(k) moves the run into its narrower workspace, waits for the stream and clears the word, and the run goes
-    // on behind step k.  The close that answers a pause may raise the word as well: a narrowing follows a committed close only.
+    // nothing either: on_narrow(k) waits for the stream, moves the run into its narrower workspace and clears the word (the f32 loops
+    // wait behind what they enqueue there, the f64 loops in front of it), and the run goes on behind step k.  The close that answers a pause may raise the word as well: a narrowing follows a committed close only.
     int run_ahead(int max_steps, const std::function<int(int)>& enqueue_step, const std::function<int(int)>& on_pause = nullptr,
                   const std::function<int(int)>& on_narrow = nullptr) {
         int enq = 0, seen = 0;

@@ -14,6 +14,7 @@
 // no counterpart here: every row is processed in every step.
 #include "pgh_kernels.h"
 #include "pgh_batch64.h"
+#include "pgh_retire64.h"
 #include "pgh_mm_run.h"
 
 #include <cmath>
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(WG) void k_mm64_rowops(int mode, double alpha, cons
 template <bool HAS_VAL, int LPR>
 __global__ __launch_bounds__(WG) void k_mm64_partial(MM64View f, const double* __restrict__ xg, int ld, double* __restrict__ sums,
                                                       const BatchState* __restrict__ state) {
-    if (state != nullptr && state->all_done) return;
+    if (state != nullptr && (state->all_done | state->paused)) return;
     constexpr int G = 64 / LPR;                            // tiles in flight per wavefront
     constexpr int R = LPR > 16 ? LPR : 16;                 // entries per round
     constexpr int W = R / LPR;                             // stream words of a round per lane
@@ -177,10 +178,88 @@ __global__ __launch_bounds__(WG) void k_mm64_partial(MM64View f, const double* _
     }
 }
 
+// The product pass of a slab that is ONE pair of columns wide (ld == 2; include/pgh_retire64.h): one lane per stream ENTRY instead of
+// one lane group per tile -- k_mm64_partial<., 4> gives such a tile to four lanes of which one holds columns, and that lane walks its
+// 512 entries one by one.  A wavefront takes a tile as 8 rounds of 64 entries.  Lane i of a round loads the words of entry 64 r + i
+// (coalesced 256-byte loads), gathers its source's 16-byte row and forms the product; an inclusive scan over the wavefront, segmented at
+// the lanes that close a row, sums both doubles in six steps; the open sum of the round before joins the lanes that have no closing lane
+// in front of them; every closing lane stores its value (head[t] for -2, the row's sums otherwise) and the open remainder behind the
+// last round is tail[t]: the contract k_mm64_fixup reads.  Words travel two rounds ahead of the scan, gathers one.  No LDS beyond
+// ds_bpermute, no atomics, a fixed order: a repeat returns the same bits.  The order of a row's additions is a tree, not the sequence of
+// the other forms.
+template <bool HAS_VAL>
+__global__ __launch_bounds__(WG) void k_mm64_partial_pair(MM64View f, const double* __restrict__ xg, double* __restrict__ sums,
+                                                           const BatchState* __restrict__ state) {
+    if (state != nullptr && (state->all_done | state->paused)) return;
+    constexpr int ROUNDS = kTile64 / 64;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (WG / 64) + (threadIdx.x >> 6)));
+    const int stride = gridDim.x * (WG / 64);
+    const unsigned long long below = (1ULL << lane) - 1ULL;            // the lanes in front of this one
+    struct Words {
+        uint32_t w;
+        int      c;
+        float    v;
+    };
+    for (int t = wave; t < f.num_tiles; t += stride) {
+        const int64_t base = (int64_t)t * kTile64 + lane;              // tiles are full and consecutive
+        auto words = [&](int r) __attribute__((always_inline)) {
+            Words q;
+            q.w = __builtin_nontemporal_load(f.colf + base + 64 * r);
+            q.c = __builtin_nontemporal_load(f.close + base + 64 * r);
+            q.v = HAS_VAL ? __builtin_nontemporal_load(f.val + base + 64 * r) : 1.f;
+            return q;
+        };
+        auto gather = [&](const Words& q) __attribute__((always_inline)) {
+            return *reinterpret_cast<const f64x2*>(xg + (int64_t)(q.w & 0x7fffffffu) * 2);
+        };
+        Words w0 = words(0), w1 = words(1);
+        f64x2 x0 = gather(w0);
+        double c0 = 0.0, c1 = 0.0;                                     // the open sum behind the rounds so far (wave-uniform)
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            Words w2 = w1;
+            if (r + 2 < ROUNDS) w2 = words(r + 2);
+            f64x2 x1 = x0;
+            if (r + 1 < ROUNDS) x1 = gather(w1);
+            double a0 = HAS_VAL ? (double)w0.v * x0.x : x0.x, a1 = HAS_VAL ? (double)w0.v * x0.y : x0.y;
+            const bool closes = w0.c != -1;
+            const unsigned long long ends = __ballot(closes);
+            const unsigned long long front = ends & below;             // the closing lanes in front of this one
+            const int first = front != 0 ? 64 - __builtin_clzll(front) : 0;     // the first lane of this lane's segment
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const double o0 = __shfl_up(a0, d, 64), o1 = __shfl_up(a1, d, 64);
+                if (lane - d >= first) {
+                    a0 += o0;
+                    a1 += o1;
+                }
+            }
+            if (front == 0) {
+                a0 += c0;
+                a1 += c1;
+            }
+            if (closes) {
+                const f64x2 s = {a0, a1};
+                if (w0.c == -2) *reinterpret_cast<f64x2*>(f.head + (int64_t)t * 2) = s;
+                else __builtin_nontemporal_store(s, reinterpret_cast<f64x2*>(sums + (int64_t)w0.c * 2));
+            }
+            const double l0 = __shfl(a0, 63, 64), l1 = __shfl(a1, 63, 64);
+            const bool shut = (ends >> 63) != 0;                       // the round's last entry closes: nothing stays open
+            c0 = shut ? 0.0 : l0;
+            c1 = shut ? 0.0 : l1;
+            w0 = w1;
+            w1 = w2;
+            x0 = x1;
+        }
+        if (lane == 0) *reinterpret_cast<f64x2*>(f.tail + (int64_t)t * 2) = f64x2{c0, c1};
+    }
+}
+
 // cross-tile segments: the chain of tail carries + the head piece, added in tile order.  A group of lanes_per_row64(ld) lanes per
 // closing tile; eight carries of a hub row's chain travel together.
 __global__ __launch_bounds__(WG) void k_mm64_fixup(MM64View f, int ld, double* __restrict__ sums, const BatchState* __restrict__ state) {
-    if (state != nullptr && state->all_done) return;
+    if (state != nullptr && (state->all_done | state->paused)) return;
     const int lpr = lanes_per_row64(ld), per_wave = 64 / lpr;
     const int lane = threadIdx.x & 63, l = lane & (lpr - 1), c2 = 2 * l;
     if (c2 >= ld) return;
@@ -294,7 +373,7 @@ __global__ __launch_bounds__(WG) void k_mm64_step(const double* __restrict__ sum
                                                    const double* __restrict__ y_old, double* __restrict__ y_new, double* __restrict__ xg, int64_t n,
                                                    int ld, int b, const BatchState* __restrict__ state, double* __restrict__ partials) {
     __shared__ double s_red[WG / 64][kLanes];
-    if (state->all_done) return;
+    if (state->all_done | state->paused) return;
     const int lane = threadIdx.x & 63;
     const int lpr = lanes_per_row64(ld), rows_per_wave = 64 / lpr;
     const int l = lane & (lpr - 1), c2 = 2 * l;
@@ -347,7 +426,7 @@ __global__ __launch_bounds__(WG) void k_mm64_residual(const double* __restrict__
                                                        int use_quotient, int linf, const BatchState* __restrict__ state,
                                                        const double* __restrict__ folded_sum, double* __restrict__ partials) {
     __shared__ double s_red[WG / 64][kLanes];
-    if (state->all_done) return;
+    if (state->all_done | state->paused) return;
     const int lane = threadIdx.x & 63;
     const int lpr = lanes_per_row64(ld), rows_per_wave = 64 / lpr;
     const int l = lane & (lpr - 1), c2 = 2 * l;
@@ -392,7 +471,7 @@ __global__ __launch_bounds__(WG) void k_mm64_residual(const double* __restrict__
 __global__ __launch_bounds__(WG) void k_mm64_fold(const double* __restrict__ partials, int count, int linf, const BatchState* __restrict__ state,
                                                    double* __restrict__ out) {
     __shared__ double s_red[WG / 64];
-    if (state != nullptr && state->all_done) return;
+    if (state != nullptr && (state->all_done | state->paused)) return;
     const int col = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double acc = 0.0;
     for (int i = threadIdx.x; i < count; i += WG) {
@@ -415,10 +494,12 @@ struct Close64 {
     double    tol;
     long long n_orig;
     int       use_quotient, check, err_kind;
+    int       narrow_at;         // a run that retires columns (include/pgh_retire64.h): with this many live columns or fewer behind the
+                                 // committed close, the steps enqueued behind it do nothing (state->paused = 2) and the host narrows; 0: never
 };
 __global__ void k_mm64_close(BatchState* __restrict__ state, const double* __restrict__ folded_sum, const double* __restrict__ folded_err, Close64 cp) {
     const int lane = threadIdx.x;
-    if (state->all_done) return;
+    if (state->all_done | state->paused) return;
     int done = 1;
     if (lane < state->b && !state->done[lane]) {
         if (cp.use_quotient) {
@@ -444,6 +525,7 @@ __global__ void k_mm64_close(BatchState* __restrict__ state, const double* __res
     if (lane == 0) {
         state->all_done = (all == ~0ULL) ? 1 : 0;
         state->executed += 1;
+        if (cp.narrow_at > 0 && all != ~0ULL && 64 - __popcll(all) <= cp.narrow_at) state->paused = 2;
     }
 }
 
@@ -467,6 +549,102 @@ __global__ void k_mm64_state_init(BatchState* state, int b, ColFactors scale0, i
         state->paused = 0;
         state->executed = 0;
         state->b = b;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// A run that retires its converged columns (include/pgh_retire64.h).  Between two steps the stopped columns leave
+// (k_mm64_retire_out), the live ones move into narrower slabs (k_mm64_repack) and the loop state follows them (k_mm64_state_narrow).
+//
+// k_mm64_way_out<float> for SOME columns of the slab, each to a column of the caller's [n, dst_b] slab: lane column j goes to column
+// cols.dst[j] (-1: stays) times cols.factor[j] in f64, rounded once.
+struct RetireCols64 {
+    int    dst[kLanes];
+    double factor[kLanes];
+};
+__global__ __launch_bounds__(WG) void k_mm64_retire_out(const double* __restrict__ slab, const int32_t* __restrict__ perm, int64_t n_int, int64_t n_valid,
+                                                         int ld, RetireCols64 cols, float* __restrict__ dst, int dst_b) {
+    const int lpr = lanes_per_row64(ld), rows_per_wave = 64 / lpr;
+    const int lane = threadIdx.x & 63, l = lane & (lpr - 1), c2 = 2 * l;
+    if (c2 >= ld) return;
+    const int to0 = cols.dst[c2], to1 = cols.dst[c2 + 1];
+    if (to0 < 0 && to1 < 0) return;
+    const double f0 = cols.factor[c2], f1 = cols.factor[c2 + 1];
+    const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + (threadIdx.x >> 6)) * rows_per_wave + lane / lpr;
+    const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
+    for (int64_t r = first; r < n_int; r += stride) {
+        const int64_t o = perm ? perm[r] : (r < n_valid ? r : -1);
+        if (o < 0) continue;
+        const f64x2 v = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(slab + r * ld + c2));
+        if (to0 >= 0) dst[o * dst_b + to0] = (float)(v.x * f0);
+        if (to1 >= 0) dst[o * dst_b + to1] = (float)(v.y * f1);
+    }
+}
+
+// The live columns of three wide slabs (p / |p|, the current iterate, the gather slab) into their narrow ones in one pass over the rows:
+// column i of a narrow slab is column src[i] of the wide one (-1: the padding column of an odd width, zeros -- a frozen lane copies
+// its old iterate forward, so the zeros stay).  A group of lanes_per_row64(ld_w) lanes loads a wide row as f64x2, the values change
+// lanes as 32-bit halves through ds_bpermute and the first ld_n / 2 lanes of the group store the narrow row.
+struct Repack64 {
+    const double* wide[3];
+    double*       narrow[3];
+    int           src[kLanes];
+};
+__global__ __launch_bounds__(WG) void k_mm64_repack(Repack64 q, int64_t n_int, int ld_w, int ld_n) {
+    const int lpr = lanes_per_row64(ld_w), rows_per_wave = 64 / lpr;
+    const int lane = threadIdx.x & 63, l = lane & (lpr - 1), c2 = 2 * l;
+    const bool reads = c2 < ld_w, writes = c2 < ld_n;
+    int from[2], part[2];                                  // per value of this lane's narrow pair: the lane that holds it and which of its two
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int s = writes ? q.src[c2 + k] : -1;
+        from[k] = s >= 0 ? (lane & ~(lpr - 1)) + (s >> 1) : lane;
+        part[k] = s >= 0 ? (s & 1) : -1;
+    }
+    // (wave-uniform trip count: every lane of the wavefront takes part in the exchange)
+    const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + (threadIdx.x >> 6)) * rows_per_wave;
+    const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
+    for (int64_t r0 = first; r0 < n_int; r0 += stride) {
+        const int64_t r = r0 + lane / lpr;
+        const bool ok = r < n_int;
+        const int64_t at = (ok ? r : 0) * ld_w + (reads ? c2 : 0);
+        f64x2 v[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            v[i] = (ok && reads) ? __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(q.wide[i] + at)) : f64x2{0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            f64x2 out;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const double x = __shfl(v[i].x, from[k], 64), y = __shfl(v[i].y, from[k], 64);
+                out[k] = part[k] == 0 ? x : (part[k] == 1 ? y : 0.0);
+            }
+            if (ok && writes) *reinterpret_cast<f64x2*>(q.narrow[i] + r * ld_n + c2) = out;
+        }
+    }
+}
+
+// the lanes of the loop state follow their columns: lane i <- lane src.v[i] for i < b_new, the lanes beyond are done from the start (as
+// k_mm64_state_init leaves them); the word that voided the enqueued steps is cleared
+struct ColMap64 {
+    int v[kLanes];
+};
+__global__ void k_mm64_state_narrow(BatchState* state, ColMap64 src, int b_new) {
+    const int lane = threadIdx.x;
+    const int s = lane < b_new ? src.v[lane] : -1;
+    const double scale = s >= 0 ? state->scale[s] : 1.0, err = s >= 0 ? state->err[s] : 0.0, sum = s >= 0 ? state->sum[s] : 0.0;
+    const int done = s >= 0 ? state->done[s] : 1, steps = s >= 0 ? state->steps[s] : 0, converged = s >= 0 ? state->converged[s] : 0;
+    __syncthreads();                                       // every lane has read before any lane writes
+    state->scale[lane] = scale;
+    state->err[lane] = err;
+    state->sum[lane] = sum;
+    state->done[lane] = done;
+    state->steps[lane] = steps;
+    state->converged[lane] = converged;
+    if (lane == 0) {
+        state->paused = 0;
+        state->b = b_new;
     }
 }
 
@@ -545,10 +723,12 @@ __global__ __launch_bounds__(WG) void k_mm64_poly_step(const double* __restrict_
 struct MM64Run : MMRunAhead {
     pgh_graph_s* const g;
     const BsfFormat&   f;
-    const int          b, ld;
+    int                b, ld;           // (a run that retires columns narrows them: narrow_to)
     const int64_t      n, n_int;
-    const size_t       slab;            // bytes of one [n_int, ld] slab of doubles
-    const int          cgrid, row_grid;
+    size_t             slab;            // bytes of one [n_int, ld] slab of doubles
+    const int          cgrid;
+    int                row_grid;
+    bool               pair = false;    // the product of a slab with ld == 2 takes the pair form (k_mm64_partial_pair)
     PoolBuf   rowop, bad, slabs[5], head, tail, partial, folded, state_mem;
     LoopTimer timer;
 
@@ -607,6 +787,27 @@ struct MM64Run : MMRunAhead {
         v.tail = tail.as<double>();
         v.num_tiles = f.num_tiles;
         const int lpr = lanes_per_row64(ld);
+        if (pair && ld == 2) {
+            static int pair_per_cu[2] = {0, 0};
+            int& per_cu = pair_per_cu[f.val ? 1 : 0];
+            if (per_cu == 0) {
+                const void* kernel = f.val ? (const void*)k_mm64_partial_pair<true> : (const void*)k_mm64_partial_pair<false>;
+                PGH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, WG, 0));
+                if (per_cu < 1) per_cu = 1;
+            }
+            const int grid = r.num_cus * per_cu;           // persistent, a wavefront per tile in flight
+            {
+                ProfScope prof(PGH_K_SPMM);
+                if (f.val) k_mm64_partial_pair<true><<<grid, WG, 0, r.stream>>>(v, xg, s(0), state);
+                else k_mm64_partial_pair<false><<<grid, WG, 0, r.stream>>>(v, xg, s(0), state);
+            }
+            {
+                ProfScope prof(PGH_K_FIXUP);
+                k_mm64_fixup<<<blocks_for((int64_t)f.num_tiles * lpr, 64), WG, 0, r.stream>>>(v, ld, s(0), state);
+            }
+            PGH_HIP(hipGetLastError());
+            return 0;
+        }
         const int which = (f.val ? 4 : 0) + (lpr == 32 ? 0 : (lpr == 16 ? 1 : (lpr == 8 ? 2 : 3)));
         const void* kernels[8] = {(const void*)k_mm64_partial<false, 32>, (const void*)k_mm64_partial<false, 16>, (const void*)k_mm64_partial<false, 8>,
                                   (const void*)k_mm64_partial<false, 4>,  (const void*)k_mm64_partial<true, 32>,  (const void*)k_mm64_partial<true, 16>,
@@ -636,6 +837,26 @@ struct MM64Run : MMRunAhead {
             k_mm64_fixup<<<blocks_for((int64_t)f.num_tiles * lpr, 64), WG, 0, r.stream>>>(v, ld, s(0), state);
         }
         PGH_HIP(hipGetLastError());
+        return 0;
+    }
+    // A run that retires columns moves into slabs of `width` columns: every slab and both carries again, the row sums and the head
+    // carries as zeros (as alloc leaves them: a row without entries is never written by the product and k_mm64_step reads it).  The wide
+    // blocks move to `wide`; what `wide` held goes back to the pool (the caller has waited for the stream since their last reader).
+    int narrow_to(int width, PoolBuf (&wide)[7]) {
+        b = width;
+        ld = (width + 1) & ~1;
+        slab = sizeof(double) * (size_t)n_int * ld;
+        row_grid = blocks_for(n_int * lanes_per_row64(ld));
+        const size_t carries = sizeof(double) * (size_t)(f.num_tiles + 1) * ld;
+        PoolBuf* mine[7] = {&slabs[0], &slabs[1], &slabs[2], &slabs[3], &slabs[4], &head, &tail};
+        for (int i = 0; i < 7; ++i) {
+            if (wide[i].p != nullptr) pool_free(wide[i].p);
+            wide[i].p = mine[i]->p;
+            mine[i]->p = nullptr;
+            PGH_TRY(mine[i]->alloc(i < 5 ? slab : carries));
+        }
+        PGH_HIP(hipMemsetAsync(slabs[0].p, 0, slab, rt().stream));
+        PGH_HIP(hipMemsetAsync(head.p, 0, carries, rt().stream));
         return 0;
     }
     // The way out: `result` times the column's factor (the state's quotient when state_scale, times its output scale), rounded once
@@ -685,12 +906,54 @@ int check64_mats(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop_cfg* 
     return 0;
 }
 
-// mode 0 / 1 / 2 of k_mm64_rowops (the modes of recursive_run_f64, pgh_spmv.hip)
+// The host's record of a run that retires its columns (include/pgh_retire64.h): the levels, and the report as it grows.  The rule of
+// pgh_spmm.hip's RetirePlan for slabs that are whole PAIRS of doubles.
+struct Retire64Plan {
+    std::vector<int>  levels;        // strictly descending
+    pgh_retire_report report{};
+    bool              pair = true;   // PGH_MM64_PAIR, read per call: the product of a stage with ld == 2 takes the pair form
+    // the live count at or below which a slab of width ld narrows (0: never): the greatest level below ld, and a narrower slab results
+    int trigger(int ld, int stages) const {
+        if (stages >= PGH_RETIRE_MAX_STAGES) return 0;
+        for (int level : levels)
+            if (level < ld) return level < ld - 2 ? level : ld - 2;
+        return 0;
+    }
+    void stage(int ld, int live, int first_step) {
+        const int s = report.num_stages;
+        if (s > 0) report.column_steps += (int64_t)report.ld[s - 1] * (first_step - report.first_step[s - 1]);
+        report.ld[s] = ld;
+        report.live[s] = live;
+        report.first_step[s] = first_step;
+        report.num_stages = s + 1;
+    }
+    void close(int executed) {
+        const int s = report.num_stages - 1;
+        report.column_steps += (int64_t)report.ld[s] * (executed + 1 - report.first_step[s]);
+    }
+    // null levels (num_levels != 0): {32, 16, 8, 4, 2}
+    int init(const int32_t* given, int32_t num_levels, const char* who) {
+        const char* env = getenv("PGH_MM64_PAIR");
+        pair = !(env != nullptr && env[0] == '0');
+        if (given == nullptr && num_levels != 0) {
+            levels = {32, 16, 8, 4, 2};
+            return 0;
+        }
+        PGH_CHECK(num_levels >= 0 && num_levels < kLanes, std::string(who) + ": the number of levels must be in [0, 63]");
+        for (int i = 0; i < num_levels; ++i) {
+            PGH_CHECK(given[i] >= 1 && given[i] < kLanes && (i == 0 || given[i] < given[i - 1]),
+                      std::string(who) + ": the levels must be strictly descending live-column counts in [1, 63]");
+            levels.push_back(given[i]);
+        }
+        return 0;
+    }
+};
+
+// mode 0 / 1 / 2 of k_mm64_rowops (the modes of recursive_run_f64, pgh_spmv.hip); retire (or null: the plain entries): the run narrows
 int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
-                      pgh_loop_result* results, const double* in_norms, const char* who) {
-    const int b = p->b;
+                      pgh_loop_result* results, const double* in_norms, const char* who, Retire64Plan* retire = nullptr) {
     ColFactors inv{};
-    for (int j = 0; j < b; ++j) {
+    for (int j = 0; j < p->b; ++j) {
         PGH_CHECK(std::isfinite(in_norms[j]) && in_norms[j] >= 0.0, std::string(who) + ": a norm that is negative or not finite");
         inv.v[j] = in_norms[j] != 0.0 ? 1.0 / in_norms[j] : 0.0;
     }
@@ -698,13 +961,14 @@ int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pg
     PGH_CHECK(mode == 0 || g->degrees != nullptr, "the absorbing walks need the graph's degrees");
     PGH_TRY(mm_ensure_layout(g));
     Runtime& r = rt();
-    MM64Run run(g, b);
+    MM64Run run(g, p->b);
     // slabs: 0 the row sums, 1 p / |p|, 2 and 3 the two iterates, 4 the gather slab
     PGH_TRY(run.alloc(4, true));
     bool bad = false;
     PGH_TRY(run.row_operands(mode, cfg->alpha, lam, &bad));
     if (bad) return declined(PGH_BATCH64_DECLINED, "a row with absorption + degree == 0 (or a non-finite absorption): the single-vector loop's NaN");
-    const int ld = run.ld, cgrid = run.cgrid;
+    int &b = run.b, &ld = run.ld;                          // (a run that retires columns narrows them, see `narrow` below)
+    const int cgrid = run.cgrid;
     const int64_t n_int = run.n_int;
     double* y[2] = {run.s(2), run.s(3)};
     double* partial = run.partial.as<double>();
@@ -721,6 +985,7 @@ int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pg
     cp.n_orig = run.n;
     cp.use_quotient = cfg->use_quotient;
     cp.err_kind = cfg->err_kind;
+    cp.narrow_at = retire != nullptr ? retire->trigger(ld, 1) : 0;
     // step k produces the iterate of iteration k + 1 and is followed by that iteration's check
     auto enqueue_step = [&](int k) -> int {
         PGH_TRY(run.product(run.s(4)));
@@ -740,22 +1005,107 @@ int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pg
         PGH_HIP(hipGetLastError());
         return run.publish_poll(k);
     };
-    PGH_TRY(run.run_ahead(max_steps, enqueue_step));
-    // the iterate of the last executed step: a stopped column was copied forward by every later one
-    BatchPoll last{};
-    PGH_HIP(hipMemcpyAsync(&last, &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
+    if (retire == nullptr) {
+        PGH_TRY(run.run_ahead(max_steps, enqueue_step));
+        // the iterate of the last executed step: a stopped column was copied forward by every later one
+        BatchPoll last{};
+        PGH_HIP(hipMemcpyAsync(&last, &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
+        PGH_HIP(hipStreamSynchronize(r.stream));
+        return run.finish(true, y[last.executed & 1], cfg, out_scales, in_norms, ranks->data, 1, results);
+    }
+    // A run that retires its columns (include/pgh_retire64.h).  col_of[i]: the caller's column in lane column i of the current slabs.  A
+    // column leaves once, at the narrowing that follows its stop or at the end, and its part of the loop state is kept for results[].
+    const int width = b;                                   // the caller's row length
+    int col_of[kLanes];
+    for (int j = 0; j < kLanes; ++j) col_of[j] = j < b ? j : -1;
+    BatchState kept{};                                     // lanes indexed by the caller's column
+    PoolBuf wide[7];                                       // what a narrowing hands back to the pool at the next one, or when this frame ends
+    auto retire_lanes = [&](const BatchState& hs, bool all) {       // the lanes that have stopped (all: every lane) leave from the last iterate
+        RetireCols64 cols;
+        for (int j = 0; j < kLanes; ++j) {
+            cols.dst[j] = -1;
+            cols.factor[j] = 1.0;
+            if (j >= b || !(all || hs.done[j])) continue;
+            const int c = col_of[j];
+            double scale = out_scales ? out_scales[c] : cfg->out_scale;
+            if (!out_scales && scale < 0.0) scale = in_norms[c];
+            cols.dst[j] = c;
+            cols.factor[j] = hs.scale[j] * scale;          // (MM64Run::finish's factor)
+            kept.steps[c] = hs.steps[j];
+            kept.converged[c] = hs.converged[j];
+            kept.err[c] = hs.err[j];
+        }
+        k_mm64_retire_out<<<run.row_grid, WG, 0, r.stream>>>(y[hs.executed & 1], run.f.perm, n_int, run.n, ld, cols, ranks->data, width);
+    };
+    auto narrow = [&](int k) -> int {
+        BatchState hs;
+        PGH_HIP(hipMemcpyAsync(&hs, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
+        PGH_HIP(hipStreamSynchronize(r.stream));
+        retire_lanes(hs, false);
+        Repack64 q{};
+        ColMap64 map{};
+        int nb = 0;
+        for (int j = 0; j < kLanes; ++j) q.src[j] = map.v[j] = -1;
+        for (int j = 0; j < b; ++j)
+            if (!hs.done[j]) q.src[nb] = map.v[nb] = j, ++nb;
+        const int wide_ld = ld, wide_grid = run.row_grid;
+        PGH_CHECK(nb >= 1 && ((nb + 1) & ~1) < ld && hs.executed == k, std::string(who) + ": the loop state does not ask for a narrowing");
+        // the narrow slabs come from the pool; the wide ones go back at the next narrowing or with this frame (the stream is still reading them)
+        PGH_TRY(run.narrow_to(nb, wide));
+        run.pair = retire->pair;                           // (a run that starts two columns wide never narrows: the plain entry's bits)
+        const int cur = hs.executed & 1;
+        y[0] = run.s(2);
+        y[1] = run.s(3);
+        q.wide[0] = wide[1].as<double>();                  // p / |p|
+        q.wide[1] = wide[2 + cur].as<double>();            // the iterate of the last executed step
+        q.wide[2] = wide[4].as<double>();                  // its gather slab
+        q.narrow[0] = run.s(1);
+        q.narrow[1] = y[cur];                              // (the other iterate is written in full by the next step before anyone reads it)
+        q.narrow[2] = run.s(4);
+        k_mm64_repack<<<wide_grid, WG, 0, r.stream>>>(q, n_int, wide_ld, ld);
+        k_mm64_state_narrow<<<1, kLanes, 0, r.stream>>>(state, map, nb);
+        PGH_HIP(hipGetLastError());
+        int cols_now[kLanes];
+        memcpy(cols_now, col_of, sizeof(cols_now));
+        for (int j = 0; j < kLanes; ++j) col_of[j] = j < nb ? cols_now[map.v[j]] : -1;
+        retire->stage(ld, nb, k + 1);
+        cp.narrow_at = retire->trigger(ld, retire->report.num_stages);
+        return 0;
+    };
+    retire->stage(ld, b, 1);
+    PGH_TRY(run.run_ahead(max_steps, enqueue_step, nullptr, narrow));
+    BatchState hs;
+    PGH_HIP(hipMemcpyAsync(&hs, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
     PGH_HIP(hipStreamSynchronize(r.stream));
-    return run.finish(true, y[last.executed & 1], cfg, out_scales, in_norms, ranks->data, 1, results);
+    retire->close(hs.executed);
+    if (retire->report.num_stages == 1)                    // never narrowed: the plain way out
+        return run.finish(true, y[hs.executed & 1], cfg, out_scales, in_norms, ranks->data, 1, results);
+    retire_lanes(hs, true);
+    PGH_HIP(hipGetLastError());
+    double ms = 0.0;
+    PGH_TRY(run.timer.stop(&ms));
+    for (int j = 0; j < width; ++j) {
+        memset(&results[j], 0, sizeof(pgh_loop_result));
+        results[j].in_norm = in_norms[j];
+        results[j].flags = PGH_RETIRE_NARROWED;
+        if (in_norms[j] == 0.0) continue;
+        results[j].iterations = 1 + kept.steps[j];
+        results[j].converged = kept.converged[j];
+        results[j].spmv_count = kept.steps[j];
+        results[j].last_error = kept.err[j];
+        results[j].loop_ms = ms;
+    }
+    return 0;
 }
 
-}  // namespace
-
-extern "C" int pgh_spmm_f64(pgh_graph_t g, const double* x_host, int32_t b, double* y_host) {
-    PGH_TRY(check64(g, b, !(g && x_host && y_host), "pgh_spmm_f64"));
-    PGH_CHECK(x_host != y_host, "pgh_spmm_f64: the output aliases the input");
+// Y = M^T X on host doubles: pgh_spmm_f64, and with `pair` (b <= 2) pgh_spmm_f64_pair
+int spmm64(pgh_graph_t g, const double* x_host, int32_t b, double* y_host, bool pair, const char* who) {
+    PGH_TRY(check64(g, b, !(g && x_host && y_host), who));
+    PGH_CHECK(x_host != y_host, std::string(who) + ": the output aliases the input");
     PGH_TRY(mm_ensure_layout(g));
     Runtime& r = rt();
     MM64Run run(g, b);
+    run.pair = pair;
     PGH_TRY(run.alloc(1, false));                          // slabs: 0 the row sums, 1 the gather slab
     bool bad = false;
     PGH_TRY(run.row_operands(3, 0.0, nullptr, &bad));
@@ -775,6 +1125,19 @@ extern "C" int pgh_spmm_f64(pgh_graph_t g, const double* x_host, int32_t b, doub
     PGH_HIP(hipMemcpyAsync(y_host, io.p, bytes, hipMemcpyDeviceToHost, r.stream));
     PGH_HIP(fence.wait());
     return 0;
+}
+
+}  // namespace
+
+extern "C" int pgh_spmm_f64(pgh_graph_t g, const double* x_host, int32_t b, double* y_host) {
+    return spmm64(g, x_host, b, y_host, false, "pgh_spmm_f64");
+}
+
+extern "C" int pgh_spmm_f64_pair(pgh_graph_t g, const double* x_host, int32_t b, double* y_host) {
+    const char* who = "pgh_spmm_f64_pair";
+    PGH_CHECK(g && x_host && y_host, std::string(who) + ": null argument");
+    PGH_CHECK(b >= 1 && b <= 2, std::string(who) + ": the width must be 1 or 2");
+    return spmm64(g, x_host, b, y_host, true, who);
 }
 
 extern "C" int pgh_ppr_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
@@ -800,6 +1163,49 @@ extern "C" int pgh_sarw_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_mat_t rank
     PGH_TRY(check64(g, p ? p->b : 1, !(g && p && ranks && cfg && results && in_norms), who));
     PGH_TRY(check64_mats(g, p, ranks, cfg, who));
     return recursive_batch64(g, 2, p, nullptr, ranks, cfg, out_scales, results, in_norms, who);
+}
+
+// The recursive loops in the mode that retires converged columns (include/pgh_retire64.h): the plain sibling's checks, the levels, the
+// loop with its plan, the report.
+namespace {
+int retire64_report_out(int status, const Retire64Plan& plan, pgh_retire_report* report) {
+    if (status == 0 && report != nullptr) *report = plan.report;
+    return status;
+}
+}  // namespace
+
+extern "C" int pgh_ppr_run_batch_f64_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                                            pgh_loop_result* results, const double* in_norms, const int32_t* levels, int32_t num_levels,
+                                            pgh_retire_report* report) {
+    const char* who = "pgh_ppr_run_batch_f64_retire";
+    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && ranks && cfg && results && in_norms), who));
+    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
+    Retire64Plan plan;
+    PGH_TRY(plan.init(levels, num_levels, who));
+    return retire64_report_out(recursive_batch64(g, 0, p, nullptr, ranks, cfg, out_scales, results, in_norms, who, &plan), plan, report);
+}
+
+extern "C" int pgh_absorb_run_batch_f64_retire(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
+                                               const double* out_scales, pgh_loop_result* results, const double* in_norms,
+                                               const int32_t* levels, int32_t num_levels, pgh_retire_report* report) {
+    const char* who = "pgh_absorb_run_batch_f64_retire";
+    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && lam && ranks && cfg && results && in_norms), who));
+    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
+    PGH_CHECK(lam->n == g->n_cols, std::string(who) + ": absorption length mismatch");
+    Retire64Plan plan;
+    PGH_TRY(plan.init(levels, num_levels, who));
+    return retire64_report_out(recursive_batch64(g, 1, p, lam->data, ranks, cfg, out_scales, results, in_norms, who, &plan), plan, report);
+}
+
+extern "C" int pgh_sarw_run_batch_f64_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                                             pgh_loop_result* results, const double* in_norms, const int32_t* levels, int32_t num_levels,
+                                             pgh_retire_report* report) {
+    const char* who = "pgh_sarw_run_batch_f64_retire";
+    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && ranks && cfg && results && in_norms), who));
+    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
+    Retire64Plan plan;
+    PGH_TRY(plan.init(levels, num_levels, who));
+    return retire64_report_out(recursive_batch64(g, 2, p, nullptr, ranks, cfg, out_scales, results, in_norms, who, &plan), plan, report);
 }
 
 // The taylor form with f64 terms and accumulator for b columns: iteration 1 is result_1 = c_1 p with the check of iteration 2 on

@@ -39,14 +39,16 @@ def _f64_image_usable(g):
     return g is not None and g.shape[0] == g.shape[1] and g.shape[0] > 0 and g.nnz > 0 and "row-major" not in g.format()
 
 
-def _batch_call(ranker, plain, retiring, args):
-    """One multi-seed call of propagate: through `plain(*args)`, or -- when ``ranker.retire`` asks for it -- through the entry
-    `retiring` of include/pgh_retire.h, which takes the same arguments with the levels and a report behind them and retires converged
-    columns inside the loop.  A library without that entry takes the plain call, and so does a call the entry DECLINED.  Returns
-    (status, the report as ``_lib.retire_stages`` gives it, or None after a plain call)."""
-    entry = L.entry(retiring) if L.retire_on(getattr(ranker, "retire", False)) else None
+def _batch_call(ranker, plain, retiring, args, switch="retire"):
+    """One multi-seed call of propagate: through `plain(*args)`, or -- when the ranker's attribute `switch` asks for it -- through the
+    entry `retiring` of include/pgh_retire.h (``retire``, the f32 loops) or include/pgh_retire64.h (``f64_retire``, the f64 loops), which
+    takes the same arguments with the levels and a report behind them and retires converged columns inside the loop.  A library without
+    that entry takes the plain call, and so does a call the entry DECLINED.  Returns (status, the report as ``_lib.retire_stages``
+    gives it, or None after a plain call)."""
+    wanted = getattr(ranker, switch, False)
+    entry = L.entry(retiring) if L.retire_on(wanted) else None
     if entry is not None:
-        levels, count = L.retire_levels(ranker.retire)
+        levels, count = L.retire_levels(wanted)
         report = L.RetireReport()
         status = entry(*args, levels, count, C.byref(report))
         if status != L.DECLINED:
@@ -99,9 +101,10 @@ def _propagate_in_batches64(ranker, features, cfg, run, raw):
     """_propagate_in_batches through an entry of include/pgh_batch64.h (``GraphFilter(f64_batch=True)``): the loop keeps its iterates,
     sums, quotients and residuals in f64 and the tolerance is clamped at fp64 eps (_f64_cfg).  raw: the chunk goes in UN-normalised
     with its column norms beside it, as _f64_operands hands a single vector to the f64 route (the recursive filters); otherwise
-    L1-normalised in f32, as the closed-form filters' single rank() does.  run(P, R, cfg_ref, scales, results, norms) -> status.
-    Every record of ``last_batches`` carries "f64": True.  Returns the [n, B] ranks, or None when the engine declined the first chunk
-    (nothing was run)."""
+    L1-normalised in f32, as the closed-form filters' single rank() does.  run(P, R, cfg_ref, scales, results, norms) -> what
+    _batch_call returns (the recursive filters: ``f64_retire`` picks the entry of include/pgh_retire64.h).  Every record of
+    ``last_batches`` carries "f64": True, and the report of a retiring run under "stages".  Returns the [n, B] ranks, or None when the
+    engine declined the first chunk (nothing was run)."""
     from pygrank_amd.device import DeviceMatrix
     F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
     if not isinstance(F, DeviceMatrix):
@@ -124,11 +127,11 @@ def _propagate_in_batches64(ranker, features, cfg, run, raw):
         scales = (C.c_double * chunk.b)(*[(float(nrm) if ranker.preserve_norm else 1.0) for nrm in norms])
         in_norms = (C.c_double * chunk.b)(*[float(nrm) for nrm in norms])
         ranker.convergence.start()
-        status = run(P, R, C.byref(cfg), scales, results, in_norms)
+        status, stages = run(P, R, C.byref(cfg), scales, results, in_norms)
         if status == L.DECLINED and not batches:
             return None
         L.check(status)
-        batches.append([dict(record, f64=True) for record in _batch_info(results, None)])
+        batches.append([dict(record, f64=True) for record in _batch_info(results, stages)])
         ranker.last_batches = batches
         for r, nrm in zip(results, norms):
             if nrm != 0:
@@ -156,7 +159,8 @@ class GraphFilter(NodeRanking):
         filters run chunks of up to 64 columns through the f64 multi-seed loops of include/pgh_batch64.h instead of one f64 loop per
         column; ``last_batches`` records carry "f64": True.  A column may differ from the column loop's in its last bits (the row sums
         are grouped differently).  Not served -- today's route: graph_dropout, the "chebyshev" form, warm starts, AlgorithmSelection's
-        mixed groups, LFPR; ``retire=`` is ignored by the f64 batch (a later piece of work)."""
+        mixed groups, LFPR; ``retire=`` is ignored by the f64 batch, whose own switch is ``f64_retire=`` of PageRank, AbsorbingWalks
+        and SymmetricAbsorbingRandomWalks (include/pgh_retire64.h)."""
         if dtype not in (None, "float32", "float64"):
             raise Exception("dtype is None (f32, f64 below fp32 eps), 'float32' or 'float64'")
         self.dtype = dtype
@@ -403,17 +407,21 @@ class RecursiveGraphFilter(GraphFilter):
 class PageRank(RecursiveGraphFilter):
     """adhoc.py:9-46: r <- alpha * M^T r + (1 - alpha) * p."""
 
-    def __init__(self, alpha=0.85, *args, dtype=None, retire=False, **kwargs):
+    def __init__(self, alpha=0.85, *args, dtype=None, retire=False, f64_retire=False, **kwargs):
         """retire (an extension of this backend; also an attribute): True, or a list of strictly descending live-column counts below 64
         (True: 32, 16, 8, 4) -- propagate's multi-seed runs retire their converged columns inside the loop (include/pgh_retire.h) and
         ``last_batches`` carries the run's report under "stages".  A column of such a run may differ from the plain batch's in its last
         bits.  graph_dropout takes the plain loop.
+        f64_retire (also an attribute): the same for the f64 batch of ``f64_batch=True`` (include/pgh_retire64.h; True: 32, 16, 8, 4, 2
+        -- a slab of doubles narrows in pairs of columns, and a last stage of one pair runs its product one lane per stream entry).
+        Without ``f64_batch`` it has no effect; a narrowed column stays within one f32 ulp of the plain f64 batch's.
         dtype="float64" (an extension of this backend): the loop keeps its iterates, sums, quotient and residual in f64 on the engine's
         f64 image (pgh_ppr_run_f64) and the tolerance is clamped at fp64 eps like the reference's numpy backend
         (pygrank/core/backend/numpy.py:84-86) instead of fp32 eps -- e.g. tol=1e-9 as in the reference's tests/test_filters.py:189,194.
         An exactness mode (one host look per step); personalization and ranks stay f32 vectors."""
         self.alpha = alpha
         self.retire = retire
+        self.f64_retire = f64_retire
         super().__init__(*args, dtype=dtype, **kwargs)
 
     def _reference(self):
@@ -492,8 +500,9 @@ class PageRank(RecursiveGraphFilter):
         entry64 = L.entry("pgh_ppr_run_batch_f64") if g64 is not None else None
         if entry64 is not None:
             out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
-                                          lambda P, R, cfg_ref, scales, res, norms: entry64(g64._h, P._h, R._h, cfg_ref, scales, res, norms),
-                                          raw=True)
+                                          lambda P, R, cfg_ref, scales, res, norms: _batch_call(
+                                              self, entry64, "pgh_ppr_run_batch_f64_retire", (g64._h, P._h, R._h, cfg_ref, scales, res, norms),
+                                              switch="f64_retire"), raw=True)
             if out is not None:
                 return out
         cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
@@ -547,11 +556,12 @@ class PageRank(RecursiveGraphFilter):
 class AbsorbingWalks(RecursiveGraphFilter):
     """adhoc.py:125-174: partially absorbing random walks."""
 
-    def __init__(self, alpha=1 - 1.E-6, *args, retire=False, **kwargs):
-        """retire: as PageRank's (propagate's multi-seed runs retire their converged columns inside the loop)."""
+    def __init__(self, alpha=1 - 1.E-6, *args, retire=False, f64_retire=False, **kwargs):
+        """retire, f64_retire: as PageRank's (propagate's multi-seed runs retire their converged columns inside the loop)."""
         super().__init__(*args, **kwargs)
         self.alpha = alpha
         self.retire = retire
+        self.f64_retire = f64_retire
 
     def _reference(self):
         return f"partially absorbing random walks (absorption scale {(1 - self.alpha) / self.alpha:.3g})"
@@ -595,8 +605,9 @@ class AbsorbingWalks(RecursiveGraphFilter):
             lam = (to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np
             if isinstance(lam, DeviceVector) and len(lam) == g64.shape[0]:
                 out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
-                                              lambda P, R, cfg_ref, scales, res, norms: entry64(g64._h, P._h, lam._h, R._h, cfg_ref, scales, res,
-                                                                                                norms), raw=True)
+                                              lambda P, R, cfg_ref, scales, res, norms: _batch_call(
+                                                  self, entry64, "pgh_absorb_run_batch_f64_retire",
+                                                  (g64._h, P._h, lam._h, R._h, cfg_ref, scales, res, norms), switch="f64_retire"), raw=True)
                 if out is not None:
                     return out
         g = self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",))
@@ -867,11 +878,12 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
     a = (1 + sqrt(1 + 4 d)) / 2 a step is ``conv(ranks / a, M) * d / (a + d) + personalization * a / (a + d)``
     (``alpha`` is accepted for signature compatibility and, as in the reference, does not enter the formula)."""
 
-    def __init__(self, alpha=0.5, *args, retire=False, **kwargs):
-        """retire: as PageRank's (propagate's multi-seed runs retire their converged columns inside the loop)."""
+    def __init__(self, alpha=0.5, *args, retire=False, f64_retire=False, **kwargs):
+        """retire, f64_retire: as PageRank's (propagate's multi-seed runs retire their converged columns inside the loop)."""
         super().__init__(*args, **kwargs)
         self.alpha = alpha
         self.retire = retire
+        self.f64_retire = f64_retire
 
     def _reference(self):
         return "symmetric partially absorbing random walks"
@@ -911,8 +923,9 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
         entry64 = L.entry("pgh_sarw_run_batch_f64") if g64 is not None else None
         if entry64 is not None:
             out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
-                                          lambda P, R, cfg_ref, scales, res, norms: entry64(g64._h, P._h, R._h, cfg_ref, scales, res, norms),
-                                          raw=True)
+                                          lambda P, R, cfg_ref, scales, res, norms: _batch_call(
+                                              self, entry64, "pgh_sarw_run_batch_f64_retire", (g64._h, P._h, R._h, cfg_ref, scales, res, norms),
+                                              switch="f64_retire"), raw=True)
             if out is not None:
                 return out
         g = self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs)
@@ -1450,8 +1463,8 @@ class ClosedFormGraphFilter(GraphFilter):
         entry64 = L.entry("pgh_poly_run_batch_f64") if g64 is not None else None
         if entry64 is not None:
             coeffs = np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64)
-            out = _propagate_in_batches64(self, features, self._loop_cfg(0.0, False, 1.0), lambda P, R, cfg_ref, scales, res, norms: entry64(
-                g64._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res), raw=False)
+            out = _propagate_in_batches64(self, features, self._loop_cfg(0.0, False, 1.0), lambda P, R, cfg_ref, scales, res, norms: (entry64(
+                g64._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res), None), raw=False)
             if out is not None:
                 return out
         entry = L.entry("pgh_poly_run_batch") if g is not None else None

@@ -14,7 +14,12 @@ Every figure is the median of --reps (9) runs timed with pgh_timer_* (events on 
 included) in ONE process, the routes alternating, after a warm-up run of each; min..max is the spread.  The batch's per-column iteration
 counts and the largest difference between the two f64 routes' values, in f32 ulps, are reported with the times.  Needs an MI355X: there is no fallback.
 
-    python tools/batch64_bench.py --scale 23 --columns 64 --filter ppr [--tol 1e-10] [--out profiles/batch64/...log]
+--retire [levels ...] times the retiring f64 batch (``f64_retire=``, include/pgh_retire64.h; no levels: the engine's default list) as a
+third f64 route ("f64_retire") beside the two; --stages prints its report (stages, slab columns streamed against the plain batch's)
+to stderr; --routes names the routes to time (default: all).  PGH_MM64_PAIR=0 in the environment keeps the four-lane product in the
+ld == 2 stages.
+
+    python tools/batch64_bench.py --scale 23 --columns 64 --filter ppr [--tol 1e-10] [--retire] [--stages] [--out profiles/batch64/...log]
 """
 import argparse
 import json
@@ -39,6 +44,9 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-10)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--retire", type=int, nargs="*", default=None, metavar="LEVEL")
+    ap.add_argument("--stages", action="store_true")
+    ap.add_argument("--routes", nargs="+", default=None, choices=("f64_batch", "f64_columns", "f32_batch", "f64_retire"))
     args = ap.parse_args()
     if not 1 <= args.columns <= 64:
         raise SystemExit("--columns: 1 to 64 (one multi-seed run)")
@@ -50,6 +58,8 @@ def main():
     L.ensure_init()                                          # raises without an MI355X
     if L.entry("pgh_ppr_run_batch_f64") is None:
         raise SystemExit("the engine library lacks the entries of include/pgh_batch64.h")
+    if args.retire is not None and (args.filter == "heat" or L.entry("pgh_ppr_run_batch_f64_retire") is None):
+        raise SystemExit("--retire: the recursive filters, and a library with the entries of include/pgh_retire64.h")
     timer = Timer(L)
 
     adj = rmat_graph(args.scale, args.ef, seed=0, symmetrize=True, a=0.57, b=0.19, c=0.19)
@@ -75,10 +85,14 @@ def main():
         if batched is not None and (hasattr(r, "last_batches") and "f64" in r.last_batches[0][0]) != batched:
             raise SystemExit("the route under test was not taken")
         iterations = [c["iterations"] for c in r.last_batches[0]] if hasattr(r, "last_batches") else None
-        return iterations, out
+        return iterations, out, (r.last_batches[0][0].get("stages") if iterations else None)
 
     routes = dict(f64_batch=lambda: run(ranker(True), True), f64_columns=lambda: run(ranker(False), False),
                   f32_batch=lambda: run(ranker(False, tol=1e-6, dtype="float32"), None))
+    if args.retire is not None:
+        routes["f64_retire"] = lambda: run(ranker(True, f64_retire=args.retire or True), True)
+    if args.routes:
+        routes = {name: fn for name, fn in routes.items() if name in args.routes}
     samples, seen = {name: [] for name in routes}, {}
     for rep in range(args.reps + 1):                         # (the first round warms every code object and pooled block up)
         for name, fn in routes.items():
@@ -86,17 +100,40 @@ def main():
             if rep:
                 samples[name].append(ms)
     times = {name: summary(got) for name, got in samples.items()}
-    a, b = seen["f64_batch"][1].numpy(), seen["f64_columns"][1].numpy()
-    ulp = np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(np.float32)).astype(np.float64)
-    iterations = seen["f64_batch"][0]
-    ratio = times["f64_batch"]["median_ms"] / times["f64_columns"]["median_ms"]
     out = dict(tool="batch64_bench", filter=args.filter, tol=args.tol, scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz),
-               columns=args.columns, seeds=args.seeds, reps=args.reps,
-               iterations=dict(min=min(iterations), max=max(iterations), sorted=sorted(iterations)),
-               f32_batch_iterations=dict(min=min(seen["f32_batch"][0]), max=max(seen["f32_batch"][0])),
-               worst_difference_f32_ulp=float(np.max(np.abs(a - b) / ulp)),
-               ms_per_propagate=times, f64_batch_over_f64_columns=round(ratio, 4),
-               verdict="win" if ratio < 1.0 else "LOSS")
+               columns=args.columns, seeds=args.seeds, reps=args.reps)
+
+    def worst_ulp(x, y):
+        x, y = seen[x][1].numpy(), seen[y][1].numpy()
+        return float(np.max(np.abs(x - y) / np.spacing(np.maximum(np.abs(x), np.abs(y)).astype(np.float32)).astype(np.float64)))
+    batch = next((name for name in ("f64_batch", "f64_retire") if name in seen), None)
+    if batch is not None:
+        iterations = seen[batch][0]
+        out["iterations"] = dict(min=min(iterations), max=max(iterations), sorted=sorted(iterations))
+    if "f32_batch" in seen:
+        out["f32_batch_iterations"] = dict(min=min(seen["f32_batch"][0]), max=max(seen["f32_batch"][0]))
+    both = "f64_batch" in seen and "f64_columns" in seen                 # (every key of a run of all routes, in the order it always had)
+    if both:
+        out["worst_difference_f32_ulp"] = worst_ulp("f64_batch", "f64_columns")
+    out["ms_per_propagate"] = times
+    if both:
+        ratio = times["f64_batch"]["median_ms"] / times["f64_columns"]["median_ms"]
+        out.update(f64_batch_over_f64_columns=round(ratio, 4), verdict="win" if ratio < 1.0 else "LOSS")
+    if "f64_retire" in seen:
+        stages = seen["f64_retire"][2]
+        out.update(retire_levels=args.retire or "default", pair=os.environ.get("PGH_MM64_PAIR", "1") != "0", stages=stages)
+        for other in ("f64_batch", "f64_columns"):
+            if other in seen:
+                out["f64_retire_over_" + other] = round(times["f64_retire"]["median_ms"] / times[other]["median_ms"], 4)
+                out["f64_retire_worst_difference_from_%s_f32_ulp" % other] = worst_ulp("f64_retire", other)
+        if "f64_batch" in seen:
+            out["same_iterations_as_f64_batch"] = seen["f64_retire"][0] == seen["f64_batch"][0]
+            out["plain_column_steps"] = ((args.columns + 1) & ~1) * (max(seen["f64_batch"][0]) - 1)
+        if args.stages:
+            for ld, live, first in zip(stages["ld"], stages["live"], stages["first_step"]):
+                print("stage: ld %2d, %2d live columns, from step %d" % (ld, live, first), file=sys.stderr)
+            print("slab columns streamed: %d (the plain f64 batch: %s)" % (stages["column_steps"], out.get("plain_column_steps", "not run")),
+                  file=sys.stderr)
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:
