@@ -16,7 +16,7 @@
 #include "pgh_batch.h"
 #include "pgh_mixed.h"
 #include "pgh_retire.h"
-#include "pgh_mm_run.h"       // BatchState, the poll ring and the run-ahead driver (shared with pgh_spmm64.hip)
+#include "pgh_mm_retire.h"    // pgh_mm_run.h (BatchState, the poll ring, the run-ahead driver) and the retiring protocol (shared with pgh_spmm64.hip)
 
 #include <functional>
 #include <type_traits>
@@ -1128,7 +1128,8 @@ __global__ __launch_bounds__(WG) void k_mm_permute_out2(const float* __restrict_
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // A run that retires its converged columns (include/pgh_retire.h).  Between two steps: the stopped columns leave
-// (k_mm_retire_out), the live ones move into a narrower workspace (k_mm_repack) and the loop state follows them (k_mm_state_narrow).
+// (k_mm_retire_out), the live ones move into a narrower workspace (k_mm_repack) and the loop state follows them (k_mm_state_narrow,
+// pgh_mm_retire.h).
 //
 // k_mm_permute_out2 for SOME columns of the slab, each to a column of the caller's [n, dst_b] slab: lane j of the slab goes to column
 // cols.dst[j] (-1: stays) times cols.factor[j].  The arithmetic per value is k_mm_permute_out2's.
@@ -1214,33 +1215,6 @@ __global__ __launch_bounds__(WG) void k_mm_repack(Repack q, int64_t n_int, int l
         *reinterpret_cast<f32x4*>(q.x_n + to) = xo;
         if (fl & 1) *reinterpret_cast<f32x4*>(q.p_n + to) = po;
         if (fl == 0) *reinterpret_cast<f32x4*>(q.other_n + to) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
-
-// the lanes of the loop state follow their columns: lane i <- lane src.v[i] for i < b_new, the lanes beyond are done from the start (as
-// k_mm_state_init leaves them); the word that voided the enqueued steps is cleared
-struct ColMap {
-    int v[kLanes];
-};
-__global__ void k_mm_state_narrow(BatchState* state, ColMap src, int b_new) {
-    const int lane = threadIdx.x;
-    const int s = lane < b_new ? src.v[lane] : -1;
-    const double scale = s >= 0 ? state->scale[s] : 1.0, err = s >= 0 ? state->err[s] : 0.0, sum = s >= 0 ? state->sum[s] : 0.0;
-    const double pred_inv = s >= 0 ? state->pred_inv[s] : 1.0, pred_raw = s >= 0 ? state->pred_raw[s] : 0.0, sum_p = s >= 0 ? state->sum_p[s] : 0.0;
-    const int done = s >= 0 ? state->done[s] : 1, steps = s >= 0 ? state->steps[s] : 0, converged = s >= 0 ? state->converged[s] : 0;
-    __syncthreads();                                       // every lane has read before any lane writes
-    state->scale[lane] = scale;
-    state->err[lane] = err;
-    state->sum[lane] = sum;
-    state->pred_inv[lane] = pred_inv;
-    state->pred_raw[lane] = pred_raw;
-    state->sum_p[lane] = sum_p;
-    state->done[lane] = done;
-    state->steps[lane] = steps;
-    state->converged[lane] = converged;
-    if (lane == 0) {
-        state->paused = 0;
-        state->b = b_new;
     }
 }
 
@@ -1464,10 +1438,11 @@ int make_drop(pgh_graph_s* g, double rate, uint64_t seed, MMDrop* out, const MMD
     return 0;
 }
 int spmm_impl(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y, double rate, uint64_t seed);
-struct RetirePlan;
 int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, double rate, uint64_t seed0,
                pgh_loop_result* results, const f32x4* walk_rowop = nullptr, const double* col_alphas = nullptr,
                const char* who = "pgh_ppr_run_batch", RetirePlan* retire = nullptr);
+int ppr_entry(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results,
+              const char* who, const RetireArgs* ra);
 }  // namespace
 
 extern "C" int pgh_spmm(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y) { return spmm_impl(g, x, y, 0.0, 0); }
@@ -1523,7 +1498,7 @@ int spmm_impl(pgh_graph_t g, pgh_mat_t x, pgh_mat_t y, double rate, uint64_t see
 // at its own iteration (frozen afterwards), exactly as b calls of pgh_ppr_run would.
 extern "C" int pgh_ppr_run_batch(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
                                  pgh_loop_result* results) {
-    return batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results);
+    return ppr_entry(g, p, ranks, cfg, out_scales, results, "pgh_ppr_run_batch", nullptr);
 }
 // ... with graph_dropout (abstract_filters.py:61: a fresh mask for every step): step k of the batch multiplies by the matrix
 // masked with seed0 + k - 1, the mask pgh_spmv_dropout(seed0 + k - 1) would apply
@@ -1661,45 +1636,6 @@ struct MMRun : MMRunAhead {
         return 0;
     }
 };
-
-// The host's record of a run that retires its columns (include/pgh_retire.h): the levels, and the report as it grows.
-struct RetirePlan {
-    std::vector<int>  levels;        // strictly descending
-    pgh_retire_report report{};
-    // the live count at or below which a slab of width ld narrows (0: never): the greatest level below ld, and a narrower slab results
-    int trigger(int ld, int stages) const {
-        if (stages >= PGH_RETIRE_MAX_STAGES) return 0;
-        for (int level : levels)
-            if (level < ld) return level < ld - 4 ? level : ld - 4;
-        return 0;
-    }
-    void stage(int ld, int live, int first_step) {
-        const int s = report.num_stages;
-        if (s > 0) report.column_steps += (int64_t)report.ld[s - 1] * (first_step - report.first_step[s - 1]);
-        report.ld[s] = ld;
-        report.live[s] = live;
-        report.first_step[s] = first_step;
-        report.num_stages = s + 1;
-    }
-    void close(int executed) {
-        const int s = report.num_stages - 1;
-        report.column_steps += (int64_t)report.ld[s] * (executed + 1 - report.first_step[s]);
-    }
-};
-// null levels (num_levels != 0): {32, 16, 8, 4}
-int make_retire_plan(const int32_t* levels, int32_t num_levels, const char* who, RetirePlan* plan) {
-    if (levels == nullptr && num_levels != 0) {
-        plan->levels = {32, 16, 8, 4};
-        return 0;
-    }
-    PGH_CHECK(num_levels >= 0 && num_levels < kLanes, std::string(who) + ": the number of levels must be in [0, 63]");
-    for (int i = 0; i < num_levels; ++i) {
-        PGH_CHECK(levels[i] >= 1 && levels[i] < kLanes && (i == 0 || levels[i] < levels[i - 1]),
-                  std::string(who) + ": the levels must be strictly descending live-column counts in [1, 63]");
-        plan->levels.push_back(levels[i]);
-    }
-    return 0;
-}
 
 // walk_rowop (null for PageRank): the row words of an absorbing walk (k_mm_walk_rowops); the step is then k_mm_step<., true> with
 // a = the quotient alone, and the residual comes from the separate kernel (the in-kernel prediction is PageRank's column sums)
@@ -1865,28 +1801,18 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         PGH_TRY(run.run_ahead(max_steps, enqueue_step, on_pause));
         return run.finish(true, nullptr, cfg, out_scales, ranks->data, 1, flags, results);
     }
-    // A run that retires its columns (include/pgh_retire.h).  col_of[i]: the caller's column in lane i of the current slabs.  A column
-    // leaves once, at the narrowing that follows its stop or at the end, and its part of the loop state is kept for results[].
-    const int width = b;                                             // the caller's row length
-    int col_of[kLanes];
-    for (int j = 0; j < kLanes; ++j) col_of[j] = j < b ? j : -1;
-    BatchState kept{};                                               // lanes indexed by the caller's column
+    // A run that retires its columns (include/pgh_retire.h, the protocol of pgh_mm_retire.h).
+    RetireLedger ledger(b, 4);
     PoolBuf wide[4];                                                 // what a narrowing hands back to the pool when this frame ends
     auto retire_lanes = [&](const BatchState& hs, bool all) {        // the lanes that have stopped (all: every lane) leave from the last iterate
         RetireCols cols;
-        for (int j = 0; j < kLanes; ++j) {
-            cols.dst[j] = -1;
-            cols.factor[j] = 1.f;
-            if (j >= b || !(all || hs.done[j])) continue;
-            const int c = col_of[j];
+        for (int j = 0; j < kLanes; ++j) cols.dst[j] = -1, cols.factor[j] = 1.f;
+        ledger.leave(hs, b, all, [&](int j, int c, double quotient) {
             cols.dst[j] = c;
-            cols.factor[j] = (float)(hs.scale[j] * (out_scales ? out_scales[c] : cfg->out_scale));
-            kept.steps[c] = hs.steps[j];
-            kept.converged[c] = hs.converged[j];
-            kept.err[c] = hs.err[j];
-        }
+            cols.factor[j] = (float)(quotient * (out_scales ? out_scales[c] : cfg->out_scale));
+        });
         k_mm_retire_out<<<blocks_for(n_int * lanes_per_row(ld)), WG, 0, r.stream>>>(buf[hs.executed & 1], rowop, f.perm, n_int, n, ld, cols,
-                                                                                  ranks->data, width, row_flags);
+                                                                                  ranks->data, ledger.width, row_flags);
     };
     auto narrow = [&](int k) -> int {
         BatchState hs;
@@ -1894,22 +1820,17 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         PGH_HIP(hipStreamSynchronize(r.stream));
         retire_lanes(hs, false);
         Repack q{};
-        ColMap map{};
+        ColMap map;
         int nb = 0;
-        for (int j = 0; j < kLanes; ++j) q.src[j] = map.v[j] = -1;
-        for (int j = 0; j < b; ++j)
-            if (!hs.done[j]) q.src[nb] = map.v[nb] = j, ++nb;
-        const int nld = (nb + 3) & ~3;
-        PGH_CHECK(nb >= 1 && nld < ld && hs.executed == k, std::string(who) + ": the loop state does not ask for a narrowing");
-        // the narrow workspace comes from the pool; the wide one goes back with this frame (the stream is still reading it)
+        PGH_TRY(ledger.live_map(hs, b, ld, k, who, &map, &nb));
+        memcpy(q.src, map.v, sizeof(q.src));
+        const int nld = ledger.padded(nb);
+        // the narrow workspace comes from the pool; the wide one goes back with this frame (the stream is still reading it; the stage
+        // before: the wait above was behind its last reader)
         const size_t slab = sizeof(float) * (size_t)n_int * nld;
         PoolBuf* mine[4] = {&run.extra, &run.xg0, &run.xg1, &run.sums};
-        for (int i = 0; i < 4; ++i) {
-            if (wide[i].p != nullptr) pool_free(wide[i].p);          // (the stage before: the wait above was behind its last reader)
-            wide[i].p = mine[i]->p;
-            mine[i]->p = nullptr;
-            PGH_TRY(mine[i]->alloc(slab));
-        }
+        const size_t bytes[4] = {slab, slab, slab, slab};
+        PGH_TRY(pool_renew(mine, bytes, 4, wide));
         float* nbuf[2] = {run.xg0.as<float>(), run.xg1.as<float>()};
         q.p_w = pint;
         q.x_w = buf[hs.executed & 1];
@@ -1922,13 +1843,9 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
         if (!run.skip_dead) PGH_HIP(hipMemsetAsync(run.sums.p, 0, slab, r.stream));
         k_mm_state_narrow<<<1, kLanes, 0, r.stream>>>(state, map, nb);
         PGH_HIP(hipGetLastError());
-        ColAlphas alphas_now = mixed_alphas;
-        int cols_now[kLanes];
-        memcpy(cols_now, col_of, sizeof(cols_now));
-        for (int j = 0; j < kLanes; ++j) {
-            col_of[j] = j < nb ? cols_now[map.v[j]] : -1;
-            mixed_alphas.v[j] = (mixed && j < nb) ? alphas_now.v[map.v[j]] : 0.0;
-        }
+        const ColAlphas alphas_now = mixed_alphas;
+        for (int j = 0; j < kLanes; ++j) mixed_alphas.v[j] = (mixed && j < nb) ? alphas_now.v[map.v[j]] : 0.0;
+        ledger.follow(map, nb);
         retire->stage(nld, nb, k + 1);
         run.buf[0] = nbuf[0];
         run.buf[1] = nbuf[1];
@@ -1943,9 +1860,7 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     PGH_TRY(run.run_ahead(max_steps, enqueue_step, on_pause, narrow));
     if (retire->report.num_stages == 1) {                            // never narrowed: the plain way out
         PGH_TRY(run.finish(true, nullptr, cfg, out_scales, ranks->data, 1, flags, results));
-        int executed = 0;
-        for (int j = 0; j < b; ++j) executed = results[j].spmv_count > executed ? results[j].spmv_count : executed;
-        retire->close(executed);
+        retire->close(executed_steps(results, b));
         return 0;
     }
     BatchState hs;
@@ -1956,15 +1871,8 @@ int batch_impl(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* 
     double ms = 0.0;
     PGH_TRY(run.timer.stop(&ms));
     retire->close(hs.executed);
-    for (int j = 0; j < width; ++j) {
-        memset(&results[j], 0, sizeof(pgh_loop_result));
-        results[j].iterations = 1 + kept.steps[j];
-        results[j].converged = kept.converged[j];
-        results[j].spmv_count = kept.steps[j];
-        results[j].last_error = kept.err[j];
-        results[j].loop_ms = ms;
-        results[j].flags = flags | PGH_RETIRE_NARROWED;
-    }
+    ledger.fill(results, ms);
+    for (int j = 0; j < ledger.width; ++j) results[j].flags |= flags;
     return 0;
 }
 }  // namespace
@@ -2052,24 +1960,6 @@ __global__ __launch_bounds__(WG) void k_mm_poly_init(float* __restrict__ res, co
         for (int w = 0; w < WG / 64; ++w) t = linf ? fmax(t, s_red[w][lane]) : t + s_red[w][lane];
         partial[(int64_t)blockIdx.x * kLanes + lane] = t;
     }
-}
-
-// the single-vector loop's host-side check at iteration 2 (convergence.py:96-101 on delta_1), per column
-__global__ void k_mm_poly_first(BatchState* __restrict__ state, const double* __restrict__ err1, int check, int err_kind, double tol, long long n) {
-    const int lane = threadIdx.x;
-    int done = 1;
-    if (lane < state->b) {
-        double e = err1[lane];
-        if (err_kind == PGH_ERR_MABS && n > 0) e /= (double)n;
-        state->err[lane] = e;
-        if (check && e <= tol) {
-            state->done[lane] = 1;
-            state->converged[lane] = 1;
-        }
-        done = state->done[lane];
-    }
-    const unsigned long long all = __ballot(done != 0);
-    if (lane == 0) state->all_done = (all == ~0ULL) ? 1 : 0;
 }
 
 // One Taylor step of every column (ClosedFormGraphFilter._step, abstract_filters.py:248-256, as pgh_poly_run's EPI_POLY epilogue):
@@ -2180,7 +2070,7 @@ int check_batch_shapes(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop
 }
 
 int walk_batch(pgh_graph_t g, pgh_mat_t p, const float* lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
-               pgh_loop_result* results, const char* who = "pgh_ppr_run_batch", RetirePlan* retire = nullptr) {
+               pgh_loop_result* results, const char* who, RetirePlan* retire) {
     PGH_CHECK(g->degrees != nullptr, "the absorbing walks need the graph's degrees");
     PGH_TRY(ensure_mm_layout(g));
     const BsfFormat& f = g->bsf_mm;
@@ -2204,19 +2094,28 @@ int walk_batch(pgh_graph_t g, pgh_mat_t p, const float* lam, pgh_mat_t ranks, co
 
 }  // namespace
 
+// the checks of the two walks' entries and of their retiring siblings (include/pgh_retire.h; ra null: a plain entry), which validate the
+// levels before the shapes; lam: the absorption (absorb) or null (the symmetric walk)
+namespace {
+int walk_entry(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, bool absorb, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+               pgh_loop_result* results, const char* who, const RetireArgs* ra) {
+    PGH_CHECK(results && (lam || !absorb), std::string(who) + ": null argument");
+    RetirePlan plan;
+    if (ra != nullptr) PGH_TRY(plan.init(ra->levels, ra->num_levels, who, 4, {32, 16, 8, 4}));
+    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
+    if (absorb) PGH_CHECK(lam->n == g->n_cols, std::string(who) + ": absorption length mismatch");
+    return retire_report_out(walk_batch(g, p, absorb ? lam->data : nullptr, ranks, cfg, out_scales, results, who, ra != nullptr ? &plan : nullptr),
+                             plan, ra);
+}
+}  // namespace
+
 extern "C" int pgh_absorb_run_batch(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
                                     const double* out_scales, pgh_loop_result* results) {
-    PGH_CHECK(results && lam, "pgh_absorb_run_batch: null argument");
-    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, "pgh_absorb_run_batch"));
-    PGH_CHECK(lam->n == g->n_cols, "pgh_absorb_run_batch: absorption length mismatch");
-    return walk_batch(g, p, lam->data, ranks, cfg, out_scales, results);
+    return walk_entry(g, p, lam, true, ranks, cfg, out_scales, results, "pgh_absorb_run_batch", nullptr);
 }
-
 extern "C" int pgh_sarw_run_batch(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
                                   pgh_loop_result* results) {
-    PGH_CHECK(results, "pgh_sarw_run_batch: null argument");
-    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, "pgh_sarw_run_batch"));
-    return walk_batch(g, p, nullptr, ranks, cfg, out_scales, results);
+    return walk_entry(g, p, nullptr, false, ranks, cfg, out_scales, results, "pgh_sarw_run_batch", nullptr);
 }
 
 // The Taylor form of pgh_poly_run for b columns: iteration `it` uses coeffs[it - 1] (0 beyond num_coeffs), iteration 1 is result_1 =
@@ -2333,11 +2232,33 @@ int check_mixed(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop_cfg* c
 }
 }  // namespace
 
+namespace {
+// pgh_ppr_run_batch and its retiring sibling (ra null: the plain entry, which leaves every check to batch_impl: a graph the loops do not
+// serve is an error there, not declined)
+int ppr_entry(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results,
+              const char* who, const RetireArgs* ra) {
+    RetirePlan plan;
+    if (ra != nullptr) {
+        PGH_CHECK(results, std::string(who) + ": null argument");
+        PGH_TRY(plan.init(ra->levels, ra->num_levels, who, 4, {32, 16, 8, 4}));
+        PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
+    }
+    return retire_report_out(batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, nullptr, who, ra != nullptr ? &plan : nullptr), plan, ra);
+}
+// pgh_ppr_run_batch_mixed and its retiring sibling (ra null: the plain entry), which validates the levels first
+int mixed_ppr_entry(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* alphas, const double* out_scales,
+                    pgh_loop_result* results, const char* who, const RetireArgs* ra) {
+    RetirePlan plan;
+    if (ra != nullptr) PGH_TRY(plan.init(ra->levels, ra->num_levels, who, 4, {32, 16, 8, 4}));
+    PGH_TRY(check_mixed(g, p, ranks, cfg, alphas, results, who));
+    for (int j = 0; j < p->b; ++j) PGH_CHECK(std::isfinite(alphas[j]), std::string(who) + ": a non-finite alpha");
+    return retire_report_out(batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, alphas, who, ra != nullptr ? &plan : nullptr), plan, ra);
+}
+}  // namespace
+
 extern "C" int pgh_ppr_run_batch_mixed(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* alphas,
                                        const double* out_scales, pgh_loop_result* results) {
-    PGH_TRY(check_mixed(g, p, ranks, cfg, alphas, results, "pgh_ppr_run_batch_mixed"));
-    for (int j = 0; j < p->b; ++j) PGH_CHECK(std::isfinite(alphas[j]), "pgh_ppr_run_batch_mixed: a non-finite alpha");
-    return batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, alphas, "pgh_ppr_run_batch_mixed");
+    return mixed_ppr_entry(g, p, ranks, cfg, alphas, out_scales, results, "pgh_ppr_run_batch_mixed", nullptr);
 }
 
 extern "C" int pgh_poly_run_batch_mixed(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
@@ -2349,57 +2270,31 @@ extern "C" int pgh_poly_run_batch_mixed(pgh_graph_t g, pgh_mat_t p, const double
 }
 
 // =================================================================================================
-// The loops of batch_impl in the mode that retires converged columns (include/pgh_retire.h): the plain sibling's checks, the levels,
-// and the report once the run has ended.  What the sibling declines or does not serve is declined here with nothing written.
+// The loops of batch_impl in the mode that retires converged columns (include/pgh_retire.h): the plain sibling's checks with the levels
+// in front of them, and the report once the run has ended.  What the sibling declines or does not serve is declined here with nothing
+// written.
 // =================================================================================================
-namespace {
-int retire_report_out(int status, const RetirePlan& plan, pgh_retire_report* report) {
-    if (status == 0 && report != nullptr) *report = plan.report;
-    return status;
-}
-}  // namespace
-
 extern "C" int pgh_ppr_run_batch_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
                                         pgh_loop_result* results, const int32_t* levels, int32_t num_levels, pgh_retire_report* report) {
-    const char* who = "pgh_ppr_run_batch_retire";
-    PGH_CHECK(results, std::string(who) + ": null argument");
-    RetirePlan plan;
-    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
-    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
-    return retire_report_out(batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, nullptr, who, &plan), plan, report);
+    const RetireArgs ra{levels, num_levels, report};
+    return ppr_entry(g, p, ranks, cfg, out_scales, results, "pgh_ppr_run_batch_retire", &ra);
 }
-
 extern "C" int pgh_ppr_run_batch_mixed_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* alphas,
                                               const double* out_scales, pgh_loop_result* results, const int32_t* levels, int32_t num_levels,
                                               pgh_retire_report* report) {
-    const char* who = "pgh_ppr_run_batch_mixed_retire";
-    RetirePlan plan;
-    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
-    PGH_TRY(check_mixed(g, p, ranks, cfg, alphas, results, who));
-    for (int j = 0; j < p->b; ++j) PGH_CHECK(std::isfinite(alphas[j]), std::string(who) + ": a non-finite alpha");
-    return retire_report_out(batch_impl(g, p, ranks, cfg, out_scales, 0.0, 0, results, nullptr, alphas, who, &plan), plan, report);
+    const RetireArgs ra{levels, num_levels, report};
+    return mixed_ppr_entry(g, p, ranks, cfg, alphas, out_scales, results, "pgh_ppr_run_batch_mixed_retire", &ra);
 }
-
 extern "C" int pgh_absorb_run_batch_retire(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
                                            const double* out_scales, pgh_loop_result* results, const int32_t* levels, int32_t num_levels,
                                            pgh_retire_report* report) {
-    const char* who = "pgh_absorb_run_batch_retire";
-    PGH_CHECK(results && lam, std::string(who) + ": null argument");
-    RetirePlan plan;
-    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
-    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
-    PGH_CHECK(lam->n == g->n_cols, std::string(who) + ": absorption length mismatch");
-    return retire_report_out(walk_batch(g, p, lam->data, ranks, cfg, out_scales, results, who, &plan), plan, report);
+    const RetireArgs ra{levels, num_levels, report};
+    return walk_entry(g, p, lam, true, ranks, cfg, out_scales, results, "pgh_absorb_run_batch_retire", &ra);
 }
-
 extern "C" int pgh_sarw_run_batch_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
                                          pgh_loop_result* results, const int32_t* levels, int32_t num_levels, pgh_retire_report* report) {
-    const char* who = "pgh_sarw_run_batch_retire";
-    PGH_CHECK(results, std::string(who) + ": null argument");
-    RetirePlan plan;
-    PGH_TRY(make_retire_plan(levels, num_levels, who, &plan));
-    PGH_TRY(check_batch_shapes(g, p, ranks, cfg, who));
-    return retire_report_out(walk_batch(g, p, nullptr, ranks, cfg, out_scales, results, who, &plan), plan, report);
+    const RetireArgs ra{levels, num_levels, report};
+    return walk_entry(g, p, nullptr, false, ranks, cfg, out_scales, results, "pgh_sarw_run_batch_retire", &ra);
 }
 
 // =================================================================================================

@@ -15,7 +15,7 @@
 #include "pgh_kernels.h"
 #include "pgh_batch64.h"
 #include "pgh_retire64.h"
-#include "pgh_mm_run.h"
+#include "pgh_mm_retire.h"
 
 #include <cmath>
 
@@ -554,7 +554,8 @@ __global__ void k_mm64_state_init(BatchState* state, int b, ColFactors scale0, i
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // A run that retires its converged columns (include/pgh_retire64.h).  Between two steps the stopped columns leave
-// (k_mm64_retire_out), the live ones move into narrower slabs (k_mm64_repack) and the loop state follows them (k_mm64_state_narrow).
+// (k_mm64_retire_out), the live ones move into narrower slabs (k_mm64_repack) and the loop state follows them (k_mm_state_narrow,
+// pgh_mm_retire.h).
 //
 // k_mm64_way_out<float> for SOME columns of the slab, each to a column of the caller's [n, dst_b] slab: lane column j goes to column
 // cols.dst[j] (-1: stays) times cols.factor[j] in f64, rounded once.
@@ -625,47 +626,6 @@ __global__ __launch_bounds__(WG) void k_mm64_repack(Repack64 q, int64_t n_int, i
     }
 }
 
-// the lanes of the loop state follow their columns: lane i <- lane src.v[i] for i < b_new, the lanes beyond are done from the start (as
-// k_mm64_state_init leaves them); the word that voided the enqueued steps is cleared
-struct ColMap64 {
-    int v[kLanes];
-};
-__global__ void k_mm64_state_narrow(BatchState* state, ColMap64 src, int b_new) {
-    const int lane = threadIdx.x;
-    const int s = lane < b_new ? src.v[lane] : -1;
-    const double scale = s >= 0 ? state->scale[s] : 1.0, err = s >= 0 ? state->err[s] : 0.0, sum = s >= 0 ? state->sum[s] : 0.0;
-    const int done = s >= 0 ? state->done[s] : 1, steps = s >= 0 ? state->steps[s] : 0, converged = s >= 0 ? state->converged[s] : 0;
-    __syncthreads();                                       // every lane has read before any lane writes
-    state->scale[lane] = scale;
-    state->err[lane] = err;
-    state->sum[lane] = sum;
-    state->done[lane] = done;
-    state->steps[lane] = steps;
-    state->converged[lane] = converged;
-    if (lane == 0) {
-        state->paused = 0;
-        state->b = b_new;
-    }
-}
-
-// a closed-form run's check of iteration 2 (convergence.py:96-101 on delta_1 = |result_1|), per column
-__global__ void k_mm64_poly_first(BatchState* __restrict__ state, const double* __restrict__ err1, int check, int err_kind, double tol, long long n) {
-    const int lane = threadIdx.x;
-    int done = 1;
-    if (lane < state->b) {
-        double e = err1[lane];
-        if (err_kind == PGH_ERR_MABS && n > 0) e /= (double)n;
-        state->err[lane] = e;
-        if (check && e <= tol) {
-            state->done[lane] = 1;
-            state->converged[lane] = 1;
-        }
-        done = state->done[lane];
-    }
-    const unsigned long long all = __ballot(done != 0);
-    if (lane == 0) state->all_done = (all == ~0ULL) ? 1 : 0;
-}
-
 // One taylor step of every column (pgh_poly_run's form 2): term_k = U_r * sum, the next gather row term_k * G_r, result += c_k * term_k
 // for the columns still running, and the workgroup's change |result_new - result_old| per column (sum or max)
 __global__ __launch_bounds__(WG) void k_mm64_poly_step(const double* __restrict__ sums, const RowOp64* __restrict__ rowop, double* __restrict__ result,
@@ -723,36 +683,48 @@ __global__ __launch_bounds__(WG) void k_mm64_poly_step(const double* __restrict_
 struct MM64Run : MMRunAhead {
     pgh_graph_s* const g;
     const BsfFormat&   f;
-    int                b, ld;           // (a run that retires columns narrows them: narrow_to)
+    int                b, ld = 0;       // (a run that retires columns narrows them: narrow_to)
     const int64_t      n, n_int;
-    size_t             slab;            // bytes of one [n_int, ld] slab of doubles
+    size_t             slab = 0;        // bytes of one [n_int, ld] slab of doubles
     const int          cgrid;
-    int                row_grid;
+    int                row_grid = 0, num_slabs = 0;
     bool               pair = false;    // the product of a slab with ld == 2 takes the pair form (k_mm64_partial_pair)
     PoolBuf   rowop, bad, slabs[5], head, tail, partial, folded, state_mem;
     LoopTimer timer;
 
-    MM64Run(pgh_graph_s* graph, int width)
-        : g(graph), f(graph->bsf_mm), b(width), ld((width + 1) & ~1), n(graph->n_cols), n_int(f.n_out),
-          slab(sizeof(double) * (size_t)n_int * ld), cgrid(rt().num_cus * 8), row_grid(blocks_for(n_int * lanes_per_row64(ld))) {}
+    MM64Run(pgh_graph_s* graph, int width) : g(graph), f(graph->bsf_mm), b(width), n(graph->n_cols), n_int(f.n_out), cgrid(rt().num_cus * 8) {}
 
     double*  s(int i) { return slabs[i].as<double>(); }
     RowOp64* ops() { return rowop.as<RowOp64>(); }
     double*  fold(int i) { return folded.as<double>() + (size_t)i * kLanes; }
 
-    // num_slabs slabs beside the row sums (slabs[0]); the sums and the head carries start as zeros: a row without entries keeps its
-    // zero sum, a tile without a head piece adds none
-    int alloc(int num_slabs, bool with_state) {
-        PGH_TRY(rowop.alloc(sizeof(RowOp64) * (size_t)n_int));
-        PGH_TRY(bad.alloc(sizeof(int)));
-        for (int i = 0; i <= num_slabs; ++i) PGH_TRY(slabs[i].alloc(slab));
+    // The slabs (the row sums, slabs[0], and num_slabs beside them) and both carries for `width` columns, from the pool in that order;
+    // the sums and the head carries start as zeros: a row without entries is never written by the product and keeps its zero sum
+    // (k_mm64_step reads it), a tile without a head piece adds none.  wide: pool_renew's.
+    int take_slabs(int width, PoolBuf* wide) {
+        b = width;
+        ld = (width + 1) & ~1;
+        slab = sizeof(double) * (size_t)n_int * ld;
+        row_grid = blocks_for(n_int * lanes_per_row64(ld));
         const size_t carries = sizeof(double) * (size_t)(f.num_tiles + 1) * ld;
-        PGH_TRY(head.alloc(carries));
-        PGH_TRY(tail.alloc(carries));
-        PGH_TRY(partial.alloc(sizeof(double) * (size_t)cgrid * kLanes));
-        PGH_TRY(folded.alloc(sizeof(double) * 2 * kLanes));
+        PoolBuf* mine[7];
+        size_t   bytes[7];
+        for (int i = 0; i <= num_slabs; ++i) mine[i] = &slabs[i], bytes[i] = slab;
+        mine[num_slabs + 1] = &head;
+        mine[num_slabs + 2] = &tail;
+        bytes[num_slabs + 1] = bytes[num_slabs + 2] = carries;
+        PGH_TRY(pool_renew(mine, bytes, num_slabs + 3, wide));
         PGH_HIP(hipMemsetAsync(slabs[0].p, 0, slab, rt().stream));
         PGH_HIP(hipMemsetAsync(head.p, 0, carries, rt().stream));
+        return 0;
+    }
+    int alloc(int slabs_beside_sums, bool with_state) {
+        num_slabs = slabs_beside_sums;
+        PGH_TRY(rowop.alloc(sizeof(RowOp64) * (size_t)n_int));
+        PGH_TRY(bad.alloc(sizeof(int)));
+        PGH_TRY(take_slabs(b, nullptr));
+        PGH_TRY(partial.alloc(sizeof(double) * (size_t)cgrid * kLanes));
+        PGH_TRY(folded.alloc(sizeof(double) * 2 * kLanes));
         PGH_HIP(hipMemsetAsync(folded.p, 0, sizeof(double) * 2 * kLanes, rt().stream));
         if (with_state) {
             PGH_TRY(state_mem.alloc(sizeof(BatchState)));
@@ -774,9 +746,36 @@ struct MM64Run : MMRunAhead {
         *is_bad = h_bad != 0;
         return 0;
     }
+    // One form of the product pass, LPR lanes per row (k_mm64_partial) or 0: the pair form, as many workgroups as the registers let the
+    // CUs hold (persistent).
+    template <bool HAS_VAL, int LPR>
+    int partial_pass(const MM64View& v, const double* xg) {
+        static int per_cu = 0;
+        const void* kernel;
+        if constexpr (LPR == 0) kernel = (const void*)k_mm64_partial_pair<HAS_VAL>;
+        else kernel = (const void*)k_mm64_partial<HAS_VAL, LPR>;
+        if (per_cu == 0) {
+            PGH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, WG, 0));
+            if (per_cu < 1) per_cu = 1;
+        }
+        const int grid = rt().num_cus * per_cu;
+        ProfScope prof(PGH_K_SPMM);
+        if constexpr (LPR == 0) k_mm64_partial_pair<HAS_VAL><<<grid, WG, 0, rt().stream>>>(v, xg, s(0), state);
+        else k_mm64_partial<HAS_VAL, LPR><<<grid, WG, 0, rt().stream>>>(v, xg, ld, s(0), state);
+        return 0;
+    }
+    template <bool HAS_VAL>
+    int partial_pass(const MM64View& v, const double* xg) {
+        if (pair && ld == 2) return partial_pass<HAS_VAL, 0>(v, xg);
+        switch (lanes_per_row64(ld)) {
+            case 32: return partial_pass<HAS_VAL, 32>(v, xg);
+            case 16: return partial_pass<HAS_VAL, 16>(v, xg);
+            case 8: return partial_pass<HAS_VAL, 8>(v, xg);
+            default: return partial_pass<HAS_VAL, 4>(v, xg);
+        }
+    }
     // slabs[0] <- the row sums of the stream times the gather slab xg
     int product(const double* xg) {
-        Runtime& r = rt();
         MM64View v;
         v.colf = f.colf;
         v.val = f.val;
@@ -786,79 +785,17 @@ struct MM64Run : MMRunAhead {
         v.head = head.as<double>();
         v.tail = tail.as<double>();
         v.num_tiles = f.num_tiles;
-        const int lpr = lanes_per_row64(ld);
-        if (pair && ld == 2) {
-            static int pair_per_cu[2] = {0, 0};
-            int& per_cu = pair_per_cu[f.val ? 1 : 0];
-            if (per_cu == 0) {
-                const void* kernel = f.val ? (const void*)k_mm64_partial_pair<true> : (const void*)k_mm64_partial_pair<false>;
-                PGH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, WG, 0));
-                if (per_cu < 1) per_cu = 1;
-            }
-            const int grid = r.num_cus * per_cu;           // persistent, a wavefront per tile in flight
-            {
-                ProfScope prof(PGH_K_SPMM);
-                if (f.val) k_mm64_partial_pair<true><<<grid, WG, 0, r.stream>>>(v, xg, s(0), state);
-                else k_mm64_partial_pair<false><<<grid, WG, 0, r.stream>>>(v, xg, s(0), state);
-            }
-            {
-                ProfScope prof(PGH_K_FIXUP);
-                k_mm64_fixup<<<blocks_for((int64_t)f.num_tiles * lpr, 64), WG, 0, r.stream>>>(v, ld, s(0), state);
-            }
-            PGH_HIP(hipGetLastError());
-            return 0;
-        }
-        const int which = (f.val ? 4 : 0) + (lpr == 32 ? 0 : (lpr == 16 ? 1 : (lpr == 8 ? 2 : 3)));
-        const void* kernels[8] = {(const void*)k_mm64_partial<false, 32>, (const void*)k_mm64_partial<false, 16>, (const void*)k_mm64_partial<false, 8>,
-                                  (const void*)k_mm64_partial<false, 4>,  (const void*)k_mm64_partial<true, 32>,  (const void*)k_mm64_partial<true, 16>,
-                                  (const void*)k_mm64_partial<true, 8>,   (const void*)k_mm64_partial<true, 4>};
-        static int per_cu_of[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int& per_cu = per_cu_of[which];
-        if (per_cu == 0) {
-            PGH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernels[which], WG, 0));
-            if (per_cu < 1) per_cu = 1;
-        }
-        const int grid = r.num_cus * per_cu;               // persistent: as many workgroups as the registers let a CU hold
-        {
-            ProfScope prof(PGH_K_SPMM);
-            switch (which) {
-                case 0: k_mm64_partial<false, 32><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-                case 1: k_mm64_partial<false, 16><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-                case 2: k_mm64_partial<false, 8><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-                case 3: k_mm64_partial<false, 4><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-                case 4: k_mm64_partial<true, 32><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-                case 5: k_mm64_partial<true, 16><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-                case 6: k_mm64_partial<true, 8><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-                default: k_mm64_partial<true, 4><<<grid, WG, 0, r.stream>>>(v, xg, ld, s(0), state); break;
-            }
-        }
+        PGH_TRY(f.val ? partial_pass<true>(v, xg) : partial_pass<false>(v, xg));
         {
             ProfScope prof(PGH_K_FIXUP);
-            k_mm64_fixup<<<blocks_for((int64_t)f.num_tiles * lpr, 64), WG, 0, r.stream>>>(v, ld, s(0), state);
+            k_mm64_fixup<<<blocks_for((int64_t)f.num_tiles * lanes_per_row64(ld), 64), WG, 0, rt().stream>>>(v, ld, s(0), state);
         }
         PGH_HIP(hipGetLastError());
         return 0;
     }
-    // A run that retires columns moves into slabs of `width` columns: every slab and both carries again, the row sums and the head
-    // carries as zeros (as alloc leaves them: a row without entries is never written by the product and k_mm64_step reads it).  The wide
-    // blocks move to `wide`; what `wide` held goes back to the pool (the caller has waited for the stream since their last reader).
-    int narrow_to(int width, PoolBuf (&wide)[7]) {
-        b = width;
-        ld = (width + 1) & ~1;
-        slab = sizeof(double) * (size_t)n_int * ld;
-        row_grid = blocks_for(n_int * lanes_per_row64(ld));
-        const size_t carries = sizeof(double) * (size_t)(f.num_tiles + 1) * ld;
-        PoolBuf* mine[7] = {&slabs[0], &slabs[1], &slabs[2], &slabs[3], &slabs[4], &head, &tail};
-        for (int i = 0; i < 7; ++i) {
-            if (wide[i].p != nullptr) pool_free(wide[i].p);
-            wide[i].p = mine[i]->p;
-            mine[i]->p = nullptr;
-            PGH_TRY(mine[i]->alloc(i < 5 ? slab : carries));
-        }
-        PGH_HIP(hipMemsetAsync(slabs[0].p, 0, slab, rt().stream));
-        PGH_HIP(hipMemsetAsync(head.p, 0, carries, rt().stream));
-        return 0;
-    }
+    // A run that retires columns moves into slabs of `width` columns: every slab and both carries again.  The wide blocks move to `wide`;
+    // what `wide` held goes back to the pool (the caller has waited for the stream since their last reader).
+    int narrow_to(int width, PoolBuf (&wide)[7]) { return take_slabs(width, wide); }
     // The way out: `result` times the column's factor (the state's quotient when state_scale, times its output scale), rounded once
     // to f32.  A column reports first_iterations + its steps; a zero column (zero[j]) reports nothing.
     int finish(bool state_scale, const double* result, const pgh_loop_cfg* cfg, const double* out_scales, const double* in_norms, float* dst,
@@ -906,52 +843,9 @@ int check64_mats(pgh_graph_t g, pgh_mat_t p, pgh_mat_t out, const pgh_loop_cfg* 
     return 0;
 }
 
-// The host's record of a run that retires its columns (include/pgh_retire64.h): the levels, and the report as it grows.  The rule of
-// pgh_spmm.hip's RetirePlan for slabs that are whole PAIRS of doubles.
-struct Retire64Plan {
-    std::vector<int>  levels;        // strictly descending
-    pgh_retire_report report{};
-    bool              pair = true;   // PGH_MM64_PAIR, read per call: the product of a stage with ld == 2 takes the pair form
-    // the live count at or below which a slab of width ld narrows (0: never): the greatest level below ld, and a narrower slab results
-    int trigger(int ld, int stages) const {
-        if (stages >= PGH_RETIRE_MAX_STAGES) return 0;
-        for (int level : levels)
-            if (level < ld) return level < ld - 2 ? level : ld - 2;
-        return 0;
-    }
-    void stage(int ld, int live, int first_step) {
-        const int s = report.num_stages;
-        if (s > 0) report.column_steps += (int64_t)report.ld[s - 1] * (first_step - report.first_step[s - 1]);
-        report.ld[s] = ld;
-        report.live[s] = live;
-        report.first_step[s] = first_step;
-        report.num_stages = s + 1;
-    }
-    void close(int executed) {
-        const int s = report.num_stages - 1;
-        report.column_steps += (int64_t)report.ld[s] * (executed + 1 - report.first_step[s]);
-    }
-    // null levels (num_levels != 0): {32, 16, 8, 4, 2}
-    int init(const int32_t* given, int32_t num_levels, const char* who) {
-        const char* env = getenv("PGH_MM64_PAIR");
-        pair = !(env != nullptr && env[0] == '0');
-        if (given == nullptr && num_levels != 0) {
-            levels = {32, 16, 8, 4, 2};
-            return 0;
-        }
-        PGH_CHECK(num_levels >= 0 && num_levels < kLanes, std::string(who) + ": the number of levels must be in [0, 63]");
-        for (int i = 0; i < num_levels; ++i) {
-            PGH_CHECK(given[i] >= 1 && given[i] < kLanes && (i == 0 || given[i] < given[i - 1]),
-                      std::string(who) + ": the levels must be strictly descending live-column counts in [1, 63]");
-            levels.push_back(given[i]);
-        }
-        return 0;
-    }
-};
-
 // mode 0 / 1 / 2 of k_mm64_rowops (the modes of recursive_run_f64, pgh_spmv.hip); retire (or null: the plain entries): the run narrows
 int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
-                      pgh_loop_result* results, const double* in_norms, const char* who, Retire64Plan* retire = nullptr) {
+                      pgh_loop_result* results, const double* in_norms, const char* who, RetirePlan* retire) {
     ColFactors inv{};
     for (int j = 0; j < p->b; ++j) {
         PGH_CHECK(std::isfinite(in_norms[j]) && in_norms[j] >= 0.0, std::string(who) + ": a norm that is negative or not finite");
@@ -1005,37 +899,21 @@ int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pg
         PGH_HIP(hipGetLastError());
         return run.publish_poll(k);
     };
-    if (retire == nullptr) {
-        PGH_TRY(run.run_ahead(max_steps, enqueue_step));
-        // the iterate of the last executed step: a stopped column was copied forward by every later one
-        BatchPoll last{};
-        PGH_HIP(hipMemcpyAsync(&last, &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
-        PGH_HIP(hipStreamSynchronize(r.stream));
-        return run.finish(true, y[last.executed & 1], cfg, out_scales, in_norms, ranks->data, 1, results);
-    }
-    // A run that retires its columns (include/pgh_retire64.h).  col_of[i]: the caller's column in lane column i of the current slabs.  A
-    // column leaves once, at the narrowing that follows its stop or at the end, and its part of the loop state is kept for results[].
-    const int width = b;                                   // the caller's row length
-    int col_of[kLanes];
-    for (int j = 0; j < kLanes; ++j) col_of[j] = j < b ? j : -1;
-    BatchState kept{};                                     // lanes indexed by the caller's column
+    // A run that retires its columns (include/pgh_retire64.h, the protocol of pgh_mm_retire.h).
+    RetireLedger ledger(b, 2);
     PoolBuf wide[7];                                       // what a narrowing hands back to the pool at the next one, or when this frame ends
+    const char* pair_env = getenv("PGH_MM64_PAIR");        // the product of a stage with ld == 2 takes the pair form unless it is 0
+    const bool pair_tail = !(pair_env != nullptr && pair_env[0] == '0');
     auto retire_lanes = [&](const BatchState& hs, bool all) {       // the lanes that have stopped (all: every lane) leave from the last iterate
         RetireCols64 cols;
-        for (int j = 0; j < kLanes; ++j) {
-            cols.dst[j] = -1;
-            cols.factor[j] = 1.0;
-            if (j >= b || !(all || hs.done[j])) continue;
-            const int c = col_of[j];
+        for (int j = 0; j < kLanes; ++j) cols.dst[j] = -1, cols.factor[j] = 1.0;
+        ledger.leave(hs, b, all, [&](int j, int c, double quotient) {
             double scale = out_scales ? out_scales[c] : cfg->out_scale;
             if (!out_scales && scale < 0.0) scale = in_norms[c];
             cols.dst[j] = c;
-            cols.factor[j] = hs.scale[j] * scale;          // (MM64Run::finish's factor)
-            kept.steps[c] = hs.steps[j];
-            kept.converged[c] = hs.converged[j];
-            kept.err[c] = hs.err[j];
-        }
-        k_mm64_retire_out<<<run.row_grid, WG, 0, r.stream>>>(y[hs.executed & 1], run.f.perm, n_int, run.n, ld, cols, ranks->data, width);
+            cols.factor[j] = quotient * scale;             // (MM64Run::finish's factor)
+        });
+        k_mm64_retire_out<<<run.row_grid, WG, 0, r.stream>>>(y[hs.executed & 1], run.f.perm, n_int, run.n, ld, cols, ranks->data, ledger.width);
     };
     auto narrow = [&](int k) -> int {
         BatchState hs;
@@ -1043,16 +921,14 @@ int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pg
         PGH_HIP(hipStreamSynchronize(r.stream));
         retire_lanes(hs, false);
         Repack64 q{};
-        ColMap64 map{};
+        ColMap map;
         int nb = 0;
-        for (int j = 0; j < kLanes; ++j) q.src[j] = map.v[j] = -1;
-        for (int j = 0; j < b; ++j)
-            if (!hs.done[j]) q.src[nb] = map.v[nb] = j, ++nb;
+        PGH_TRY(ledger.live_map(hs, b, ld, k, who, &map, &nb));
+        memcpy(q.src, map.v, sizeof(q.src));
         const int wide_ld = ld, wide_grid = run.row_grid;
-        PGH_CHECK(nb >= 1 && ((nb + 1) & ~1) < ld && hs.executed == k, std::string(who) + ": the loop state does not ask for a narrowing");
         // the narrow slabs come from the pool; the wide ones go back at the next narrowing or with this frame (the stream is still reading them)
         PGH_TRY(run.narrow_to(nb, wide));
-        run.pair = retire->pair;                           // (a run that starts two columns wide never narrows: the plain entry's bits)
+        run.pair = pair_tail;                              // (a run that starts two columns wide never narrows: the plain entry's bits)
         const int cur = hs.executed & 1;
         y[0] = run.s(2);
         y[1] = run.s(3);
@@ -1063,37 +939,39 @@ int recursive_batch64(pgh_graph_t g, int mode, pgh_mat_t p, const float* lam, pg
         q.narrow[1] = y[cur];                              // (the other iterate is written in full by the next step before anyone reads it)
         q.narrow[2] = run.s(4);
         k_mm64_repack<<<wide_grid, WG, 0, r.stream>>>(q, n_int, wide_ld, ld);
-        k_mm64_state_narrow<<<1, kLanes, 0, r.stream>>>(state, map, nb);
+        k_mm_state_narrow<<<1, kLanes, 0, r.stream>>>(state, map, nb);
         PGH_HIP(hipGetLastError());
-        int cols_now[kLanes];
-        memcpy(cols_now, col_of, sizeof(cols_now));
-        for (int j = 0; j < kLanes; ++j) col_of[j] = j < nb ? cols_now[map.v[j]] : -1;
+        ledger.follow(map, nb);
         retire->stage(ld, nb, k + 1);
         cp.narrow_at = retire->trigger(ld, retire->report.num_stages);
         return 0;
     };
-    retire->stage(ld, b, 1);
-    PGH_TRY(run.run_ahead(max_steps, enqueue_step, nullptr, narrow));
+    if (retire != nullptr) retire->stage(ld, b, 1);
+    PGH_TRY(run.run_ahead(max_steps, enqueue_step, nullptr, narrow));      // (without a plan the close never asks for a narrowing)
+    if (retire == nullptr || retire->report.num_stages == 1) {      // never narrowed: the plain way out
+        // the iterate of the last executed step: a stopped column was copied forward by every later one
+        BatchPoll last{};
+        PGH_HIP(hipMemcpyAsync(&last, &state->all_done, sizeof(BatchPoll), hipMemcpyDeviceToHost, r.stream));
+        PGH_HIP(hipStreamSynchronize(r.stream));
+        PGH_TRY(run.finish(true, y[last.executed & 1], cfg, out_scales, in_norms, ranks->data, 1, results));
+        if (retire != nullptr) retire->close(executed_steps(results, b));
+        return 0;
+    }
     BatchState hs;
     PGH_HIP(hipMemcpyAsync(&hs, state, sizeof(BatchState), hipMemcpyDeviceToHost, r.stream));
     PGH_HIP(hipStreamSynchronize(r.stream));
-    retire->close(hs.executed);
-    if (retire->report.num_stages == 1)                    // never narrowed: the plain way out
-        return run.finish(true, y[hs.executed & 1], cfg, out_scales, in_norms, ranks->data, 1, results);
     retire_lanes(hs, true);
     PGH_HIP(hipGetLastError());
     double ms = 0.0;
     PGH_TRY(run.timer.stop(&ms));
-    for (int j = 0; j < width; ++j) {
-        memset(&results[j], 0, sizeof(pgh_loop_result));
+    retire->close(hs.executed);
+    ledger.fill(results, ms);
+    for (int j = 0; j < ledger.width; ++j) {               // a zero column's record stays empty
+        if (in_norms[j] == 0.0) {
+            memset(&results[j], 0, sizeof(pgh_loop_result));
+            results[j].flags = PGH_RETIRE_NARROWED;
+        }
         results[j].in_norm = in_norms[j];
-        results[j].flags = PGH_RETIRE_NARROWED;
-        if (in_norms[j] == 0.0) continue;
-        results[j].iterations = 1 + kept.steps[j];
-        results[j].converged = kept.converged[j];
-        results[j].spmv_count = kept.steps[j];
-        results[j].last_error = kept.err[j];
-        results[j].loop_ms = ms;
     }
     return 0;
 }
@@ -1140,72 +1018,51 @@ extern "C" int pgh_spmm_f64_pair(pgh_graph_t g, const double* x_host, int32_t b,
     return spmm64(g, x_host, b, y_host, true, who);
 }
 
-extern "C" int pgh_ppr_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
-                                     pgh_loop_result* results, const double* in_norms) {
-    const char* who = "pgh_ppr_run_batch_f64";
-    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && ranks && cfg && results && in_norms), who));
-    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
-    return recursive_batch64(g, 0, p, nullptr, ranks, cfg, out_scales, results, in_norms, who);
-}
-
-extern "C" int pgh_absorb_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
-                                        const double* out_scales, pgh_loop_result* results, const double* in_norms) {
-    const char* who = "pgh_absorb_run_batch_f64";
-    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && lam && ranks && cfg && results && in_norms), who));
-    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
-    PGH_CHECK(lam->n == g->n_cols, std::string(who) + ": absorption length mismatch");
-    return recursive_batch64(g, 1, p, lam->data, ranks, cfg, out_scales, results, in_norms, who);
-}
-
-extern "C" int pgh_sarw_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
-                                      pgh_loop_result* results, const double* in_norms) {
-    const char* who = "pgh_sarw_run_batch_f64";
-    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && ranks && cfg && results && in_norms), who));
-    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
-    return recursive_batch64(g, 2, p, nullptr, ranks, cfg, out_scales, results, in_norms, who);
-}
-
-// The recursive loops in the mode that retires converged columns (include/pgh_retire64.h): the plain sibling's checks, the levels, the
-// loop with its plan, the report.
 namespace {
-int retire64_report_out(int status, const Retire64Plan& plan, pgh_retire_report* report) {
-    if (status == 0 && report != nullptr) *report = plan.report;
-    return status;
+// The checks of the three recursive entries and of their retiring siblings (include/pgh_retire64.h; ra null: a plain entry): the shapes,
+// then the levels, the loop with its plan, the report.  lam: the absorption of mode 1.
+int recursive_entry64(pgh_graph_t g, int mode, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                      pgh_loop_result* results, const double* in_norms, const char* who, const RetireArgs* ra) {
+    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && (lam || mode != 1) && ranks && cfg && results && in_norms), who));
+    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
+    if (mode == 1) PGH_CHECK(lam->n == g->n_cols, std::string(who) + ": absorption length mismatch");
+    RetirePlan plan;
+    if (ra != nullptr) PGH_TRY(plan.init(ra->levels, ra->num_levels, who, 2, {32, 16, 8, 4, 2}));
+    return retire_report_out(recursive_batch64(g, mode, p, mode == 1 ? lam->data : nullptr, ranks, cfg, out_scales, results, in_norms, who,
+                                               ra != nullptr ? &plan : nullptr),
+                             plan, ra);
 }
 }  // namespace
 
+extern "C" int pgh_ppr_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                                     pgh_loop_result* results, const double* in_norms) {
+    return recursive_entry64(g, 0, p, nullptr, ranks, cfg, out_scales, results, in_norms, "pgh_ppr_run_batch_f64", nullptr);
+}
+extern "C" int pgh_absorb_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
+                                        const double* out_scales, pgh_loop_result* results, const double* in_norms) {
+    return recursive_entry64(g, 1, p, lam, ranks, cfg, out_scales, results, in_norms, "pgh_absorb_run_batch_f64", nullptr);
+}
+extern "C" int pgh_sarw_run_batch_f64(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
+                                      pgh_loop_result* results, const double* in_norms) {
+    return recursive_entry64(g, 2, p, nullptr, ranks, cfg, out_scales, results, in_norms, "pgh_sarw_run_batch_f64", nullptr);
+}
 extern "C" int pgh_ppr_run_batch_f64_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
                                             pgh_loop_result* results, const double* in_norms, const int32_t* levels, int32_t num_levels,
                                             pgh_retire_report* report) {
-    const char* who = "pgh_ppr_run_batch_f64_retire";
-    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && ranks && cfg && results && in_norms), who));
-    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
-    Retire64Plan plan;
-    PGH_TRY(plan.init(levels, num_levels, who));
-    return retire64_report_out(recursive_batch64(g, 0, p, nullptr, ranks, cfg, out_scales, results, in_norms, who, &plan), plan, report);
+    const RetireArgs ra{levels, num_levels, report};
+    return recursive_entry64(g, 0, p, nullptr, ranks, cfg, out_scales, results, in_norms, "pgh_ppr_run_batch_f64_retire", &ra);
 }
-
 extern "C" int pgh_absorb_run_batch_f64_retire(pgh_graph_t g, pgh_mat_t p, pgh_vec_t lam, pgh_mat_t ranks, const pgh_loop_cfg* cfg,
                                                const double* out_scales, pgh_loop_result* results, const double* in_norms,
                                                const int32_t* levels, int32_t num_levels, pgh_retire_report* report) {
-    const char* who = "pgh_absorb_run_batch_f64_retire";
-    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && lam && ranks && cfg && results && in_norms), who));
-    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
-    PGH_CHECK(lam->n == g->n_cols, std::string(who) + ": absorption length mismatch");
-    Retire64Plan plan;
-    PGH_TRY(plan.init(levels, num_levels, who));
-    return retire64_report_out(recursive_batch64(g, 1, p, lam->data, ranks, cfg, out_scales, results, in_norms, who, &plan), plan, report);
+    const RetireArgs ra{levels, num_levels, report};
+    return recursive_entry64(g, 1, p, lam, ranks, cfg, out_scales, results, in_norms, "pgh_absorb_run_batch_f64_retire", &ra);
 }
-
 extern "C" int pgh_sarw_run_batch_f64_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat_t ranks, const pgh_loop_cfg* cfg, const double* out_scales,
                                              pgh_loop_result* results, const double* in_norms, const int32_t* levels, int32_t num_levels,
                                              pgh_retire_report* report) {
-    const char* who = "pgh_sarw_run_batch_f64_retire";
-    PGH_TRY(check64(g, p ? p->b : 1, !(g && p && ranks && cfg && results && in_norms), who));
-    PGH_TRY(check64_mats(g, p, ranks, cfg, who));
-    Retire64Plan plan;
-    PGH_TRY(plan.init(levels, num_levels, who));
-    return retire64_report_out(recursive_batch64(g, 2, p, nullptr, ranks, cfg, out_scales, results, in_norms, who, &plan), plan, report);
+    const RetireArgs ra{levels, num_levels, report};
+    return recursive_entry64(g, 2, p, nullptr, ranks, cfg, out_scales, results, in_norms, "pgh_sarw_run_batch_f64_retire", &ra);
 }
 
 // The taylor form with f64 terms and accumulator for b columns: iteration 1 is result_1 = c_1 p with the check of iteration 2 on
@@ -1249,7 +1106,7 @@ extern "C" int pgh_poly_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* 
     k_mm64_residual<<<cgrid, WG, 0, r.stream>>>(run.s(1), nullptr, n_int, ld, b, 0, linf, state, run.fold(0), partial);
     k_mm64_fold<<<kLanes, WG, 0, r.stream>>>(partial, cgrid, linf, state, run.fold(1));
     const int check2 = loop_checks_at(cfg->err_kind, 2, cfg->max_iters, cfg->end_modulo);
-    k_mm64_poly_first<<<1, kLanes, 0, r.stream>>>(state, run.fold(1), check2, cfg->err_kind, cfg->tol, (long long)run.n);
+    k_mm_poly_first<<<1, kLanes, 0, r.stream>>>(state, run.fold(1), check2, cfg->err_kind, cfg->tol, (long long)run.n);
     PGH_HIP(hipGetLastError());
     const int max_steps = cfg->max_iters - 2 > 0 ? cfg->max_iters - 2 : 0;
     Close64 cp{};

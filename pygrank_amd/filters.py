@@ -63,75 +63,44 @@ def _batch_info(results, stages):
             for r in results]
 
 
-def _propagate_in_batches(ranker, features, cfg, run):
-    """signals.py:225-226 (one rank() per feature column) as multi-seed device loops of up to 64 columns with the prologue of
-    PageRank.propagate: per-column L1 norms (abstract_filters.py:52-55; zero columns stay zero), preserve_norm factors, the loop
-    started from p (:56), ConvergenceManager's verdict per non-zero column.  run(P, R, cfg_ref, scales, results) -> what _batch_call
-    returns for one include/pgh_batch.h call.  Returns the [n, B] ranks, or None when the engine declined the first chunk (nothing was run)."""
+def _propagate_in_chunks(ranker, features, cfg, run, f64=False, raw=False):
+    """signals.py:225-226 (one rank() per feature column) as multi-seed device loops of up to 64 columns: per-column L1 norms
+    (abstract_filters.py:52-55; zero columns stay zero), preserve_norm factors, the loop started from p (:56), ConvergenceManager's
+    verdict per non-zero column.  run(P, R, cfg_ref, scales, results[, in_norms]) -> what _batch_call returns for one call of
+    include/pgh_batch.h, or with f64 of include/pgh_batch64.h (``GraphFilter(f64_batch=True)``): the loop then keeps its iterates, sums,
+    quotients and residuals in f64, the tolerance is clamped at fp64 eps (_f64_cfg), the column norms go in beside the chunk and every
+    record of ``last_batches`` carries "f64": True.  raw (f64 only): the chunk goes in UN-normalised, as _f64_operands hands a single
+    vector to the f64 route (the recursive filters); otherwise L1-normalised in f32.  A retiring run's report is recorded under "stages".
+    Returns the [n, B] ranks, or None when the engine declined the first chunk (nothing was run)."""
     from pygrank_amd.device import DeviceMatrix
     F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
     if not isinstance(F, DeviceMatrix):
         F = DeviceMatrix.from_columns([F])
-    cfg.start_from_p = 1
+    if f64:
+        cfg = ranker._f64_cfg(cfg)
+    cfg.start_from_p = 1                                                          # ranks start as a copy of p (:56)
     batches = []
     out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
     for start, chunk in F.chunks():
         norms = chunk.col_abssum()
-        P = chunk.div_cols(norms)
-        R = DeviceMatrix.empty(chunk.n, chunk.b)
-        results = (L.LoopResult * chunk.b)()
-        scales = (C.c_double * chunk.b)(*[(float(nrm) if ranker.preserve_norm else 1.0) for nrm in norms])
-        ranker.convergence.start()
-        status, stages = run(P, R, C.byref(cfg), scales, results)
-        if status == L.DECLINED and not batches:
-            return None
-        L.check(status)
-        batches.append(_batch_info(results, stages))
-        ranker.last_batches = batches
-        for r, nrm in zip(results, norms):
-            if nrm != 0:
-                ranker.convergence.finish_device_loop(r.iterations, r.converged)   # raises like the per-column run would
-        if out is None:
-            return R
-        out.set_cols(start, R)
-    return out
-
-
-def _propagate_in_batches64(ranker, features, cfg, run, raw):
-    """_propagate_in_batches through an entry of include/pgh_batch64.h (``GraphFilter(f64_batch=True)``): the loop keeps its iterates,
-    sums, quotients and residuals in f64 and the tolerance is clamped at fp64 eps (_f64_cfg).  raw: the chunk goes in UN-normalised
-    with its column norms beside it, as _f64_operands hands a single vector to the f64 route (the recursive filters); otherwise
-    L1-normalised in f32, as the closed-form filters' single rank() does.  run(P, R, cfg_ref, scales, results, norms) -> what
-    _batch_call returns (the recursive filters: ``f64_retire`` picks the entry of include/pgh_retire64.h).  Every record of
-    ``last_batches`` carries "f64": True, and the report of a retiring run under "stages".  Returns the [n, B] ranks, or None when the
-    engine declined the first chunk (nothing was run)."""
-    from pygrank_amd.device import DeviceMatrix
-    F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
-    if not isinstance(F, DeviceMatrix):
-        F = DeviceMatrix.from_columns([F])
-    cfg = ranker._f64_cfg(cfg)
-    cfg.start_from_p = 1
-    batches = []
-    out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
-    for start, chunk in F.chunks():
-        norms = chunk.col_abssum()
-        P = chunk
-        if not raw:
-            # p * f32(1 / |p|), the bits a single rank() hands its loop (device.py _scalar_factor: a division by a scalar is a
+        if f64 and raw:
+            P = chunk
+        else:
+            # f64: p * f32(1 / |p|), the bits a single rank() hands its loop (device.py _scalar_factor: a division by a scalar is a
             # multiplication); a library without the slab form divides (a last bit of p may then differ from the single run's)
-            P = chunk.col_scale([1.0 / nrm if nrm != 0 else 1.0 for nrm in norms])
+            P = chunk.col_scale([1.0 / nrm if nrm != 0 else 1.0 for nrm in norms]) if f64 else None
             if P is None:
                 P = chunk.div_cols(norms)
         R = DeviceMatrix.empty(chunk.n, chunk.b)
         results = (L.LoopResult * chunk.b)()
         scales = (C.c_double * chunk.b)(*[(float(nrm) if ranker.preserve_norm else 1.0) for nrm in norms])
-        in_norms = (C.c_double * chunk.b)(*[float(nrm) for nrm in norms])
+        in_norms = ((C.c_double * chunk.b)(*[float(nrm) for nrm in norms]),) if f64 else ()
         ranker.convergence.start()
-        status, stages = run(P, R, C.byref(cfg), scales, results, in_norms)
+        status, stages = run(P, R, C.byref(cfg), scales, results, *in_norms)
         if status == L.DECLINED and not batches:
             return None
         L.check(status)
-        batches.append([dict(record, f64=True) for record in _batch_info(results, stages)])
+        batches.append([dict(record, f64=True) for record in _batch_info(results, stages)] if f64 else _batch_info(results, stages))
         ranker.last_batches = batches
         for r, nrm in zip(results, norms):
             if nrm != 0:
@@ -294,6 +263,31 @@ class GraphFilter(NodeRanking):
         if g is None or g.shape[0] != g.shape[1] or g.shape[0] == 0 or g.nnz == 0 or "row-major" in g.format():
             return None
         return g
+
+    def _propagate_batched(self, features, graph_of, cfg_of, entries, pack, raw=False, usable=None):
+        """propagate's multi-seed routes in their order: the f64 loops (include/pgh_batch64.h), then the f32 ones (include/pgh_batch.h).
+        A route the filter names in `entries` is taken when graph_of(f64) names its device graph, the library exports its entry and
+        usable(g) (if given) agrees; it ends the search unless the engine DECLINED its first chunk.  entries[f64]: (the plain entry's
+        name, its retiring sibling's or None -- then _batch_call is not asked); pack(g, P, R, cfg_ref, scales, results[, in_norms]) ->
+        the call's arguments; cfg_of() -> a fresh loop configuration; raw: _propagate_in_chunks'.  Returns the ranks, or None: the
+        column loop is the caller's."""
+        for f64 in (True, False):
+            if f64 not in entries:
+                continue
+            plain, retiring = entries[f64]
+            g = graph_of(f64)
+            entry = L.entry(plain) if g is not None else None
+            if entry is None or (usable is not None and not usable(g)):
+                continue
+
+            def run(*operands):
+                if retiring is None:
+                    return entry(*pack(g, *operands)), None
+                return _batch_call(self, entry, retiring, pack(g, *operands), switch="f64_retire" if f64 else "retire")
+            out = _propagate_in_chunks(self, features, cfg_of(), run, f64=f64, raw=raw)
+            if out is not None:
+                return out
+        return None
 
     def _start(self, M, personalization, ranks, *args, **kwargs):
         pass
@@ -495,17 +489,13 @@ class PageRank(RecursiveGraphFilter):
         keeps its own quotient, residual and stopping iteration.  With f64_batch=True a run that wants f64 iterates goes through
         pgh_ppr_run_batch_f64 (include/pgh_batch64.h) the same way; graph_dropout, a library without that entry and a declined call
         take the route below."""
-        from pygrank_amd.device import DeviceMatrix
-        g64 = self._walk_batch_graph(PageRank, graph, args, kwargs, f64=True)
-        entry64 = L.entry("pgh_ppr_run_batch_f64") if g64 is not None else None
-        if entry64 is not None:
-            out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
-                                          lambda P, R, cfg_ref, scales, res, norms: _batch_call(
-                                              self, entry64, "pgh_ppr_run_batch_f64_retire", (g64._h, P._h, R._h, cfg_ref, scales, res, norms),
-                                              switch="f64_retire"), raw=True)
-            if out is not None:
-                return out
-        cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
+        cfg_of = lambda: self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
+        out = self._propagate_batched(features, lambda f64: self._walk_batch_graph(PageRank, graph, args, kwargs, f64=f64), cfg_of,
+                                      {True: ("pgh_ppr_run_batch_f64", "pgh_ppr_run_batch_f64_retire")},
+                                      lambda g, P, R, *rest: (g._h, P._h, R._h, *rest), raw=True)
+        if out is not None:
+            return out
+        cfg = cfg_of()
         dropout = float(kwargs.get("graph_dropout", 0) or 0)
         only_dropout = not kwargs or (set(kwargs) == {"graph_dropout"} and 0 <= dropout < 1)
         batched = (not args and only_dropout and cfg is not None and self._plain_quotient()
@@ -519,38 +509,20 @@ class PageRank(RecursiveGraphFilter):
         g = _device_graph(M) if batched else None
         if g is None or g.shape[0] != g.shape[1]:
             return super().propagate(graph, features, *args, **kwargs)
-        F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
-        if not isinstance(F, DeviceMatrix):
-            F = DeviceMatrix.from_columns([F])
-        self.last_batches = []
-        out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
-        for start, chunk in F.chunks():
-            norms = chunk.col_abssum()                                            # abstract_filters.py:52-55 per column
-            P = chunk.div_cols(norms)                                             # zero columns stay zero (:53-54)
-            R = DeviceMatrix.empty(chunk.n, chunk.b)
-            results = (L.LoopResult * chunk.b)()
-            scales = (C.c_double * chunk.b)(*[(float(nrm) if self.preserve_norm else 1.0) for nrm in norms])
-            cfg.start_from_p = 1                                                  # ranks start as a copy of p (:56)
-            self.convergence.start()
-            stages = None
+
+        def run(P, R, cfg_ref, scales, results):                                  # (a status other than 0 is an error here, no fallback)
             if dropout > 0:
                 # graph_dropout(M, rate) of every step (abstract_filters.py:59-62) inside the batch kernel: one mask per step,
                 # seeds reserved up front (the loop stops on the device)
                 from pygrank_amd.backend import hip as _hip
                 seed0 = _hip.take_dropout_seeds(max(int(cfg.max_iters), 1))
-                L.check(L.lib().pgh_ppr_run_batch_dropout(g._h, P._h, R._h, C.byref(cfg), scales, dropout, seed0, results))
-            else:
-                status, stages = _batch_call(self, L.lib().pgh_ppr_run_batch, "pgh_ppr_run_batch_retire",
-                                             (g._h, P._h, R._h, C.byref(cfg), scales, results))
-                L.check(status)
-            self.last_batches.append(_batch_info(results, stages))
-            for r, nrm in zip(results, norms):
-                if nrm != 0:
-                    self.convergence.finish_device_loop(r.iterations, r.converged)   # raises like the per-column run would
-            if out is None:
-                return R
-            out.set_cols(start, R)
-        return out
+                L.check(L.lib().pgh_ppr_run_batch_dropout(g._h, P._h, R._h, cfg_ref, scales, dropout, seed0, results))
+                return 0, None
+            status, stages = _batch_call(self, L.lib().pgh_ppr_run_batch, "pgh_ppr_run_batch_retire", (g._h, P._h, R._h, cfg_ref, scales, results))
+            L.check(status)
+            return status, stages
+        self.last_batches = []
+        return _propagate_in_chunks(self, features, cfg, run)
 
 
 class AbsorbingWalks(RecursiveGraphFilter):
@@ -599,28 +571,18 @@ class AbsorbingWalks(RecursiveGraphFilter):
         columns through pgh_absorb_run_batch (include/pgh_batch.h) wherever a single rank() would run the f32 loop of pgh_absorb_run;
         every column keeps its own quotient, residual and stopping iteration.  With f64_batch=True a run that wants f64 iterates goes
         through pgh_absorb_run_batch_f64 (include/pgh_batch64.h) the same way.  The column loop otherwise."""
-        g64 = self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",), f64=True)
-        entry64 = L.entry("pgh_absorb_run_batch_f64") if g64 is not None else None
-        if entry64 is not None:
-            lam = (to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np
-            if isinstance(lam, DeviceVector) and len(lam) == g64.shape[0]:
-                out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
-                                              lambda P, R, cfg_ref, scales, res, norms: _batch_call(
-                                                  self, entry64, "pgh_absorb_run_batch_f64_retire",
-                                                  (g64._h, P._h, lam._h, R._h, cfg_ref, scales, res, norms), switch="f64_retire"), raw=True)
-                if out is not None:
-                    return out
-        g = self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",))
-        entry = L.entry("pgh_absorb_run_batch") if g is not None else None
-        if entry is not None:
-            lam = (to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np
-            if isinstance(lam, DeviceVector) and len(lam) == g.shape[0]:
-                cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
-                out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: _batch_call(
-                    self, entry, "pgh_absorb_run_batch_retire", (g._h, P._h, lam._h, R._h, cfg_ref, scales, res)))
-                if out is not None:
-                    return out
-        return super().propagate(graph, features, *args, **kwargs)
+        lam = []                                                                  # the absorption, formed once by the first route that asks
+
+        def usable(g):
+            if not lam:
+                lam.append((to_signal(graph, kwargs.get("absorption")) * ((1 - self.alpha) / self.alpha)).np)
+            return isinstance(lam[0], DeviceVector) and len(lam[0]) == g.shape[0]
+        out = self._propagate_batched(
+            features, lambda f64: self._walk_batch_graph(AbsorbingWalks, graph, args, kwargs, allowed=("absorption",), f64=f64),
+            lambda: self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
+            {True: ("pgh_absorb_run_batch_f64", "pgh_absorb_run_batch_f64_retire"), False: ("pgh_absorb_run_batch", "pgh_absorb_run_batch_retire")},
+            lambda g, P, R, *rest: (g._h, P._h, lam[0]._h, R._h, *rest), raw=True, usable=usable)
+        return out if out is not None else super().propagate(graph, features, *args, **kwargs)
 
 
 class LFPR(RecursiveGraphFilter):
@@ -919,24 +881,12 @@ class SymmetricAbsorbingRandomWalks(RecursiveGraphFilter):
         """signals.py:225-226 as multi-seed batches of up to 64 columns through pgh_sarw_run_batch (include/pgh_batch.h) wherever a
         single rank() would run the f32 loop of pgh_sarw_run; with f64_batch=True a run that wants f64 iterates goes through
         pgh_sarw_run_batch_f64 (include/pgh_batch64.h) the same way; the column loop otherwise."""
-        g64 = self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs, f64=True)
-        entry64 = L.entry("pgh_sarw_run_batch_f64") if g64 is not None else None
-        if entry64 is not None:
-            out = _propagate_in_batches64(self, features, self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
-                                          lambda P, R, cfg_ref, scales, res, norms: _batch_call(
-                                              self, entry64, "pgh_sarw_run_batch_f64_retire", (g64._h, P._h, R._h, cfg_ref, scales, res, norms),
-                                              switch="f64_retire"), raw=True)
-            if out is not None:
-                return out
-        g = self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs)
-        entry = L.entry("pgh_sarw_run_batch") if g is not None else None
-        if entry is not None:
-            cfg = self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0)
-            out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: _batch_call(
-                self, entry, "pgh_sarw_run_batch_retire", (g._h, P._h, R._h, cfg_ref, scales, res)))
-            if out is not None:
-                return out
-        return super().propagate(graph, features, *args, **kwargs)
+        out = self._propagate_batched(
+            features, lambda f64: self._walk_batch_graph(SymmetricAbsorbingRandomWalks, graph, args, kwargs, f64=f64),
+            lambda: self._loop_cfg(self.alpha, bool(self.use_quotient), 1.0),
+            {True: ("pgh_sarw_run_batch_f64", "pgh_sarw_run_batch_f64_retire"), False: ("pgh_sarw_run_batch", "pgh_sarw_run_batch_retire")},
+            lambda g, P, R, *rest: (g._h, P._h, R._h, *rest), raw=True)
+        return out if out is not None else super().propagate(graph, features, *args, **kwargs)
 
 
 class LowPassRecursiveGraphFilter(GraphFilter):
@@ -1454,28 +1404,19 @@ class ClosedFormGraphFilter(GraphFilter):
         through pgh_poly_run_batch_f64 (include/pgh_batch64.h) the same way, its personalizations L1-normalised in f32 as a single
         rank() normalises them."""
         own = ClosedFormGraphFilter
-        g = g64 = None
-        if self.coefficient_type == "taylor" and self.optimization_dict is None and self.krylov_dims is None and type(self)._step is own._step \
-                and type(self)._recursion is own._recursion and type(self)._start is own._start \
-                and type(self)._retrieve_power is own._retrieve_power and type(self)._prepare is own._prepare:
-            g64 = self._batch_graph(graph, args, kwargs, f64=True)
-            g = self._batch_graph(graph, args, kwargs) if g64 is None else None
-        entry64 = L.entry("pgh_poly_run_batch_f64") if g64 is not None else None
-        if entry64 is not None:
-            coeffs = np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64)
-            out = _propagate_in_batches64(self, features, self._loop_cfg(0.0, False, 1.0), lambda P, R, cfg_ref, scales, res, norms: (entry64(
-                g64._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res), None), raw=False)
-            if out is not None:
-                return out
-        entry = L.entry("pgh_poly_run_batch") if g is not None else None
-        if entry is not None:
-            cfg = self._loop_cfg(0.0, False, 1.0)
-            coeffs = np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64)
-            out = _propagate_in_batches(self, features, cfg, lambda P, R, cfg_ref, scales, res: (entry(
-                g._h, P._h, coeffs.ctypes.data_as(C.c_void_p), len(coeffs), R._h, cfg_ref, scales, res), None))
-            if out is not None:
-                return out
-        return super().propagate(graph, features, *args, **kwargs)
+        if not (self.coefficient_type == "taylor" and self.optimization_dict is None and self.krylov_dims is None and type(self)._step is own._step
+                and type(self)._recursion is own._recursion and type(self)._start is own._start
+                and type(self)._retrieve_power is own._retrieve_power and type(self)._prepare is own._prepare):
+            return super().propagate(graph, features, *args, **kwargs)
+        coeffs = []                                                               # the schedule, formed by the first route that asks
+
+        def pack(g, P, R, cfg_ref, scales, results, *in_norms):                   # (pgh_poly_run_batch_f64 normalises nothing: no norms)
+            if not coeffs:
+                coeffs.append(np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64))
+            return g._h, P._h, coeffs[0].ctypes.data_as(C.c_void_p), len(coeffs[0]), R._h, cfg_ref, scales, results
+        out = self._propagate_batched(features, lambda f64: self._batch_graph(graph, args, kwargs, f64=f64), lambda: self._loop_cfg(0.0, False, 1.0),
+                                      {True: ("pgh_poly_run_batch_f64", None), False: ("pgh_poly_run_batch", None)}, pack)
+        return out if out is not None else super().propagate(graph, features, *args, **kwargs)
 
 
 class GenericGraphFilter(ClosedFormGraphFilter):

@@ -115,14 +115,15 @@ def stand_in(host_engine):
     assert L.entry("pgh_ppr_run_batch_f64") is None
     saved = cdll._pgh_batch64_entries
 
-    def columns(name, g, p, out, cfg, scales, results, norms, single):
+    def columns(name, g, p, out, cfg, scales, results, norms, single, **extra):
         n, b = C.c_int64(), C.c_int32()
         assert cdll.pgh_mat_shape(p, C.byref(n), C.byref(b)) == 0
         slab = np.empty((n.value, b.value))
         assert cdll.pgh_mat_d2h_f64(p, slab.ctypes.data_as(C.c_void_p)) == 0
         cfg = cfg._obj
         log.append(dict(entry=name, width=b.value, slab=slab, tol=cfg.tol, start_from_p=cfg.start_from_p,
-                        norms=None if norms is None else [norms[j] for j in range(b.value)], scales=[scales[j] for j in range(b.value)]))
+                        norms=None if norms is None else [norms[j] for j in range(b.value)], scales=[scales[j] for j in range(b.value)],
+                        **extra))
         if behaviour["status"] is not None:
             return behaviour["status"]
         for j in range(b.value):
@@ -148,16 +149,19 @@ def stand_in(host_engine):
                        lambda g, v, r, one, res: cdll.pgh_ppr_run_f64(g, v, r, C.byref(one), C.byref(res)))
 
     def absorb(g, p, lam, out, cfg, scales, results, norms):
+        absorption = np.empty(cdll.pgh_vec_len(lam))                          # the third argument is the absorption vector
+        assert cdll.pgh_vec_d2h_f64(lam, absorption.ctypes.data_as(C.c_void_p), len(absorption)) == 0
         return columns("pgh_absorb_run_batch_f64", g, p, out, cfg, scales, results, norms,
-                       lambda g, v, r, one, res: cdll.pgh_absorb_run_f64(g, v, lam, r, C.byref(one), C.byref(res)))
+                       lambda g, v, r, one, res: cdll.pgh_absorb_run_f64(g, v, lam, r, C.byref(one), C.byref(res)), lam=absorption)
 
     def sarw(g, p, out, cfg, scales, results, norms):
         return columns("pgh_sarw_run_batch_f64", g, p, out, cfg, scales, results, norms,
                        lambda g, v, r, one, res: cdll.pgh_sarw_run_f64(g, v, r, C.byref(one), C.byref(res)))
 
     def poly(g, p, coeffs, count, out, cfg, scales, results):
+        schedule = np.ctypeslib.as_array(C.cast(coeffs, C.POINTER(C.c_double)), (count,)).copy()    # the schedule and its length follow p
         return columns("pgh_poly_run_batch_f64", g, p, out, cfg, scales, results, None,
-                       lambda g, v, r, one, res: cdll.pgh_poly_run(g, v, coeffs, count, 2, r, C.byref(one), C.byref(res)))
+                       lambda g, v, r, one, res: cdll.pgh_poly_run(g, v, coeffs, count, 2, r, C.byref(one), C.byref(res)), coeffs=schedule)
     cdll._pgh_batch64_entries = dict(saved, pgh_ppr_run_batch_f64=ppr, pgh_absorb_run_batch_f64=absorb, pgh_sarw_run_batch_f64=sarw,
                                      pgh_poly_run_batch_f64=poly)
     try:
@@ -194,9 +198,13 @@ def test_propagate_calls_the_right_entry_with_raw_slab_norms_and_tolerance(stand
         if name == "pgh_poly_run_batch_f64":
             sums = np.abs(call["slab"]).sum(axis=0)                         # L1-normalised in f32, the zero column stays zero
             assert np.allclose(np.delete(sums, 3), 1.0, rtol=0, atol=1e-6) and sums[3] == 0
+            want_coeffs = on._coefficient_schedule(int(on.convergence.max_iters) - 1)
+            assert len(want_coeffs) > 1 and np.array_equal(call["coeffs"], np.asarray(want_coeffs, dtype=np.float64))
         else:
             assert np.array_equal(call["slab"], F32), name                  # UN-normalised ...
             assert call["norms"] == list(np.abs(F32).sum(axis=0)), name      # ... with the norms beside it
+        if name == "pgh_absorb_run_batch_f64":                              # absorption=None: ones, times (1 - alpha) / alpha
+            assert call["lam"].shape == (n,) and np.allclose(call["lam"], (1 - 0.85) / 0.85, rtol=1e-6, atol=0)
         assert len(counted) == 6, name                                      # the zero column is not counted
         assert len(on.last_batches) == 1 and len(on.last_batches[0]) == 7 and all(c["f64"] is True for c in on.last_batches[0])
         assert not got[:, 3].any() and not hasattr(off, "last_batches")
