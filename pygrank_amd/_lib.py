@@ -410,6 +410,12 @@ RETIRE64_SIGNATURES = {
     "pgh_spmm_f64_pair": BATCH64_SIGNATURES["pgh_spmm_f64"],
 }
 
+# include/pgh_cheb64.h: the "chebyshev" form beside the taylor loop of include/pgh_batch64.h, with that loop's arguments.  Unfused route:
+# one single-vector f64 loop (pgh_poly_run, form 1) per column.
+CHEB64_SIGNATURES = {
+    "pgh_cheb_run_batch_f64": BATCH64_SIGNATURES["pgh_poly_run_batch_f64"],
+}
+
 
 # header -> its table: every optional entry family; the names are distinct across the tables and from SIGNATURES
 OPTIONAL = {
@@ -422,9 +428,9 @@ OPTIONAL = {
 # ... and every header entry() serves: OPTIONAL -- the thirteen families whose number and 41 names tests/test_fused_plumbing.py pins --
 # and the headers added since, which tests of their own enumerate (include/pgh_gnn.h: tests/test_gnn_host.py; include/pgh_select.h:
 # tests/test_subgraph_host.py; include/pgh_retire.h: tests/test_retire_host.py; include/pgh_batch64.h: tests/test_batch64_host.py;
-# include/pgh_retire64.h: tests/test_retire64_host.py)
+# include/pgh_retire64.h: tests/test_retire64_host.py; include/pgh_cheb64.h: tests/test_gpu_cheb_batch64.py)
 TABLES = dict(OPTIONAL, **{"pgh_gnn.h": GNN_SIGNATURES, "pgh_select.h": SELECT_SIGNATURES, "pgh_retire.h": RETIRE_SIGNATURES,
-                           "pgh_batch64.h": BATCH64_SIGNATURES, "pgh_retire64.h": RETIRE64_SIGNATURES})
+                           "pgh_batch64.h": BATCH64_SIGNATURES, "pgh_retire64.h": RETIRE64_SIGNATURES, "pgh_cheb64.h": CHEB64_SIGNATURES})
 _HEADER_OF = {name: header for header, table in TABLES.items() for name in table}
 DECLINED = 2              # every optional header's PGH_*_DECLINED: nothing was written, the caller takes its unfused route
 

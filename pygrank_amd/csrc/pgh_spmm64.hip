@@ -1,5 +1,6 @@
 // The f64 siblings of the multi-seed loops (include/pgh_batch64.h): Y = M^T X and the device loops of PageRank, the two absorbing
-// walks and the closed-form filters' taylor form over [n, ld] slabs of DOUBLES, b <= 64 columns.
+// walks and the closed-form filters' taylor form -- and their "chebyshev" form (include/pgh_cheb64.h) -- over [n, ld] slabs of DOUBLES,
+// b <= 64 columns.
 //
 // They walk the multi-seed stream the f32 loops walk (pgh_spmm.hip ensure_mm_layout: colf, val, close, tile, seg_row, perm): no image
 // is built for them.  A group of lanes walks one 512-entry tile and a lane owns TWO columns, so one 16-byte load per lane fetches a
@@ -15,6 +16,7 @@
 #include "pgh_kernels.h"
 #include "pgh_batch64.h"
 #include "pgh_retire64.h"
+#include "pgh_cheb64.h"
 #include "pgh_mm_retire.h"
 
 #include <cmath>
@@ -675,6 +677,72 @@ __global__ __launch_bounds__(WG) void k_mm64_poly_step(const double* __restrict_
     mm64_block_fold(acc[0], acc[1], lpr, c2, live, linf, s_red, partials);
 }
 
+// One step of the reference's "chebyshev" recurrence for every column (pgh_poly_run's form 1, abstract_filters.py:215-224):
+//   term <- a * (U_r * sum) + b * term, in place;   the next gather row term * G_r;   result += c * term
+// with (a, b) = (1, 0) for T_2 and (2, -1) from T_3 on.  The recurrence is row-local once the row sums exist, so the lane that owns a
+// pair of columns of a row reads its old term and writes the new one where it stood: no second term slab.  What a step does not need it
+// does not move: b == 0 reads no term, add == 0 (a zero coefficient after iteration 2, where the reference skips the addition) neither
+// reads nor writes the result, and a lane whose two columns have both stopped passes over its rows altogether.  A stopped column
+// beside a running one keeps its result, and its term becomes zero: it stays finite however long its neighbour runs.
+struct ChebStep {
+    double a, b, c;
+    int    add, linf;
+};
+__global__ __launch_bounds__(WG) void k_mm64_cheb_step(const double* __restrict__ sums, const RowOp64* __restrict__ rowop, double* __restrict__ term,
+                                                        double* __restrict__ result, double* __restrict__ xg, ChebStep q, int64_t n, int ld, int b,
+                                                        const BatchState* __restrict__ state, double* __restrict__ partials) {
+    __shared__ double s_red[WG / 64][kLanes];
+    if (state->all_done) return;
+    const int lane = threadIdx.x & 63;
+    const int lpr = lanes_per_row64(ld), rows_per_wave = 64 / lpr;
+    const int l = lane & (lpr - 1), c2 = 2 * l;
+    const bool live = c2 < ld;
+    bool frozen[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) frozen[k] = !(c2 + k < b) || state->done[c2 + k] != 0;
+    const bool works = live && !(frozen[0] && frozen[1]);
+    const bool reads_term = q.b != 0.0;
+    double acc[2] = {0.0, 0.0};
+    const int64_t first = (blockIdx.x * (int64_t)(WG / 64) + (threadIdx.x >> 6)) * rows_per_wave + lane / lpr;
+    const int64_t stride = (int64_t)gridDim.x * (WG / 64) * rows_per_wave;
+    constexpr int U = 2;
+    for (int64_t r0 = first; works && r0 < n; r0 += stride * U) {
+        f64x2 sum[U], tp[U], ro[U];
+        RowOp64 op[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t r = r0 + u * stride;
+            ok[u] = r < n;
+            const int64_t at = (ok[u] ? r : 0) * ld + c2;
+            sum[u] = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(sums + at));
+            tp[u] = reads_term ? *reinterpret_cast<const f64x2*>(term + at) : f64x2{0.0, 0.0};
+            ro[u] = q.add ? *reinterpret_cast<const f64x2*>(result + at) : f64x2{0.0, 0.0};
+            op[u] = rowop[ok[u] ? r : 0];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!ok[u]) continue;
+            const int64_t at = (r0 + u * stride) * ld + c2;
+            const f64x2 y = sum[u] * op[u].U;
+            f64x2 t;
+            t.x = frozen[0] ? 0.0 : (reads_term ? q.a * y.x + q.b * tp[u].x : q.a * y.x);
+            t.y = frozen[1] ? 0.0 : (reads_term ? q.a * y.y + q.b * tp[u].y : q.a * y.y);
+            *reinterpret_cast<f64x2*>(term + at) = t;
+            *reinterpret_cast<f64x2*>(xg + at) = t * op[u].G;
+            if (!q.add) continue;
+            f64x2 rn;
+            rn.x = frozen[0] ? ro[u].x : ro[u].x + q.c * t.x;
+            rn.y = frozen[1] ? ro[u].y : ro[u].y + q.c * t.y;
+            *reinterpret_cast<f64x2*>(result + at) = rn;
+            const double d0 = fabs(rn.x - ro[u].x), d1 = fabs(rn.y - ro[u].y);
+            acc[0] = q.linf ? fmax(acc[0], d0) : acc[0] + d0;
+            acc[1] = q.linf ? fmax(acc[1], d1) : acc[1] + d1;
+        }
+    }
+    mm64_block_fold(acc[0], acc[1], lpr, c2, live, q.linf, s_red, partials);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1065,12 +1133,14 @@ extern "C" int pgh_sarw_run_batch_f64_retire(pgh_graph_t g, pgh_mat_t p, pgh_mat
     return recursive_entry64(g, 2, p, nullptr, ranks, cfg, out_scales, results, in_norms, "pgh_sarw_run_batch_f64_retire", &ra);
 }
 
-// The taylor form with f64 terms and accumulator for b columns: iteration 1 is result_1 = c_1 p with the check of iteration 2 on
-// |result_1|, step k (iteration k + 1) adds c_{k+1} (M^T)^k p and the check of iteration k + 2 compares result_{k+1} with result_k.
-// Column j: iterations = 2 + its steps, as pgh_poly_run reports them.
-extern "C" int pgh_poly_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
-                                      const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results) {
-    const char* who = "pgh_poly_run_batch_f64";
+// The closed-form filters' loop with f64 terms and accumulator for b columns: iteration 1 is result_1 = c_1 p with the check of
+// iteration 2 on |result_1|, step k (iteration k + 1) adds c_{k+1} T_{k+1} and the check of iteration k + 2 compares result_{k+1} with
+// result_k.  Taylor: T_{k+1} = (M^T)^k p, the gather slab is the current term (k_mm64_poly_step).  cheb: the reference's "chebyshev"
+// recurrence, T_2 = M^T T_1 and T_{k+1} = 2 M^T T_k - T_k from step 2 on, with the term kept in a slab of its own and closed in place
+// (k_mm64_cheb_step).  Column j: iterations = 2 + its steps, as pgh_poly_run reports them.
+namespace {
+int closed_form_batch64(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result, const pgh_loop_cfg* cfg,
+                        const double* out_scales, pgh_loop_result* results, bool cheb, const char* who) {
     PGH_TRY(check64(g, p ? p->b : 1, !(g && p && result && cfg && results && (coeffs || num_coeffs == 0)), who));
     PGH_TRY(check64_mats(g, p, result, cfg, who));
     PGH_CHECK(num_coeffs >= 0, std::string(who) + ": a negative schedule length");
@@ -1089,7 +1159,10 @@ extern "C" int pgh_poly_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* 
     }
     PGH_TRY(mm_ensure_layout(g));
     MM64Run run(g, b);
-    PGH_TRY(run.alloc(2, true));                           // slabs: 0 the row sums, 1 the result, 2 the gather slab (the current term)
+    // slabs: 0 the row sums, 1 the result, then the gather slab -- taylor: it is the current term; cheb: 2 the term, 3 the gather slab
+    PGH_TRY(run.alloc(cheb ? 3 : 2, true));
+    double* const term = cheb ? run.s(2) : nullptr;
+    double* const xg = run.s(cheb ? 3 : 2);
     bool bad = false;
     PGH_TRY(run.row_operands(3, 0.0, nullptr, &bad));
     const int ld = run.ld, cgrid = run.cgrid;
@@ -1100,8 +1173,8 @@ extern "C" int pgh_poly_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* 
     ColFactors c1{};
     for (int j = 0; j < kLanes; ++j) c1.v[j] = coeff(1);
     k_mm64_state_init<<<1, kLanes, 0, r.stream>>>(state, b, c1, 0);
-    // result_1 = c_1 p, term_1 = p in gather form
-    k_mm64_way_in<float><<<run.row_grid, WG, 0, r.stream>>>(p->data, run.f.perm, n_int, run.n, b, ld, c1, run.ops(), run.s(1), nullptr, run.s(2));
+    // result_1 = c_1 p, T_1 = p (cheb: in the term slab, every row and padding column of it) and in gather form
+    k_mm64_way_in<float><<<run.row_grid, WG, 0, r.stream>>>(p->data, run.f.perm, n_int, run.n, b, ld, c1, run.ops(), run.s(1), term, xg);
     const int linf = cfg->err_kind == PGH_ERR_LINF;
     k_mm64_residual<<<cgrid, WG, 0, r.stream>>>(run.s(1), nullptr, n_int, ld, b, 0, linf, state, run.fold(0), partial);
     k_mm64_fold<<<kLanes, WG, 0, r.stream>>>(partial, cgrid, linf, state, run.fold(1));
@@ -1116,10 +1189,19 @@ extern "C" int pgh_poly_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* 
     cp.err_kind = cfg->err_kind;
     // step k runs iteration k + 1; its check is the one of iteration k + 2
     auto enqueue_step = [&](int k) -> int {
-        PGH_TRY(run.product(run.s(2)));
+        PGH_TRY(run.product(xg));
+        const double c = coeff(k + 1);
         {
             ProfScope prof(PGH_K_COMBINE);
-            k_mm64_poly_step<<<cgrid, WG, 0, r.stream>>>(run.s(0), run.ops(), run.s(1), run.s(2), coeff(k + 1), linf, n_int, ld, b, state, partial);
+            if (cheb) {
+                // abstract_filters.py:217-223: the recurrence proper starts at iteration 3, and from there a zero coefficient adds nothing
+                // (the step's change is then 0, as the reference's unchanged result makes it)
+                const bool recur = k + 1 > 2;
+                const ChebStep q{recur ? 2.0 : 1.0, recur ? -1.0 : 0.0, c, (recur && c == 0.0) ? 0 : 1, linf};
+                k_mm64_cheb_step<<<cgrid, WG, 0, r.stream>>>(run.s(0), run.ops(), term, run.s(1), xg, q, n_int, ld, b, state, partial);
+            } else {
+                k_mm64_poly_step<<<cgrid, WG, 0, r.stream>>>(run.s(0), run.ops(), run.s(1), xg, c, linf, n_int, ld, b, state, partial);
+            }
         }
         Close64 c2 = cp;
         c2.check = loop_checks_at(cfg->err_kind, k + 2, cfg->max_iters, cfg->end_modulo) ? 1 : 0;
@@ -1131,5 +1213,16 @@ extern "C" int pgh_poly_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* 
     PGH_TRY(run.run_ahead(max_steps, enqueue_step));
     return run.finish(false, run.s(1), cfg, out_scales, nullptr, result->data, 2, results);
 }
+}  // namespace
 
+extern "C" int pgh_poly_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
+                                      const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results) {
+    return closed_form_batch64(g, p, coeffs, num_coeffs, result, cfg, out_scales, results, false, "pgh_poly_run_batch_f64");
+}
+extern "C" int pgh_cheb_run_batch_f64(pgh_graph_t g, pgh_mat_t p, const double* coeffs, int32_t num_coeffs, pgh_mat_t result,
+                                      const pgh_loop_cfg* cfg, const double* out_scales, pgh_loop_result* results) {
+    return closed_form_batch64(g, p, coeffs, num_coeffs, result, cfg, out_scales, results, true, "pgh_cheb_run_batch_f64");
+}
+
+// (one registration per translation unit loads its code object: k_mm64_cheb_step comes with its siblings)
 PGH_WARM_KERNEL(k_mm64_fixup)

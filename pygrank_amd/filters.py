@@ -16,6 +16,7 @@ Two execution routes, both on the GPU:
     ``convergence.iteration`` are those of the generic route.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -37,6 +38,14 @@ def _device_graph(M):
 def _f64_image_usable(g):
     """The engine's f64 image serves square graphs that carry the blocked layout (csrc/pgh_bsf64.hip bsf64_usable)."""
     return g is not None and g.shape[0] == g.shape[1] and g.shape[0] > 0 and g.nnz > 0 and "row-major" not in g.format()
+
+
+def _cheb_in_f32():
+    """PGH_CHEB_F32=1 (read per call, as csrc/pgh_spmv.hip pgh_poly_run reads it): the single-vector "chebyshev" loop runs in f32"""
+    try:
+        return int(os.environ.get("PGH_CHEB_F32", "0")) != 0
+    except ValueError:
+        return False
 
 
 def _batch_call(ranker, plain, retiring, args, switch="retire"):
@@ -63,7 +72,7 @@ def _batch_info(results, stages):
             for r in results]
 
 
-def _propagate_in_chunks(ranker, features, cfg, run, f64=False, raw=False):
+def _propagate_in_chunks(ranker, features, cfg, run, f64=False, raw=False, form=None):
     """signals.py:225-226 (one rank() per feature column) as multi-seed device loops of up to 64 columns: per-column L1 norms
     (abstract_filters.py:52-55; zero columns stay zero), preserve_norm factors, the loop started from p (:56), ConvergenceManager's
     verdict per non-zero column.  run(P, R, cfg_ref, scales, results[, in_norms]) -> what _batch_call returns for one call of
@@ -71,13 +80,16 @@ def _propagate_in_chunks(ranker, features, cfg, run, f64=False, raw=False):
     quotients and residuals in f64, the tolerance is clamped at fp64 eps (_f64_cfg), the column norms go in beside the chunk and every
     record of ``last_batches`` carries "f64": True.  raw (f64 only): the chunk goes in UN-normalised, as _f64_operands hands a single
     vector to the f64 route (the recursive filters); otherwise L1-normalised in f32.  A retiring run's report is recorded under "stages".
+    form (f64 only): a closed-form filter's form that runs in f64 at EVERY tolerance ("chebyshev", include/pgh_cheb64.h): the tolerance
+    is clamped at fp64 eps only where a single rank() clamps it there (the run wants f64 iterates), and the records carry "form".
     Returns the [n, B] ranks, or None when the engine declined the first chunk (nothing was run)."""
     from pygrank_amd.device import DeviceMatrix
     F = features if isinstance(features, DeviceMatrix) else backend.to_primitive(features)
     if not isinstance(F, DeviceMatrix):
         F = DeviceMatrix.from_columns([F])
-    if f64:
+    if f64 and (form is None or ranker._f64_wanted()):
         cfg = ranker._f64_cfg(cfg)
+    marks = dict(f64=True) if form is None else dict(f64=True, form=form)
     cfg.start_from_p = 1                                                          # ranks start as a copy of p (:56)
     batches = []
     out = DeviceMatrix.empty(F.n, F.b) if F.b > 64 else None
@@ -100,7 +112,7 @@ def _propagate_in_chunks(ranker, features, cfg, run, f64=False, raw=False):
         if status == L.DECLINED and not batches:
             return None
         L.check(status)
-        batches.append([dict(record, f64=True) for record in _batch_info(results, stages)] if f64 else _batch_info(results, stages))
+        batches.append([dict(record, **marks) for record in _batch_info(results, stages)] if f64 else _batch_info(results, stages))
         ranker.last_batches = batches
         for r, nrm in zip(results, norms):
             if nrm != 0:
@@ -127,8 +139,9 @@ class GraphFilter(NodeRanking):
         take its f32 multi-seed route, PageRank, AbsorbingWalks, SymmetricAbsorbingRandomWalks and the taylor form of the closed-form
         filters run chunks of up to 64 columns through the f64 multi-seed loops of include/pgh_batch64.h instead of one f64 loop per
         column; ``last_batches`` records carry "f64": True.  A column may differ from the column loop's in its last bits (the row sums
-        are grouped differently).  Not served -- today's route: graph_dropout, the "chebyshev" form, warm starts, AlgorithmSelection's
-        mixed groups, LFPR; ``retire=`` is ignored by the f64 batch, whose own switch is ``f64_retire=`` of PageRank, AbsorbingWalks
+        are grouped differently).  The closed-form filters' "chebyshev" form, f64 at every tolerance, runs such chunks through
+        include/pgh_cheb64.h whatever the run wants (ClosedFormGraphFilter.propagate).  Not served -- today's route: graph_dropout,
+        warm starts, AlgorithmSelection's mixed groups, LFPR; ``retire=`` is ignored by the f64 batch, whose own switch is ``f64_retire=`` of PageRank, AbsorbingWalks
         and SymmetricAbsorbingRandomWalks (include/pgh_retire64.h)."""
         if dtype not in (None, "float32", "float64"):
             raise Exception("dtype is None (f32, f64 below fp32 eps), 'float32' or 'float64'")
@@ -246,15 +259,16 @@ class GraphFilter(NodeRanking):
     def _prepare_graph(self, graph, *args, **kwargs):
         return graph
 
-    def _batch_graph(self, graph, args, kwargs, allowed=(), f64=False):
+    def _batch_graph(self, graph, args, kwargs, allowed=(), f64=False, always_f64=False):
         """The device graph of a multi-seed loop (include/pgh_batch.h) for propagate(graph, ..., *args, **kwargs), or None where a single
         rank() would not run the f32 fused loop: extra arguments, graph_dropout, f64 iterates (dtype or a tolerance below fp32 eps), a
         personalization transform, a stopping rule the engine cannot evaluate, a non-square / row-major / empty or non-device graph.
         f64: the same question for the f64 multi-seed loops (include/pgh_batch64.h) -- the run must WANT f64 iterates and the filter
-        must have been built with f64_batch=True; everything else is judged alike."""
+        must have been built with f64_batch=True; everything else is judged alike.  always_f64: a form whose single rank() is f64 at
+        every tolerance (the "chebyshev" form): what the run wants is not asked."""
         if args or any(k not in allowed and not (k == "graph_dropout" and not kwargs[k]) for k in kwargs):
             return None
-        if self._loop_cfg() is None or self._f64_wanted() != f64 or (f64 and not getattr(self, "f64_batch", False)):
+        if self._loop_cfg() is None or (f64 and not getattr(self, "f64_batch", False)) or (self._f64_wanted() != f64 and not always_f64):
             return None
         transform = self.personalization_transform
         if not (isinstance(transform, Tautology) and transform.ranker is None) or type(self)._prepare_graph is not GraphFilter._prepare_graph:
@@ -264,12 +278,12 @@ class GraphFilter(NodeRanking):
             return None
         return g
 
-    def _propagate_batched(self, features, graph_of, cfg_of, entries, pack, raw=False, usable=None):
+    def _propagate_batched(self, features, graph_of, cfg_of, entries, pack, raw=False, usable=None, form=None):
         """propagate's multi-seed routes in their order: the f64 loops (include/pgh_batch64.h), then the f32 ones (include/pgh_batch.h).
         A route the filter names in `entries` is taken when graph_of(f64) names its device graph, the library exports its entry and
         usable(g) (if given) agrees; it ends the search unless the engine DECLINED its first chunk.  entries[f64]: (the plain entry's
         name, its retiring sibling's or None -- then _batch_call is not asked); pack(g, P, R, cfg_ref, scales, results[, in_norms]) ->
-        the call's arguments; cfg_of() -> a fresh loop configuration; raw: _propagate_in_chunks'.  Returns the ranks, or None: the
+        the call's arguments; cfg_of() -> a fresh loop configuration; raw, form: _propagate_in_chunks'.  Returns the ranks, or None: the
         column loop is the caller's."""
         for f64 in (True, False):
             if f64 not in entries:
@@ -284,7 +298,7 @@ class GraphFilter(NodeRanking):
                 if retiring is None:
                     return entry(*pack(g, *operands)), None
                 return _batch_call(self, entry, retiring, pack(g, *operands), switch="f64_retire" if f64 else "retire")
-            out = _propagate_in_chunks(self, features, cfg_of(), run, f64=f64, raw=raw)
+            out = _propagate_in_chunks(self, features, cfg_of(), run, f64=f64, raw=raw, form=form)
             if out is not None:
                 return out
         return None
@@ -1399,12 +1413,17 @@ class ClosedFormGraphFilter(GraphFilter):
     def propagate(self, graph, features, *args, **kwargs):
         """signals.py:225-226 (one rank() per feature column) as multi-seed batches of up to 64 columns through pgh_poly_run_batch
         (include/pgh_batch.h) wherever a single rank() would run the f32 taylor loop of pgh_poly_run: the adjacency is streamed once
-        per term for the whole batch and every column stops at its own iteration.  The column loop otherwise (the "chebyshev" form,
-        an optimisation dict, overridden hooks, f64 iterates ...).  With f64_batch=True a taylor run that wants f64 iterates goes
+        per term for the whole batch and every column stops at its own iteration.  The column loop otherwise (the "chebyshev" form
+        without f64_batch, an optimisation dict, overridden hooks, f64 iterates ...).  With f64_batch=True a taylor run that wants f64 iterates goes
         through pgh_poly_run_batch_f64 (include/pgh_batch64.h) the same way, its personalizations L1-normalised in f32 as a single
-        rank() normalises them."""
+        rank() normalises them.  The "chebyshev" form, whose single rank() is f64 at every tolerance, goes through
+        pgh_cheb_run_batch_f64 (include/pgh_cheb64.h) with f64_batch=True whatever the tolerance -- not under PGH_CHEB_F32=1, which
+        puts the single-vector loop on f32 -- and its ``last_batches`` records carry "form": "chebyshev"; without f64_batch it keeps
+        the column loop."""
         own = ClosedFormGraphFilter
-        if not (self.coefficient_type == "taylor" and self.optimization_dict is None and self.krylov_dims is None and type(self)._step is own._step
+        cheb = self.coefficient_type == "chebyshev"
+        if not ((self.coefficient_type == "taylor" or (cheb and self.f64_batch and not _cheb_in_f32()))
+                and self.optimization_dict is None and self.krylov_dims is None and type(self)._step is own._step
                 and type(self)._recursion is own._recursion and type(self)._start is own._start
                 and type(self)._retrieve_power is own._retrieve_power and type(self)._prepare is own._prepare):
             return super().propagate(graph, features, *args, **kwargs)
@@ -1414,8 +1433,13 @@ class ClosedFormGraphFilter(GraphFilter):
             if not coeffs:
                 coeffs.append(np.asarray(self._coefficient_schedule(max(int(self.convergence.max_iters) - 1, 0)), dtype=np.float64))
             return g._h, P._h, coeffs[0].ctypes.data_as(C.c_void_p), len(coeffs[0]), R._h, cfg_ref, scales, results
-        out = self._propagate_batched(features, lambda f64: self._batch_graph(graph, args, kwargs, f64=f64), lambda: self._loop_cfg(0.0, False, 1.0),
-                                      {True: ("pgh_poly_run_batch_f64", None), False: ("pgh_poly_run_batch", None)}, pack)
+        cfg_of = lambda: self._loop_cfg(0.0, False, 1.0)                          # noqa: E731
+        if cheb:
+            out = self._propagate_batched(features, lambda f64: self._batch_graph(graph, args, kwargs, f64=True, always_f64=True), cfg_of,
+                                          {True: ("pgh_cheb_run_batch_f64", None)}, pack, form="chebyshev")
+        else:
+            out = self._propagate_batched(features, lambda f64: self._batch_graph(graph, args, kwargs, f64=f64), cfg_of,
+                                          {True: ("pgh_poly_run_batch_f64", None), False: ("pgh_poly_run_batch", None)}, pack)
         return out if out is not None else super().propagate(graph, features, *args, **kwargs)
 
 

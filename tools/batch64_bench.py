@@ -19,6 +19,11 @@ third f64 route ("f64_retire") beside the two; --stages prints its report (stage
 to stderr; --routes names the routes to time (default: all).  PGH_MM64_PAIR=0 in the environment keeps the four-lane product in the
 ld == 2 stages.
 
+--form chebyshev (with --filter heat) times the "chebyshev" form: its f64 batch (include/pgh_cheb64.h) against one single-vector f64
+loop per column.  That form has no f32 multi-seed loop, so no "f32_batch" is timed.  For --filter heat, either form,
+"f64_batch_ms_per_step" is the batch's median divided by its device steps (the most iterations of a column, less the two that need
+no product).
+
     python tools/batch64_bench.py --scale 23 --columns 64 --filter ppr [--tol 1e-10] [--retire] [--stages] [--out profiles/batch64/...log]
 """
 import argparse
@@ -41,6 +46,7 @@ def main():
     ap.add_argument("--columns", type=int, default=64)
     ap.add_argument("--seeds", type=int, default=20)
     ap.add_argument("--filter", choices=("ppr", "heat", "absorbing"), default="ppr")
+    ap.add_argument("--form", choices=("taylor", "chebyshev"), default="taylor")
     ap.add_argument("--tol", type=float, default=1e-10)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default=None)
@@ -50,6 +56,9 @@ def main():
     args = ap.parse_args()
     if not 1 <= args.columns <= 64:
         raise SystemExit("--columns: 1 to 64 (one multi-seed run)")
+    cheb = args.form == "chebyshev"
+    if cheb and args.filter != "heat":
+        raise SystemExit("--form chebyshev: a closed-form filter (--filter heat)")
 
     import pygrank_amd as pg
     from pygrank_amd import _lib as L
@@ -60,6 +69,8 @@ def main():
         raise SystemExit("the engine library lacks the entries of include/pgh_batch64.h")
     if args.retire is not None and (args.filter == "heat" or L.entry("pgh_ppr_run_batch_f64_retire") is None):
         raise SystemExit("--retire: the recursive filters, and a library with the entries of include/pgh_retire64.h")
+    if cheb and L.entry("pgh_cheb_run_batch_f64") is None:
+        raise SystemExit("the engine library lacks the entry of include/pgh_cheb64.h")
     timer = Timer(L)
 
     adj = rmat_graph(args.scale, args.ef, seed=0, symmetrize=True, a=0.57, b=0.19, c=0.19)
@@ -77,7 +88,9 @@ def main():
         rule = dict(error_type=pg.L1, tol=tol, max_iters=5000, f64_batch=f64_batch, **kw)
         if args.filter == "ppr":
             return pg.PageRank(0.85, **dict(dict(dtype="float64"), **rule))
-        return pg.HeatKernel(3, **rule) if args.filter == "heat" else pg.AbsorbingWalks(**rule)
+        if args.filter == "heat":
+            return pg.HeatKernel(3, **dict(rule, coefficient_type=args.form))
+        return pg.AbsorbingWalks(**rule)
 
     def run(r, batched):
         out = r.propagate(adj, F)
@@ -89,6 +102,8 @@ def main():
 
     routes = dict(f64_batch=lambda: run(ranker(True), True), f64_columns=lambda: run(ranker(False), False),
                   f32_batch=lambda: run(ranker(False, tol=1e-6, dtype="float32"), None))
+    if cheb:
+        del routes["f32_batch"]
     if args.retire is not None:
         routes["f64_retire"] = lambda: run(ranker(True, f64_retire=args.retire or True), True)
     if args.routes:
@@ -100,7 +115,7 @@ def main():
             if rep:
                 samples[name].append(ms)
     times = {name: summary(got) for name, got in samples.items()}
-    out = dict(tool="batch64_bench", filter=args.filter, tol=args.tol, scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz),
+    out = dict(tool="batch64_bench", filter=args.filter, **(dict(form=args.form) if cheb else {}), tol=args.tol, scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz),
                columns=args.columns, seeds=args.seeds, reps=args.reps)
 
     def worst_ulp(x, y):
@@ -119,6 +134,8 @@ def main():
     if both:
         ratio = times["f64_batch"]["median_ms"] / times["f64_columns"]["median_ms"]
         out.update(f64_batch_over_f64_columns=round(ratio, 4), verdict="win" if ratio < 1.0 else "LOSS")
+    if args.filter == "heat" and "f64_batch" in seen and max(seen["f64_batch"][0]) > 2:
+        out["f64_batch_ms_per_step"] = round(times["f64_batch"]["median_ms"] / (max(seen["f64_batch"][0]) - 2), 4)
     if "f64_retire" in seen:
         stages = seen["f64_retire"][2]
         out.update(retire_levels=args.retire or "default", pair=os.environ.get("PGH_MM64_PAIR", "1") != "0", stages=stages)
