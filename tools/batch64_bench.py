@@ -10,8 +10,8 @@ symmetrised RMAT graph built on the device with --columns seed sets of --seeds n
 all under error_type=L1 and --tol (1e-10).  For orientation the f32 multi-seed loop of the same filter at tol 1e-6 is timed beside them
 ("f32_batch"): it runs fewer iterations and is no substitute.
 
-Every figure is the median of --reps (9) runs timed with pgh_timer_* (events on the engine's stream, host work between the launches
-included) in ONE process, the routes alternating, after a warm-up run of each; min..max is the spread.  The batch's per-column iteration
+Every figure is the median of --reps (9) runs timed as tools/benchkit.py fixes it (pgh_timer_* events, ONE process, the routes
+alternating after a warm-up round of each); min..max is the spread.  The batch's per-column iteration
 counts and the largest difference between the two f64 routes' values, in f32 ulps, are reported with the times.  Needs an MI355X: there is no fallback.
 
 --retire [levels ...] times the retiring f64 batch (``f64_retire=``, include/pgh_retire64.h; no levels: the engine's default list) as a
@@ -27,16 +27,14 @@ no product).
     python tools/batch64_bench.py --scale 23 --columns 64 --filter ppr [--tol 1e-10] [--retire] [--stages] [--out profiles/batch64/...log]
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from tune_bench import Timer, summary  # noqa: E402
+from benchkit import alternate, emit, engine, nodes_with_edges, over, rmat, seed_columns  # noqa: E402
 
 
 def main():
@@ -60,29 +58,16 @@ def main():
     if cheb and args.filter != "heat":
         raise SystemExit("--form chebyshev: a closed-form filter (--filter heat)")
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if L.entry("pgh_ppr_run_batch_f64") is None:
-        raise SystemExit("the engine library lacks the entries of include/pgh_batch64.h")
+    pg, L, timer = engine("pgh_ppr_run_batch_f64", what="the entries of include/pgh_batch64.h")
     if args.retire is not None and (args.filter == "heat" or L.entry("pgh_ppr_run_batch_f64_retire") is None):
         raise SystemExit("--retire: the recursive filters, and a library with the entries of include/pgh_retire64.h")
     if cheb and L.entry("pgh_cheb_run_batch_f64") is None:
         raise SystemExit("the engine library lacks the entry of include/pgh_cheb64.h")
-    timer = Timer(L)
 
-    adj = rmat_graph(args.scale, args.ef, seed=0, symmetrize=True, a=0.57, b=0.19, c=0.19)
+    adj = rmat(args, symmetrize=True)
     n = adj.array.shape[0]
-    nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
-    rng = np.random.default_rng(1)
-    columns = []
-    for _ in range(args.columns):
-        p = np.zeros(n)
-        p[rng.choice(nodes, size=min(args.seeds, len(nodes)), replace=False)] = 1.0
-        columns.append(pg.DeviceVector.from_host(p))
-    F = pg.DeviceMatrix.from_columns(columns)
+    columns = seed_columns(pg, n, nodes_with_edges(pg, adj), args.columns, args.seeds, np.random.default_rng(1))
+    F = pg.DeviceMatrix.from_columns(columns)                 # (the columns stay allocated: part of the pool's state under the timed runs)
 
     def ranker(f64_batch, tol=args.tol, **kw):
         rule = dict(error_type=pg.L1, tol=tol, max_iters=5000, f64_batch=f64_batch, **kw)
@@ -108,13 +93,7 @@ def main():
         routes["f64_retire"] = lambda: run(ranker(True, f64_retire=args.retire or True), True)
     if args.routes:
         routes = {name: fn for name, fn in routes.items() if name in args.routes}
-    samples, seen = {name: [] for name in routes}, {}
-    for rep in range(args.reps + 1):                         # (the first round warms every code object and pooled block up)
-        for name, fn in routes.items():
-            ms, seen[name] = timer.time(fn)
-            if rep:
-                samples[name].append(ms)
-    times = {name: summary(got) for name, got in samples.items()}
+    times, seen = alternate(timer, routes, args.reps)
     out = dict(tool="batch64_bench", filter=args.filter, **(dict(form=args.form) if cheb else {}), tol=args.tol, scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz),
                columns=args.columns, seeds=args.seeds, reps=args.reps)
 
@@ -141,7 +120,7 @@ def main():
         out.update(retire_levels=args.retire or "default", pair=os.environ.get("PGH_MM64_PAIR", "1") != "0", stages=stages)
         for other in ("f64_batch", "f64_columns"):
             if other in seen:
-                out["f64_retire_over_" + other] = round(times["f64_retire"]["median_ms"] / times[other]["median_ms"], 4)
+                out["f64_retire_over_" + other] = over(times["f64_retire"], times[other])
                 out["f64_retire_worst_difference_from_%s_f32_ulp" % other] = worst_ulp("f64_retire", other)
         if "f64_batch" in seen:
             out["same_iterations_as_f64_batch"] = seen["f64_retire"][0] == seen["f64_batch"][0]
@@ -151,12 +130,7 @@ def main():
                 print("stage: ld %2d, %2d live columns, from step %d" % (ld, live, first), file=sys.stderr)
             print("slab columns streamed: %d (the plain f64 batch: %s)" % (stages["column_steps"], out.get("plain_column_steps", "not run")),
                   file=sys.stderr)
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

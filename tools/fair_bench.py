@@ -8,8 +8,8 @@ sensitive group:
                   multi-seed loop, evaluate_many scores the columns;
   (b) sequential: the same candidates one by one through `loss` -- the reference's route (fairness.py:123-132), what batch=False runs.
 
-Both routes are timed with pgh_timer_* (events on the engine's stream, host work between the launches included) in ONE process,
-alternating, after a warm-up step; medians and min..max spreads over steps x repetitions are reported, with the call of pgh_prior_edit
+Both routes are timed with the Timer of tools/benchkit.py (pgh_timer_*) in ONE process, alternating, after a warm-up step; medians and
+min..max spreads over steps x repetitions are reported (its loop is its own: a step's candidates change), with the call of pgh_prior_edit
 alone and its GB/s (bytes from shapes: 12 n read, 4 n probes written).  Needs an MI355X: there is no fallback.
 
 --tol is the base ranker's tolerance: the run for the original scores stops by it and fixes the iteration count of every candidate's run.
@@ -17,16 +17,14 @@ alone and its GB/s (bytes from shapes: 12 n read, 4 n probes written).  Needs an
     python tools/fair_bench.py --scale 23 --steps 8 [--reps 3] [--tol 1e-6] [--out profiles/fairness/fair_bench_scale23.log]
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from tune_bench import Timer, summary  # noqa: E402
+from benchkit import disjoint, emit, engine, nodes_with_edges, over, rmat, seed_vector, summary  # noqa: E402
 
 
 def main():
@@ -40,20 +38,12 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
     from pygrank_amd import autotune
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if L.entry("pgh_prior_edit") is None:
-        raise SystemExit("the engine library lacks pgh_prior_edit")
-    adj = rmat_graph(args.scale, args.ef, seed=0, normalization="col", a=0.57, b=0.19, c=0.19)
+    pg, _, timer = engine("pgh_prior_edit")
+    adj = rmat(args, normalization="col")
     n = adj.array.shape[0]
-    nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
     rng = np.random.default_rng(1)
-    p = np.zeros(n)
-    p[np.sort(rng.choice(nodes, size=min(args.seeds, len(nodes)), replace=False))] = 1.0
+    p = seed_vector(n, nodes_with_edges(pg, adj), args.seeds, rng)
     s = np.zeros(n)
     s[rng.choice(n, n // 5, replace=False)] = 1.0
     signal, sensitive = pg.to_signal(adj, p), pg.to_signal(adj, s)
@@ -64,7 +54,6 @@ def main():
     hi, lo, partitions = [1, 1, 5, 5, personalizer.max_residual], [0, 0, -5, -5, 0], 10
     weights = [(a + b) / 2 for a, b in zip(lo, hi)]
     ranges = [(b - a) / 2 for a, b in zip(lo, hi)]
-    timer = Timer(L)
 
     def step_candidates(variable):
         ranges[variable] /= 2
@@ -94,16 +83,10 @@ def main():
     out = dict(tool="fair_bench", scale=args.scale, edge_factor=args.ef, n=int(n), seeds=args.seeds, tol=args.tol,
                max_residual=personalizer.max_residual, steps=args.steps,
                reps=args.reps, candidates_per_step=partitions, iterations_per_run=iterations, batched=a, sequential=b, prior_edit_call=e,
-               ratio_batched_over_sequential=round(a["median_ms"] / b["median_ms"], 4),
-               spreads_disjoint=bool(a["max_ms"] < b["min_ms"] or b["max_ms"] < a["min_ms"]),
+               ratio_batched_over_sequential=over(a, b), spreads_disjoint=disjoint(a, b),
                edit_bytes=int(edit_bytes), prior_edit_gbps=round(edit_bytes / (e["median_ms"] * 1e-3) / 1e9, 1),
                largest_loss_difference_between_routes=worst, routes=dict(personalizer.last_fit))
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -12,14 +12,13 @@ bench.py draws them:
             (= run / (columns - 1): the way in, the division of the columns and the way out amortised over the steps);
   parameter_tuner   for orientation, ONE ParameterTuner.tune on the same graph and seeds (its default search: hundreds of probes).
 
-Every figure but the last is the median of --reps (9) runs timed with pgh_timer_* (events on the engine's stream, host work between the
-launches included) in ONE process, the routes alternating, after a warm-up run of each; min..max is the spread, and
+Every figure but the last is the median of --reps (9) runs timed as tools/benchkit.py fixes it (pgh_timer_* events, ONE process, the
+routes alternating after a warm-up round of each); min..max is the spread, and
 `spreads_disjoint` says whether the spreads of the two routes compared separate.  Needs an MI355X: there is no fallback.
 
     python tools/hop_bench.py --scale 23 --params 20 [--basis krylov|arnoldi] [--measure cos|auc] [--out profiles/hop/hop_bench_scale23_k20_krylov_cos.log]
 """
 import argparse
-import json
 import os
 import sys
 import warnings
@@ -27,24 +26,8 @@ import warnings
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from tune_bench import Timer, summary  # noqa: E402
-
-
-def disjoint(a, b):
-    return bool(a["max_ms"] < b["min_ms"] or b["max_ms"] < a["min_ms"])
-
-
-def alternate(timer, routes, reps):
-    """{name: summary} of `reps` timed runs of every route, the routes alternating, after one warm-up round; the last value of each."""
-    samples, last = {name: [] for name in routes}, {}
-    for rep in range(reps + 1):                              # (the first round warms every code object and pooled block up)
-        for name, once in routes.items():
-            ms, last[name] = timer.time(once)
-            if rep:
-                samples[name].append(ms)
-    return {name: summary(got) for name, got in samples.items()}, last
+from benchkit import alternate, disjoint, emit, engine, nodes_with_edges, over, rmat, seed_vector  # noqa: E402
 
 
 def sweep_spmm(pg, g, halves, hops):
@@ -73,24 +56,13 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
+    pg, L, timer = engine("pgh_basis_dots", "pgh_arnoldi_close", what="the entries of include/pgh_arnoldi.h")
     from pygrank_amd import krylov
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if L.entry("pgh_basis_dots") is None or L.entry("pgh_arnoldi_close") is None:
-        raise SystemExit("the engine library lacks the entries of include/pgh_arnoldi.h")
     warnings.simplefilter("ignore")
-    timer = Timer(L)
 
-    adj = rmat_graph(args.scale, args.ef, seed=0, normalization="symmetric", symmetrize=True, a=0.57, b=0.19, c=0.19)
+    adj = rmat(args, normalization="symmetric", symmetrize=True)
     n = adj.array.shape[0]
-    rng = np.random.default_rng(1)
-    nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
-    p = np.zeros(n)
-    p[np.sort(rng.choice(nodes, size=min(args.seeds, len(nodes)), replace=False))] = 1.0
-    signal = pg.to_signal(adj, p)
+    signal = pg.to_signal(adj, seed_vector(n, nodes_with_edges(pg, adj), args.seeds, np.random.default_rng(1)))
     measure = pg.Cos if args.measure == "cos" else pg.AUC
 
     # ---- a whole tune
@@ -133,7 +105,7 @@ def main():
         if took != dict(fused="fused", primitive="primitive"):
             raise SystemExit(f"arnoldi_iteration took {took}")
         arnoldi[str(columns)] = dict(ms_per_run=got, ms_per_step={name: round(s["median_ms"] / (columns - 1), 4) for name, s in got.items()},
-                                     fused_over_primitive=round(got["fused"]["median_ms"] / got["primitive"]["median_ms"], 4),
+                                     fused_over_primitive=over(got["fused"], got["primitive"]),
                                      spreads_disjoint=disjoint(got["fused"], got["primitive"]))
 
     # ---- for orientation: one ParameterTuner.tune
@@ -149,17 +121,12 @@ def main():
 
     out = dict(tool="hop_bench", scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz), seeds=args.seeds, params=args.params,
                basis=args.basis, measure=args.measure, reps=args.reps, ms_per_tune=tune_ms,
-               fused_over_primitive_tune=round(tune_ms["fused"]["median_ms"] / tune_ms["primitive"]["median_ms"], 4),
+               fused_over_primitive_tune=over(tune_ms["fused"], tune_ms["primitive"]),
                tune_spreads_disjoint=disjoint(tune_ms["fused"], tune_ms["primitive"]),
-               ms_per_sweep=sweep_ms, spmm_over_steps_sweep=round(sweep_ms["spmm"]["median_ms"] / sweep_ms["steps"]["median_ms"], 4),
+               ms_per_sweep=sweep_ms, spmm_over_steps_sweep=over(sweep_ms["spmm"], sweep_ms["steps"]),
                sweep_spreads_disjoint=disjoint(sweep_ms["spmm"], sweep_ms["steps"]), sweep_routes_max_abs_difference=worst,
                arnoldi=arnoldi, parameter_tuner=parameter_tuner)
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

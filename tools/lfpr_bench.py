@@ -11,23 +11,21 @@ draws them and a random fifth of the nodes as the sensitive group
             device image on every call as the reference does, and with preprocessor(normalization="none", assume_immutability=True),
             which builds it once (the run that builds it is not timed).
 
-Every figure is the median of --reps (9) runs timed with pgh_timer_* (events on the engine's stream, host work between the launches
-included) in ONE process, the routes alternating, after a warm-up run of each; min..max is the spread.  Needs an MI355X: there is no
+Every figure is the median of --reps (9) runs timed as tools/benchkit.py fixes it (pgh_timer_* events, ONE process, the routes
+alternating after a warm-up round of each); min..max is the spread.  Needs an MI355X: there is no
 fallback.
 
     python tools/lfpr_bench.py --scale 23 [--redistributor original] [--out profiles/lfpr/lfpr_bench_scale23.log]
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from tune_bench import Timer, summary  # noqa: E402
+from benchkit import alternate, emit, engine, over, rmat, sample, seed_vector, summary  # noqa: E402
 
 SHORT, LONG = 6, 16
 
@@ -44,24 +42,15 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if L.entry("pgh_lfpr_close") is None:
-        raise SystemExit("the engine library lacks pgh_lfpr_close")
-    timer = Timer(L)
+    pg, _, timer = engine("pgh_lfpr_close")
 
     def operands(graph, n, degrees):
         rng = np.random.default_rng(1)
-        nodes = np.flatnonzero(degrees > 0)
-        p, s = np.zeros(n), np.zeros(n)
-        p[np.sort(rng.choice(nodes, size=min(args.seeds, len(nodes)), replace=False))] = 1.0
+        p, s = seed_vector(n, np.flatnonzero(degrees > 0), args.seeds, rng), np.zeros(n)
         s[rng.choice(n, n // 5, replace=False)] = 1.0
         return pg.to_signal(graph, p), pg.to_signal(graph, s)
 
-    adj = rmat_graph(args.scale, args.ef, seed=0, normalization="none", symmetrize=True, a=0.57, b=0.19, c=0.19)
+    adj = rmat(args, normalization="none", symmetrize=True)
     n = adj.array.shape[0]
     signal, sensitive = operands(adj, n, np.asarray(pg.degrees(adj.array)))
 
@@ -81,64 +70,55 @@ def main():
 
     routes = dict(lfpr_fused=lambda **k: run(lfpr(True, **k)), lfpr_primitives=lambda **k: run(lfpr(False, **k)),
                   pagerank_primitives=lambda **k: run(pagerank(**k), False))
+
     # (the step rows always use the uniform redistributor: the redistributor enters _start only, and the inner PageRank of "original"
     # shares the manager, whose "iters" count it would use up)
-    samples = {name: {SHORT: [], LONG: []} for name in routes}
-    for rep in range(args.reps + 1):                         # (the first round warms every code object and pooled block up)
-        for name, make in routes.items():
-            for iters in (SHORT, LONG):
-                kwargs = dict(error_type="iters", max_iters=iters, **({} if name == "pagerank_primitives" else dict(redistributor=None)))
-                ms, ranker = timer.time(lambda: make(**kwargs))
-                assert ranker.convergence.iteration == iters
-                if rep:
-                    samples[name][iters].append(ms)
-    step = {name: summary([(b - a) / (LONG - SHORT) for a, b in zip(got[SHORT], got[LONG])]) for name, got in samples.items()}
+    def fixed(name, iters):
+        kwargs = dict(error_type="iters", max_iters=iters, **({} if name == "pagerank_primitives" else dict(redistributor=None)))
+        return lambda: routes[name](**kwargs)
 
-    rank = {}
-    rank_samples = {name: [] for name in ("lfpr_fused", "lfpr_primitives")}
+    def ran_them_all(key, ranker):
+        assert ranker.convergence.iteration == key[1]
+    samples, _ = sample(timer, {(name, iters): fixed(name, iters) for name in routes for iters in (SHORT, LONG)}, args.reps, ran_them_all,
+                        keep=False)
+    step = {name: summary([(b - a) / (LONG - SHORT) for a, b in zip(samples[(name, SHORT)], samples[(name, LONG)])]) for name in routes}
+
+    def stopped(name):
+        return lambda: routes[name](error_type=pg.L1, tol=args.tol, max_iters=1000)
     iterations = {}
-    for rep in range(args.reps + 1):
-        for name in rank_samples:
-            ms, ranker = timer.time(lambda: routes[name](error_type=pg.L1, tol=args.tol, max_iters=1000))
-            iterations[name] = int(ranker.convergence.iteration)
-            if rep:
-                rank_samples[name].append(ms)
-    for name, got in rank_samples.items():
-        rank[name] = dict(summary(got), iterations=iterations[name])
+
+    def count(name, ranker):
+        iterations[name] = int(ranker.convergence.iteration)
+    rank, _ = alternate(timer, {name: stopped(name) for name in ("lfpr_fused", "lfpr_primitives")}, args.reps, count, keep=False)
+    for name in rank:
+        rank[name].update(iterations=iterations[name])
 
     image_scale = min(args.scale, 20) if args.image_scale is None else args.image_scale
-    small = rmat_graph(image_scale, args.ef, seed=0, normalization="none", symmetrize=True, a=0.57, b=0.19, c=0.19)
+    small = rmat(argparse.Namespace(scale=image_scale, ef=args.ef), normalization="none", symmetrize=True)
     host = small.array.download_transposed().tocsr()         # (symmetric: M^T is M)
     graph = pg.AdjacencyWrapper(host, directed=False)
     del small
     signal2, sensitive2 = operands(graph, host.shape[0], np.asarray(host.sum(axis=1)).ravel())
     remembered = pg.preprocessor(normalization="none", assume_immutability=True)
-    image_samples = dict(rebuilt_per_rank=[], remembered=[])
-    for rep in range(args.reps + 1):
-        for name, extra in (("rebuilt_per_rank", {}), ("remembered", dict(preprocessor=remembered))):
-            def once():
-                ranker = lfpr(True, error_type=pg.L1, tol=args.tol, max_iters=1000, **extra)
-                np.asarray(ranker.rank(graph, signal2, sensitive=sensitive2).np[0])
-                return ranker
-            ms, ranker = timer.time(once)
-            if rep:
-                image_samples[name].append(ms)
-    image = {name: summary(got) for name, got in image_samples.items()}
+
+    def on_host_graph(**extra):
+        def once():
+            ranker = lfpr(True, error_type=pg.L1, tol=args.tol, max_iters=1000, **extra)
+            np.asarray(ranker.rank(graph, signal2, sensitive=sensitive2).np[0])
+            return ranker
+        return once
+    image, _ = alternate(timer, dict(rebuilt_per_rank=on_host_graph(), remembered=on_host_graph(preprocessor=remembered)), args.reps,
+                         keep=False)
 
     out = dict(tool="lfpr_bench", scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz), seeds=args.seeds,
                redistributor=args.redistributor or "uniform", reps=args.reps, tol=args.tol, step_from_iterations=[SHORT, LONG],
                ms_per_step=step, ms_per_rank=rank,
-               fused_over_primitives_step=round(step["lfpr_fused"]["median_ms"] / step["lfpr_primitives"]["median_ms"], 4),
-               fused_over_primitives_rank=round(rank["lfpr_fused"]["median_ms"] / rank["lfpr_primitives"]["median_ms"], 4),
-               fused_step_over_pagerank_primitive_step=round(step["lfpr_fused"]["median_ms"] / step["pagerank_primitives"]["median_ms"], 4),
+               fused_over_primitives_step=over(step["lfpr_fused"], step["lfpr_primitives"]),
+               fused_over_primitives_rank=over(rank["lfpr_fused"], rank["lfpr_primitives"]),
+               fused_step_over_pagerank_primitive_step=over(step["lfpr_fused"], step["pagerank_primitives"]),
                image=dict(scale=image_scale, n=int(host.shape[0]), nnz=int(host.nnz), ms_per_rank=image,
-                          remembered_over_rebuilt=round(image["remembered"]["median_ms"] / image["rebuilt_per_rank"]["median_ms"], 4)))
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+                          remembered_over_rebuilt=over(image["remembered"], image["rebuilt_per_rank"])))
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ slab of --columns columns of random scores in [0, 1) (three in ten are zeros: ti
   (b) host:    fused=False -- the slab is downloaded (n x columns doubles) and the same restatement runs in numpy.
 
 Both are timed with time.perf_counter around evaluate (the device route synchronises before it returns) in ONE process, alternating,
-after a warm-up of each that also builds the plan; medians and min..max over the repetitions are reported, and a route counts as faster
+after a warm-up of each that also builds the plan (the sampler of tools/benchkit.py on this wall clock); medians and min..max over the repetitions are reported, and a route counts as faster
 only when the two min..max intervals are disjoint.  The plan -- the sample, the BFS balls and the pair list, numpy on the host CSR -- is
 built once per instance and shared by every evaluation; its construction is timed apart, on fresh instances (--plan-reps).  The
 device route's stages are not timed one by one here.  Needs an MI355X: there is no fallback.
@@ -15,9 +15,7 @@ device route's stages are not timed one by one here.  Needs an MI355X: there is 
     python tools/link_bench.py --scale 20 --columns 64 [--hops 1] [--similarity cos|dot] [--reps 9] [--plan-reps 3] [--out FILE]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 import time
 import warnings
@@ -26,16 +24,16 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-
-def summary(samples):
-    return dict(median_ms=round(statistics.median(samples), 4), min_ms=round(min(samples), 4), max_ms=round(max(samples), 4),
-                samples=len(samples))
+from benchkit import alternate, disjoint, emit, engine, over, summary  # noqa: E402
 
 
-def timed(fn):
-    start = time.perf_counter()
-    value = fn()
-    return (time.perf_counter() - start) * 1e3, value
+class WallClock:
+    """benchkit.Timer's `time` on the host's clock."""
+    @staticmethod
+    def time(fn):
+        start = time.perf_counter()
+        value = fn()
+        return (time.perf_counter() - start) * 1e3, value
 
 
 def main():
@@ -52,14 +50,10 @@ def main():
         raise SystemExit("at least 5 repetitions")
 
     import scipy.sparse as sp
-    import pygrank_amd as pg
     from oracle import rmat_np
     from pygrank_amd import _lib as L
     from pygrank_amd.device import DeviceMatrix
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if any(L.entry(name) is None for name in L.LINK_SIGNATURES):
-        raise SystemExit("the engine library lacks the entries of include/pgh_link.h")
+    pg, _, _ = engine(*L.LINK_SIGNATURES, what="the entries of include/pgh_link.h")
     warnings.simplefilter("ignore")
     A = rmat_np.rmat_csr(args.scale, 8, seed=3)
     A = sp.csr_array(A + A.T)
@@ -74,31 +68,21 @@ def main():
     kwargs = dict(hops=args.hops, similarity=args.similarity)
     plan_ms = []
     for _ in range(max(1, args.plan_reps)):
-        ms, plan = timed(pg.LinkAssessment(graph, **kwargs).plan)
+        ms, plan = WallClock.time(pg.LinkAssessment(graph, **kwargs).plan)
         plan_ms.append(ms)
     device, host = pg.LinkAssessment(graph, **kwargs), pg.LinkAssessment(graph, fused=False, **kwargs)
     runs = dict(device=lambda: device.evaluate(slab), host=lambda: host.evaluate(slab))
-    values = {key: run() for key, run in runs.items()}       # warm-up: the plans, the device scratch, every code object
+    times, values = alternate(WallClock, runs, args.reps)     # (the warm-up round builds the plans, the device scratch, every code object)
     assert (device.last_route, host.last_route) == ("device", "host")
-    samples = {key: [] for key in runs}
-    for _ in range(args.reps):
-        for key, run in runs.items():
-            ms, values[key] = timed(run)
-            samples[key].append(ms)
     out = dict(tool="link_bench", scale=args.scale, n=n, nnz=int(A.nnz), columns=b, hops=args.hops, similarity=args.similarity,
                reps=args.reps, pairs=plan.num_pairs, positives=plan.num_positive, candidates=len(plan.candidates),
-               plan_build=summary(plan_ms), device=summary(samples["device"]), host=summary(samples["host"]),
+               plan_build=summary(plan_ms), device=times["device"], host=times["host"],
                slab_download_bytes=n * b * 8)
-    out["device_over_host"] = round(out["device"]["median_ms"] / out["host"]["median_ms"], 5)
-    out["spreads_disjoint"] = bool(out["device"]["max_ms"] < out["host"]["min_ms"] or out["host"]["max_ms"] < out["device"]["min_ms"])
+    out["device_over_host"] = over(out["device"], out["host"], 5)
+    out["spreads_disjoint"] = disjoint(out["device"], out["host"])
     out["values_equal"] = bool(values["device"] == values["host"])
     out["auc"] = values["device"]
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -9,42 +9,23 @@ maximum: values in [0, 1], as Normalize("max") leaves a propagate result.
                   pgh_reduce (max), pgh_ewise_vs (max_rank - s), two pgh_spmv, four pgh_dot.  The columns are taken out of the slab
                   before the clock starts.
 
-Both routes are timed with pgh_timer_* (events on the engine's stream, host work between the launches included) in ONE process,
-alternating, after a warm-up of each; medians and min..max over the repetitions are reported, with the largest relative difference
-between the two routes' Conductance values.  The slab route counts as faster only when the two min..max intervals are disjoint.
+Both routes are timed as tools/benchkit.py fixes it (pgh_timer_* events, ONE process, the routes alternating after a warm-up round of
+each); medians and min..max over the repetitions are reported, with the largest relative difference between the two routes'
+Conductance values.  The slab route counts as faster only when the two min..max intervals are disjoint.
 Needs an MI355X: there is no fallback.
 
     python tools/measure_bench.py --scale 23 --columns 64 [--reps 5] [--out FILE]
 """
 import argparse
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-
-class Timer:
-    def __init__(self, L):
-        self.L, self.lib, self.h = L, L.lib(), L.c_timer()
-        L.check(self.lib.pgh_timer_create(C.byref(self.h)))
-
-    def time(self, fn):
-        self.L.check(self.lib.pgh_timer_start(self.h))
-        value = fn()
-        self.L.check(self.lib.pgh_timer_stop(self.h))
-        ms = C.c_double()
-        self.L.check(self.lib.pgh_timer_elapsed_ms(self.h, C.byref(ms)))
-        return ms.value, value
-
-
-def summary(samples):
-    return dict(median_ms=round(statistics.median(samples), 4), min_ms=round(min(samples), 4), max_ms=round(max(samples), 4),
-                samples=len(samples))
+from benchkit import alternate, disjoint, emit, engine, over, seed_vector  # noqa: E402
 
 
 def conductance(forms):
@@ -65,25 +46,17 @@ def main():
     if args.reps < 5:
         raise SystemExit("at least 5 repetitions")
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
+    _, L, timer = engine("pgh_mat_col_stats", "pgh_cut_forms", what="the entries of include/pgh_measure.h")
     from pygrank_amd.device import DeviceMatrix, DeviceVector
     from pygrank_amd.synthetic import rmat_device_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    stats_fn, forms_fn = L.entry("pgh_mat_col_stats"), L.entry("pgh_cut_forms")
-    if stats_fn is None or forms_fn is None:
-        raise SystemExit("the engine library lacks the entries of include/pgh_measure.h")
-    lib = L.lib()
+    stats_fn, forms_fn, lib = L.entry("pgh_mat_col_stats"), L.entry("pgh_cut_forms"), L.lib()
     g = rmat_device_graph(args.scale, args.ef, seed=0, normalization="none")
     n, b = g.shape[0], args.columns
     candidates = np.flatnonzero(np.asarray(g.degrees()) > 0)
     rng = np.random.default_rng(1)
     seeds = DeviceMatrix.empty(n, b)
     for j in range(b):
-        p = np.zeros(n)
-        p[rng.choice(candidates, size=min(args.seeds, len(candidates)), replace=False)] = 1.0
-        seeds.set_column(j, DeviceVector.from_host(p))
+        seeds.set_column(j, DeviceVector.from_host(seed_vector(n, candidates, args.seeds, rng)))
     hops = g.conv(g.conv(seeds)) if b <= 64 else None
     if hops is None:
         raise SystemExit("at most 64 columns")
@@ -93,7 +66,6 @@ def main():
     del seeds, hops
     columns = scores.columns()
     max_rank = 1.0
-    timer = Timer(L)
 
     def slab():
         stats, forms = np.empty((b, 4)), np.empty((b, 4))
@@ -127,17 +99,15 @@ def main():
             out.append(conductance([dot(near, s), dot(near, rest), dot(far, s), dot(far, rest)]))
         return out
 
-    slab(), slab_internal(), per_column()                     # warm-up: the multi-seed image, the pool's blocks, every code object
-    a_ms, d_ms, b_ms, worst = [], [], [], 0.0
-    for _ in range(args.reps):
-        ms, got_a = timer.time(slab)
-        a_ms.append(ms)
-        ms, got_b = timer.time(per_column)
-        b_ms.append(ms)
-        ms, _ = timer.time(slab_internal)
-        d_ms.append(ms)
-        worst = max(worst, max(abs(x - y) / abs(y) for x, y in zip(got_a, got_b) if np.isfinite(y) and y != 0))
-    a, d, per = summary(a_ms), summary(d_ms), summary(b_ms)
+    seen = dict(worst=0.0)
+
+    def compare(name, got):
+        if name == "slab":
+            seen["slab"] = got
+        elif name == "per_column":                            # the slab route of the same round against it
+            seen["worst"] = max(seen["worst"], max(abs(x - y) / abs(y) for x, y in zip(seen["slab"], got) if np.isfinite(y) and y != 0))
+    times, _ = alternate(timer, dict(slab=slab, per_column=per_column, slab_internal=slab_internal), args.reps, compare)
+    a, d, per, worst = times["slab"], times["slab_internal"], times["per_column"], seen["worst"]
     chunks = -(-b // 32)
     width = 2 * ((min(b, 32) + 3) & ~3)
     # bytes from shapes: the statistics read the slab; per chunk the pack reads its columns and writes X, the forms read X and Y
@@ -146,16 +116,10 @@ def main():
     out = dict(tool="measure_bench", scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(info["nnz"]), columns=b, reps=args.reps,
                seeds_per_column=args.seeds, slab_conductance=a, slab_density=d, per_column_conductance=per,
                graph_passes=dict(slab=chunks, per_column=2 * b),
-               ratio_slab_over_per_column=round(a["median_ms"] / per["median_ms"], 4),
-               spreads_disjoint=bool(a["max_ms"] < per["min_ms"] or per["max_ms"] < a["min_ms"]),
+               ratio_slab_over_per_column=over(a, per), spreads_disjoint=disjoint(a, per),
                slab_stream_bytes_outside_the_graph_pass=int(slab_bytes),
                largest_relative_difference_between_routes=worst, graph_format=g.format())
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

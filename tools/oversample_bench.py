@@ -9,23 +9,21 @@ among the nodes with edges:
   round      ms per round's slab passes -- resample, the three sums, the update with the next floor -- and of the first floor, on
              [n, columns] slabs through include/pgh_oversample.h (fused) and from backend primitives (fused=False).
 
-Every figure is the median of --reps (9) runs timed with pgh_timer_* (events on the engine's stream, host work between the launches
-included) in ONE process, the routes alternating, after a warm-up run of each; min..max is the spread.  Needs an MI355X: there is no
+Every figure is the median of --reps (9) runs timed as tools/benchkit.py fixes it (pgh_timer_* events, ONE process, the routes
+alternating after a warm-up round of each); min..max is the spread.  Needs an MI355X: there is no
 fallback.
 
     python tools/oversample_bench.py --scale 23 --columns 64 [--objective naive] [--source original] [--retire] [--out profiles/oversampling/...log]
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from tune_bench import Timer, summary  # noqa: E402
+from benchkit import alternate, emit, engine, nodes_with_edges, over, rmat, seed_columns  # noqa: E402
 
 
 def main():
@@ -41,27 +39,12 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
+    pg, _, timer = engine("pgh_boost_update")
     from pygrank_amd.oversampling import _SlabPasses
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if L.entry("pgh_boost_update") is None:
-        raise SystemExit("the engine library lacks pgh_boost_update")
-    timer = Timer(L)
 
-    adj = rmat_graph(args.scale, args.ef, seed=0, symmetrize=True, a=0.57, b=0.19, c=0.19)
+    adj = rmat(args, symmetrize=True)
     n = adj.array.shape[0]
-    nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
-    rng = np.random.default_rng(1)
-    columns = []
-    for _ in range(args.columns):
-        p = np.zeros(n)
-        p[rng.choice(nodes, size=min(args.seeds, len(nodes)), replace=False)] = 1.0
-        columns.append(pg.DeviceVector.from_host(p))
-    F = pg.DeviceMatrix.from_columns(columns)
-    del columns
+    F = pg.DeviceMatrix.from_columns(seed_columns(pg, n, nodes_with_edges(pg, adj), args.columns, args.seeds, np.random.default_rng(1)))
 
     def boosted(**kwargs):
         ranker = pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000, retire=args.retire)
@@ -73,73 +56,67 @@ def main():
         out.column(0)[0]                                     # noqa: B018 -- the result is there
         return algo
 
-    samples = dict(batch=[], one_by_one=[])
-    rounds = {}
-    for rep in range(args.reps + 1):                         # (the first round warms every code object and pooled block up)
-        for name, kwargs in (("batch", dict(min_batch_width=2)), ("one_by_one", dict(batch=False))):
-            ms, algo = timer.time(lambda: run(**kwargs))
-            rounds[name] = list(algo.last_rounds)
-            widths = algo.last_widths
-            if name == "batch":
-                batch_widths = widths[0]
-                assert algo.last_passes["primitive"] == 0
-            if rep:
-                samples[name].append(ms)
+    rounds, widths = {}, {}
+
+    def what_it_ran(name, algo):
+        rounds[name], widths[name] = list(algo.last_rounds), algo.last_widths
+        assert name != "batch" or algo.last_passes["primitive"] == 0
+    propagate, _ = alternate(timer, dict(batch=lambda: run(min_batch_width=2), one_by_one=lambda: run(batch=False)), args.reps,
+                             what_it_ran, keep=False)
+    batch_widths = widths["batch"][0]
     assert rounds["batch"] == rounds["one_by_one"], (rounds["batch"], rounds["one_by_one"])
-    propagate = {name: summary(got) for name, got in samples.items()}
 
     # what a round spends most of its time in: the inner ranker on the seed sets, as one multi-seed run and as a single rank()
     ranker = pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000, retire=args.retire)
     first = pg.to_signal(adj, F.column(0))
-    inner_samples = dict(propagate=[], rank=[])
-    for rep in range(args.reps + 1):
-        ms_many, _ = timer.time(lambda: ranker.propagate(adj, F).column(0)[0])
-        many_iterations = [r["iterations"] for r in ranker.last_batches[0]] if getattr(ranker, "last_batches", None) else []
-        ms_one, _ = timer.time(lambda: ranker.rank(adj, first).np[0])
-        one_iterations = int(ranker.convergence.iteration)
-        if rep:
-            inner_samples["propagate"].append(ms_many)
-            inner_samples["rank"].append(ms_one)
-    inner = dict(propagate=dict(summary(inner_samples["propagate"]), iterations_min=min(many_iterations, default=0),
-                                iterations_max=max(many_iterations, default=0)),
-                 rank=dict(summary(inner_samples["rank"]), iterations=one_iterations))
+    counts = {}
+
+    def iterations(name, _):                                 # (the ranker is shared: each route's count is read before the other runs)
+        if name == "propagate":
+            counts[name] = [r["iterations"] for r in ranker.last_batches[0]] if getattr(ranker, "last_batches", None) else []
+        else:
+            counts[name] = int(ranker.convergence.iteration)
+    inner, _ = alternate(timer, dict(propagate=lambda: ranker.propagate(adj, F).column(0)[0], rank=lambda: ranker.rank(adj, first).np[0]),
+                         args.reps, iterations)
+    inner["propagate"].update(iterations_min=min(counts["propagate"], default=0), iterations_max=max(counts["propagate"], default=0))
+    inner["rank"].update(iterations=counts["rank"])
 
     # one round's passes on full-width slabs: the ranks of the seed sets as `total`, a second copy as `fresh`
     ranker = pg.PageRank(0.9, error_type=pg.L1, tol=1e-6, max_iters=1000)
     total = ranker.propagate(adj, F)
     fresh = ranker.propagate(adj, F)
     weights = [0.01] * F.b
-    pass_samples = dict(fused=dict(floor=[], round=[]), primitives=dict(floor=[], round=[]))
-    for rep in range(args.reps + 1):
-        for name, fused in (("fused", True), ("primitives", False)):
-            passes = _SlabPasses(fused)
-            ms_floor, (floors, counts) = timer.time(lambda: passes.floor(total, F))
+    names = ("fused", "primitives")
+    passes, floors = {name: _SlabPasses(name == "fused") for name in names}, []
 
-            def one_round():
-                grown, _ = passes.resample(total, floors)
-                passes.forms(grown, fresh, total)
-                return passes.update(total, fresh, weights, grown)
-            ms_round, _ = timer.time(one_round)
-            assert passes.calls == (dict(fused=4, primitive=0) if fused else dict(fused=0, primitive=4))
-            if rep:
-                pass_samples[name]["floor"].append(ms_floor)
-                pass_samples[name]["round"].append(ms_round)
-    per_round = {name: {what: summary(got) for what, got in both.items()} for name, both in pass_samples.items()}
+    def one_round(name):
+        grown, _ = passes[name].resample(total, floors[0])
+        passes[name].forms(grown, fresh, total)
+        return passes[name].update(total, fresh, weights, grown)
+
+    def between(key, value):                                 # a route's floor feeds its round; every round counts its four passes anew
+        name, what = key
+        if what == "floor":
+            floors[:] = [value[0]]
+        else:
+            assert passes[name].calls == (dict(fused=4, primitive=0) if name == "fused" else dict(fused=0, primitive=4))
+            passes[name] = _SlabPasses(name == "fused")
+    routes = {}
+    for name in names:
+        routes[(name, "floor")] = lambda name=name: passes[name].floor(total, F)
+        routes[(name, "round")] = lambda name=name: one_round(name)
+    got, _ = alternate(timer, routes, args.reps, between, keep=False)
+    per_round = {name: dict(floor=got[(name, "floor")], round=got[(name, "round")]) for name in names}
 
     out = dict(tool="oversample_bench", scale=args.scale, edge_factor=args.ef, n=int(n), nnz=int(adj.array.nnz), columns=args.columns,
                seeds=args.seeds, objective=args.objective, source=args.source, reps=args.reps, retire=args.retire,
                rounds=dict(min=min(rounds["batch"]), max=max(rounds["batch"]), total=sum(rounds["batch"])), batch_widths=batch_widths,
                ms_per_propagate=propagate,
-               batch_over_one_by_one=round(propagate["batch"]["median_ms"] / propagate["one_by_one"]["median_ms"], 4),
+               batch_over_one_by_one=over(propagate["batch"], propagate["one_by_one"]),
                ms_per_inner_run=inner, ms_per_round_passes=per_round,
-               fused_over_primitives_round=round(per_round["fused"]["round"]["median_ms"] / per_round["primitives"]["round"]["median_ms"], 4),
-               fused_over_primitives_floor=round(per_round["fused"]["floor"]["median_ms"] / per_round["primitives"]["floor"]["median_ms"], 4))
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+               fused_over_primitives_round=over(per_round["fused"]["round"], per_round["primitives"]["round"]),
+               fused_over_primitives_floor=over(per_round["fused"]["floor"], per_round["primitives"]["floor"]))
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

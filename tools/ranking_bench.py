@@ -11,8 +11,8 @@ rows:
                 and ranked by numpy on the host).  --baseline-columns C scores only the first C columns on this route (the host ranking
                 of 2^23 rows takes seconds per column); both routes are also reported per column.
 
-All are timed with pgh_timer_* (events on the engine's stream, host work between the launches included) in ONE process, alternating,
-after a warm-up of each; medians and min..max over the repetitions are reported.  pgh_mat_col_stats (include/pgh_measure.h), the plain
+All are timed as tools/benchkit.py fixes it (pgh_timer_* events, ONE process, the routes alternating after a warm-up round of each);
+medians and min..max over the repetitions are reported.  pgh_mat_col_stats (include/pgh_measure.h), the plain
 read of the same slab, is timed alongside as the yardstick of the streaming pass.  A route counts as faster only when the two min..max
 intervals (per column) are disjoint.  Needs an MI355X: there is no fallback.
 
@@ -20,7 +20,6 @@ intervals (per column) are disjoint.  Needs an MI355X: there is no fallback.
 """
 import argparse
 import ctypes as C
-import json
 import os
 import statistics
 import sys
@@ -29,32 +28,16 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from benchkit import disjoint, emit, engine, sample, summary  # noqa: E402
+
 ROOFLINE_GBPS = 8000.0
+PER_COLUMN = dict(lo="min_ms_per_column", hi="max_ms_per_column")
 
 
-class Timer:
-    def __init__(self, L):
-        self.L, self.lib, self.h = L, L.lib(), L.c_timer()
-        L.check(self.lib.pgh_timer_create(C.byref(self.h)))
-
-    def time(self, fn):
-        self.L.check(self.lib.pgh_timer_start(self.h))
-        value = fn()
-        self.L.check(self.lib.pgh_timer_stop(self.h))
-        ms = C.c_double()
-        self.L.check(self.lib.pgh_timer_elapsed_ms(self.h, C.byref(ms)))
-        return ms.value, value
-
-
-def summary(samples, columns):
-    median = statistics.median(samples)
-    return dict(median_ms=round(median, 4), min_ms=round(min(samples), 4), max_ms=round(max(samples), 4), samples=len(samples),
-                columns=columns, median_ms_per_column=round(median / columns, 5), min_ms_per_column=round(min(samples) / columns, 5),
-                max_ms_per_column=round(max(samples) / columns, 5))
-
-
-def disjoint(a, b):
-    return bool(a["max_ms_per_column"] < b["min_ms_per_column"] or b["max_ms_per_column"] < a["min_ms_per_column"])
+def per_column(samples, columns):
+    """benchkit's summary, and the same three figures per column (from the samples, not from the rounded figures)."""
+    return dict(summary(samples), columns=columns, median_ms_per_column=round(statistics.median(samples) / columns, 5),
+                min_ms_per_column=round(min(samples) / columns, 5), max_ms_per_column=round(max(samples) / columns, 5))
 
 
 def main():
@@ -70,14 +53,10 @@ def main():
     if args.reps < 5:
         raise SystemExit("at least 5 repetitions")
 
-    import pygrank_amd as pg
     from pygrank_amd import _lib as L
+    pg, L, timer = engine(*L.RANK_SIGNATURES, what="the entries of include/pgh_rank.h")
     from pygrank_amd import measures
     from pygrank_amd.device import DeviceMatrix, DeviceVector
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if any(L.entry(name) is None for name in L.RANK_SIGNATURES):
-        raise SystemExit("the engine library lacks the entries of include/pgh_rank.h")
     n, b = 1 << args.scale, args.columns
     few = b if args.baseline_columns is None else min(b, args.baseline_columns)
     rng = np.random.default_rng(1)
@@ -89,7 +68,6 @@ def main():
     host_known = np.zeros(n, dtype=np.float32)
     host_known[rng.choice(n, min(args.relevant, n), replace=False)] = rng.choice([0.25, 0.5, 1.0], min(args.relevant, n))
     known = DeviceVector.from_host(host_known)
-    timer = Timer(L)
     stats_fn = L.entry("pgh_mat_col_stats")
     k = 1000 if args.measure == "ndcg" else None
     measure = pg.NDCG(known, k=k) if args.measure == "ndcg" else pg.SpearmanCorrelation(known)
@@ -126,37 +104,26 @@ def main():
     runs = dict(slab=(slab_route, b), columns=(columns_route, few), pgh_mat_col_stats=(col_stats, b))
     if args.measure == "ndcg":
         runs["slab_sorted_route"] = (sorted_route, b)
-    for run, _ in runs.values():                             # warm-up: the plan, the pool's blocks, every code object
-        run()
-    samples, values = {key: [] for key in runs}, {}
-    for _ in range(args.reps):
-        for key, (run, _) in runs.items():
-            ms, values[key] = timer.time(run)
-            samples[key].append(ms)
+    samples, values = sample(timer, {key: run for key, (run, _) in runs.items()}, args.reps)
     plan = measure._plan_cache[4]
     stream_bytes = n * b * 4 + n
     out = dict(tool="ranking_bench", measure=args.measure, scale=args.scale, n=n, columns=b, baseline_columns=few, relevant=plan.num_relevant,
                k=k, reps=args.reps, stream_bytes=stream_bytes, roofline_gbps=ROOFLINE_GBPS)
     for key, (_, width) in runs.items():
-        out[key] = summary(samples[key], width)
+        out[key] = per_column(samples[key], width)
     gbps = stream_bytes / (out["slab"]["median_ms"] * 1e-3) / 1e9
     out["slab"].update(gbps=round(gbps, 1), share_of_roofline=round(gbps / ROOFLINE_GBPS, 4))
     out["pgh_mat_col_stats"]["gbps"] = round(n * b * 4 / (out["pgh_mat_col_stats"]["median_ms"] * 1e-3) / 1e9, 1)
     out["slab_over_columns_per_column"] = round(out["slab"]["median_ms_per_column"] / out["columns"]["median_ms_per_column"], 5)
-    out["spreads_disjoint"] = disjoint(out["slab"], out["columns"])
+    out["spreads_disjoint"] = disjoint(out["slab"], out["columns"], **PER_COLUMN)
     out["slab_over_col_stats"] = round(out["slab"]["median_ms"] / out["pgh_mat_col_stats"]["median_ms"], 3)
     if args.measure == "ndcg":
         out["streaming_over_sorted"] = round(out["slab"]["median_ms"] / out["slab_sorted_route"]["median_ms"], 5)
-        out["streaming_sorted_spreads_disjoint"] = disjoint(out["slab"], out["slab_sorted_route"])
+        out["streaming_sorted_spreads_disjoint"] = disjoint(out["slab"], out["slab_sorted_route"], **PER_COLUMN)
         out["largest_difference_streaming_sorted"] = max(abs(x - y) for x, y in zip(values["slab"], values["slab_sorted_route"]))
     pairs = [(x, y) for x, y in zip(values["slab"][:few], values["columns"]) if np.isfinite(x) and np.isfinite(y)]
     out["largest_difference_between_routes"] = max((abs(x - y) for x, y in pairs), default=None)
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -12,24 +12,22 @@ PageRank(0.9, error_type=L1, tol=1e-6) -- the setting of tools/oversample_bench.
 --mixed: one alpha per column, from 0.5 to 0.97 (pgh_ppr_run_batch_mixed and its retiring sibling through the C-ABI; "ranks": one
 PageRank(alpha_j).rank per column).  --levels: a comma-separated level list instead of the default 32,16,8,4.
 
-Every figure is the median of --reps (9) runs timed with pgh_timer_* (events on the engine's stream, host work between the launches
-included) in ONE process, the routes alternating, after a warm-up run of each; min..max is the spread.  Needs an MI355X: there is no
+Every figure is the median of --reps (9) runs timed as tools/benchkit.py fixes it (pgh_timer_* events, ONE process, the routes
+alternating after a warm-up round of each); min..max is the spread.  Needs an MI355X: there is no
 fallback.
 
     python tools/retire_bench.py --scale 23 --columns 64 [--mixed] [--levels 48,20,12,4] [--stages] [--out profiles/retire/...log]
 """
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from tune_bench import Timer, summary  # noqa: E402
+from benchkit import alternate, emit, engine, nodes_with_edges, over, rmat, seed_columns  # noqa: E402
 
 
 def main():
@@ -48,24 +46,12 @@ def main():
         raise SystemExit("--columns: 1 to 64 (one multi-seed run)")
     levels = [32, 16, 8, 4] if args.levels is None else [int(v) for v in args.levels.split(",") if v]
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if L.entry("pgh_ppr_run_batch_mixed_retire" if args.mixed else "pgh_ppr_run_batch_retire") is None:
-        raise SystemExit("the engine library lacks the entries of include/pgh_retire.h")
-    timer = Timer(L)
+    pg, L, timer = engine("pgh_ppr_run_batch_mixed_retire" if args.mixed else "pgh_ppr_run_batch_retire",
+                          what="the entries of include/pgh_retire.h")
 
-    adj = rmat_graph(args.scale, args.ef, seed=0, symmetrize=True, a=0.57, b=0.19, c=0.19)
+    adj = rmat(args, symmetrize=True)
     n = adj.array.shape[0]
-    nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
-    rng = np.random.default_rng(1)
-    columns = []
-    for _ in range(args.columns):
-        p = np.zeros(n)
-        p[rng.choice(nodes, size=min(args.seeds, len(nodes)), replace=False)] = 1.0
-        columns.append(pg.DeviceVector.from_host(p))
+    columns = seed_columns(pg, n, nodes_with_edges(pg, adj), args.columns, args.seeds, np.random.default_rng(1))
     F = pg.DeviceMatrix.from_columns(columns)
     signals = [pg.to_signal(adj, column) for column in columns]
     alphas = [float(a) for a in np.linspace(0.5, 0.97, args.columns)] if args.mixed else [0.9] * args.columns
@@ -102,14 +88,7 @@ def main():
         out[-1].np[0]                                        # noqa: B018
         return None, None
 
-    routes = dict(retire=lambda: batch(list(levels)), plain=lambda: batch(False), ranks=ranks)
-    samples, seen = {name: [] for name in routes}, {}
-    for rep in range(args.reps + 1):                         # (the first round warms every code object and pooled block up)
-        for name, run in routes.items():
-            ms, seen[name] = timer.time(run)
-            if rep:
-                samples[name].append(ms)
-    propagate = {name: summary(got) for name, got in samples.items()}
+    propagate, seen = alternate(timer, dict(retire=lambda: batch(list(levels)), plain=lambda: batch(False), ranks=ranks), args.reps)
     iterations, stages = seen["retire"]
     plain_iterations = seen["plain"][0]
     executed = max(iterations) - 1
@@ -119,21 +98,16 @@ def main():
                iterations_differ_from_plain=sum(1 for a, b in zip(iterations, plain_iterations) if a != b),
                stages=stages, column_steps=dict(retire=stages["column_steps"], plain=stages["ld"][0] * (max(plain_iterations) - 1)),
                ms_per_propagate=propagate,
-               retire_over_plain=round(propagate["retire"]["median_ms"] / propagate["plain"]["median_ms"], 4),
-               retire_over_ranks=round(propagate["retire"]["median_ms"] / propagate["ranks"]["median_ms"], 4),
-               plain_over_ranks=round(propagate["plain"]["median_ms"] / propagate["ranks"]["median_ms"], 4))
+               retire_over_plain=over(propagate["retire"], propagate["plain"]),
+               retire_over_ranks=over(propagate["retire"], propagate["ranks"]),
+               plain_over_ranks=over(propagate["plain"], propagate["ranks"]))
 
     if args.stages:
         # prefix i of the levels: the run narrows through its first i levels only; what prefix i costs over prefix i - 1 is what the
         # deepest of its stages costs over staying in the stage before
         prefixes = [levels[:i] for i in range(len(levels) + 1)]
-        samples, reports = [[] for _ in prefixes], [None] * len(prefixes)
-        for rep in range(args.reps + 1):
-            for i, prefix in enumerate(prefixes):
-                ms, (_, reports[i]) = timer.time(lambda: batch(list(prefix)))
-                if rep:
-                    samples[i].append(ms)
-        medians = [summary(got) for got in samples]
+        medians, last = alternate(timer, {i: lambda prefix=prefix: batch(list(prefix)) for i, prefix in enumerate(prefixes)}, args.reps)
+        reports = [last[i][1] for i in range(len(prefixes))]
         per_stage, wide_step = [], medians[0]["median_ms"] / max(executed, 1)
         per_stage.append(dict(levels=[], ld=reports[0]["ld"][0], steps=executed, ms_per_step=round(wide_step, 4), run=medians[0]))
         for i in range(1, len(prefixes)):
@@ -151,12 +125,7 @@ def main():
                                   run=medians[i]))
         out["per_stage"] = per_stage
 
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ routes.  --filters demo: create_demo_filters(tol=--tol): 3 PageRanks and 3 HeatK
 default mean absolute change (on millions of nodes the default rule at tol 1e-6 ends every run within a few iterations).
 
 Both routes are timed in ONE process, alternating, after one warm-up run of each: the engine's stream events around the whole _tune
-(pgh_timer_*, host work between the launches included) and the host's wall clock around the same call (it ends synchronised: the
+(the Timer of tools/benchkit.py; the loop is this tool's own: a run builds its rankers outside the clock and reads two clocks) and the host's wall clock around the same call (it ends synchronised: the
 values are host floats).  Medians and min..max over --reps repetitions.  Both routes must select the same ranker.  Needs an MI355X.
 
 --min-width w: the batch route's min_batch_width (default 2, so that the mixed batches are what is timed at every width).
@@ -21,7 +21,6 @@ values are host floats).  Medians and min..max over --reps repetitions.  Both ro
     python tools/select_bench.py --scale 23 --filters many [--splits 1] [--reps 3] [--l1] [--out profiles/selection/NAME.log]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -29,9 +28,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from tune_bench import Timer, summary  # noqa: E402
+from benchkit import disjoint, emit, engine, nodes_with_edges, over, rmat, seed_vector, summary  # noqa: E402
 
 
 def main():
@@ -49,20 +47,11 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
-    import pygrank_amd as pg
     from pygrank_amd import _lib as L
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    for name in L.MIXED_SIGNATURES:
-        if L.entry(name) is None:
-            raise SystemExit("the engine library lacks " + name)
-    adj = rmat_graph(args.scale, args.ef, seed=0, normalization="col", a=0.57, b=0.19, c=0.19)
+    pg, _, timer = engine(*L.MIXED_SIGNATURES)
+    adj = rmat(args, normalization="col")
     n = adj.array.shape[0]
-    nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
-    p = np.zeros(n)
-    p[np.sort(np.random.default_rng(1).choice(nodes, size=min(args.seeds, len(nodes)), replace=False))] = 1.0
-    signal = pg.to_signal(adj, p)
+    signal = pg.to_signal(adj, seed_vector(n, nodes_with_edges(pg, adj), args.seeds, np.random.default_rng(1)))
     fractions = [0.9, 0.8, 0.7, 0.6, 0.5, 0.4][:args.splits]
     if len(fractions) != args.splits or args.splits < 1:
         raise SystemExit("--splits is 1 to 6")
@@ -73,8 +62,6 @@ def main():
             for ranker in rankers.values():
                 ranker.convergence.error_type = pg.L1
         return rankers
-
-    timer = Timer(L)
 
     def run(batch):
         rankers = family()
@@ -106,15 +93,9 @@ def main():
                                  loop_ms=round(c["loop_ms"], 3)) for c in mixed["mixed_calls"]],
                batch_event_ms=a, one_by_one_event_ms=b, batch_wall_ms=summary(times[True]["wall"]),
                one_by_one_wall_ms=summary(times[False]["wall"]),
-               ratio_batch_over_one_by_one=round(a["median_ms"] / b["median_ms"], 4),
-               spreads_disjoint=bool(a["max_ms"] < b["min_ms"] or b["max_ms"] < a["min_ms"]),
+               ratio_batch_over_one_by_one=over(a, b), spreads_disjoint=disjoint(a, b),
                largest_value_difference_between_routes=worst)
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

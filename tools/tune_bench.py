@@ -7,42 +7,22 @@ graphs built on the device with 100 seeds drawn as bench.py draws them (SURVEY.m
                   measures.AUC(validation, exclude=training) -- the reference's evaluation (parameterized.py:135-145), which already
                   reads the stored powers (one pgh_mat_gemv per candidate).
 
-Both routes are timed with pgh_timer_* (events on the engine's stream, host work between the launches included) in ONE process,
-alternating, after a warm-up step; medians and min..max spreads over steps x repetitions are reported, with the call of
+Both routes are timed with the Timer of tools/benchkit.py (pgh_timer_*) in ONE process, alternating, after a warm-up step; medians and
+min..max spreads over steps x repetitions are reported (its loop is its own: a step's candidates change), with the call of
 pgh_probe_auc alone and its GB/s (bytes from shapes: the 128-byte lines of every 256-byte slab row that the leading `terms` floats
 touch, plus one class byte per node).  Needs an MI355X: there is no fallback.
 
     python tools/tune_bench.py --scale 23 --steps 8 [--reps 5] [--out FILE]
 """
 import argparse
-import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-
-class Timer:
-    def __init__(self, L):
-        self.L, self.lib, self.h = L, L.lib(), L.c_timer()
-        L.check(self.lib.pgh_timer_create(C.byref(self.h)))
-
-    def time(self, fn):
-        self.L.check(self.lib.pgh_timer_start(self.h))
-        value = fn()
-        self.L.check(self.lib.pgh_timer_stop(self.h))
-        ms = C.c_double()
-        self.L.check(self.lib.pgh_timer_elapsed_ms(self.h, C.byref(ms)))
-        return ms.value, value
-
-
-def summary(samples):
-    return dict(median_ms=round(statistics.median(samples), 4), min_ms=round(min(samples), 4), max_ms=round(max(samples), 4),
-                samples=len(samples))
+from benchkit import disjoint, emit, engine, nodes_with_edges, over, rmat, seed_vector, summary  # noqa: E402
 
 
 def main():
@@ -59,21 +39,11 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
-    import pygrank_amd as pg
-    from pygrank_amd import _lib as L
     from pygrank_amd import autotune
-    from pygrank_amd.synthetic import rmat_graph
-    pg.load_backend("hip")
-    L.ensure_init()                                          # raises without an MI355X
-    if L.entry("pgh_probe_auc") is None:
-        raise SystemExit("the engine library lacks pgh_probe_auc")
-    adj = rmat_graph(args.scale, args.ef, seed=0, normalization="col", a=0.57, b=0.19, c=0.19)
+    pg, _, timer = engine("pgh_probe_auc")
+    adj = rmat(args, normalization="col")
     n = adj.array.shape[0]
-    candidates_nodes = np.flatnonzero(np.asarray(pg.degrees(adj.array)) > 0)
-    rng = np.random.default_rng(1)
-    p = np.zeros(n)
-    p[np.sort(rng.choice(candidates_nodes, size=min(args.seeds, len(candidates_nodes)), replace=False))] = 1.0
-    signal = pg.to_signal(adj, p)
+    signal = pg.to_signal(adj, seed_vector(n, nodes_with_edges(pg, adj), args.seeds, np.random.default_rng(1)))
 
     tuner = pg.ParameterTuner(verbose=False, **(dict(error_type=pg.L1) if args.l1 else {}))
     splits = tuner._splits(signal, 0)
@@ -81,7 +51,6 @@ def main():
     opt = tuner.optimize_args
     weights = [(lo + hi) / 2 for lo, hi in zip(opt["min_vals"], opt["max_vals"])]
     ranges = [(hi - lo) / 2 for lo, hi in zip(opt["min_vals"], opt["max_vals"])]
-    timer = Timer(L)
 
     def step_candidates(variable):
         ranges[variable] /= opt["divide_range"]
@@ -125,17 +94,11 @@ def main():
     stream_bytes = n * 128 * lines + n
     out = dict(tool="tune_bench", scale=args.scale, edge_factor=args.ef, n=int(n), seeds=args.seeds, steps=args.steps, reps=args.reps,
                candidates_per_step=opt["partitions"], stopping_rule="L1" if args.l1 else "default (Mabs)", terms=int(terms), fused=a, sequential=b, probe_auc_call=e,
-               ratio_fused_over_sequential=round(a["median_ms"] / b["median_ms"], 4),
-               spreads_disjoint=bool(a["max_ms"] < b["min_ms"] or b["max_ms"] < a["min_ms"]),
+               ratio_fused_over_sequential=over(a, b), spreads_disjoint=disjoint(a, b),
                stream_bytes=int(stream_bytes), probe_auc_gbps=round(stream_bytes / (e["median_ms"] * 1e-3) / 1e9, 1),
                largest_loss_difference_between_routes=worst, positives=loss._plans[0].num_positive,
                negatives=loss._plans[0].num_negative, routes=dict(tuner.last_tune))
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":
